@@ -8,6 +8,8 @@ unroll, diffpiso/combined_training_integrated.py:396-478), then back-propagates 
 Inputs are synthetic (random solenoidal velocity with E(k) ~ k^4 exp(-(k/8)^2), seed 0, u_rms = 1, nu = 1e-3,
 CFL 0.5, p0 = 0) and resident in HBM before the clock starts.  Solver settings are the reference's training settings:
 tolerance 1e-6, max_iterations 10000, CG residual_reset 1000, pressure solve fp64, advection solve fp32.
+`--dump-outputs DIR` writes what the timed K-step call returned (u_K, p_K, dL/du_0, dL/dp_0, L) as DIR/<name>.npy: the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 
 Multi-GPU (default `--decomp auto`): the headline is the SHARDED step -- ONE 2048 x (2048 N) periodic box cut into y-slabs, a
 2048^2 slab per GPU, every kernel of the step on the rank's rows (assembly, glue, Laplacian; halo rows through peer-mapped
@@ -191,9 +193,30 @@ def run_unrolled(P, steps, backward=True, clock=None, keep=None, adjoint_accurac
         if clock is not None:
             torch.cuda.synchronize()
             clock["bwd_s"] = clock.get("bwd_s", 0.0) + time.perf_counter() - t1
-    if keep is not None:          # (--dump-fields: the fields behind the loss, for the field-level parity tests of the sharded step)
+    if keep is not None:          # (--dump-fields, --dump-outputs: the fields behind the loss and the gradients of the reverse sweep)
         keep.update(u=vn.staggered_tensor().detach(), p=out[4].data.detach(), du=vel_t.grad, dp=p_t.grad)
     return vel_t.grad, float(loss.detach()), warn
+
+
+DUMP_OUTPUTS_MAX_BYTES = 60 * 10 ** 6   # --dump-outputs: all files of one run together stay below 64 MB
+
+
+def dump_outputs(dirname, fields, loss):
+    """--dump-outputs: what the timed run_unrolled call handed back, as <dirname>/<name>.npy (float32 fields, float64 loss): u_K, p_K,
+    dL/du_0, dL/dp_0 and L.  Fields that together exceed DUMP_OUTPUTS_MAX_BYTES are written as samples: the same share of every
+    field's flattened elements, at sorted positions drawn without replacement from a generator seeded with 0 - a function of the
+    shapes alone, so two builds run with the same arguments write the same elements in the same order."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: v.detach().cpu().numpy() for k, v in fields.items()}
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    rng = np.random.default_rng(0)
+    for name, a in arrays.items():
+        if total > DUMP_OUTPUTS_MAX_BYTES:
+            take = int(a.size * float(DUMP_OUTPUTS_MAX_BYTES) / total)
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, size=take, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    np.save(os.path.join(dirname, "loss.npy"), np.array([loss], np.float64))
 
 
 # tests/golden/make_golden_configs.py::TIGHT_SOLVER_2048: the settings at which two correct implementations agree to 1e-5 on this workload
@@ -799,6 +822,9 @@ def main():
                     "fixed-iteration runs of two summation orders stay comparable (DESIGN.md 4)")
     ap.add_argument("--dump-fields", default="", help="directory: every rank writes ITS rows of u_K, p_K, dL/du_0, dL/dp_0 of the timed run to "
                     "rank<r>.npz (tests/test_gpu_sharded_fields.py)")
+    ap.add_argument("--dump-outputs", default="", help="directory: after the timed steps rank 0 writes what the timed call returned - velocity.npy "
+                    "(u_K), pressure.npy (p_K), grad_velocity.npy (dL/du_0), grad_pressure.npy (dL/dp_0), loss.npy - of its problem (N > 1: its "
+                    "replica, or its rows of a sharded box), at most 64 MB in all: larger fields as a fixed seeded sample of their elements")
     ap.add_argument("--perturb-input", type=float, default=0.0, help=argparse.SUPPRESS)    # (diagnostics: relative white noise on the initial velocity)
     ap.add_argument("--self-check-child", action="store_true", help=argparse.SUPPRESS)      # (internal: one rank of the N > 1 self-check)
     ap.add_argument("--sharded-child", action="store_true", help=argparse.SUPPRESS)         # (internal: one rank of the 'auto' mode's slab-weak run)
@@ -908,11 +934,13 @@ def main():
         print("STAGE timed run (%d steps)" % args.steps, flush=True)
     barrier()
     t0 = time.perf_counter()
-    keep = {} if args.dump_fields else None
+    keep = {} if (args.dump_fields or args.dump_outputs) else None
     grad, loss, warn = run_unrolled(P, args.steps, clock=clock, keep=keep)
     barrier()
     elapsed = time.perf_counter() - t0
-    if keep:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"velocity": keep["u"], "pressure": keep["p"], "grad_velocity": keep["du"], "grad_pressure": keep["dp"]}, loss)
+    if args.dump_fields:
         sh_ = P.get("sharding")
         os.makedirs(args.dump_fields, exist_ok=True)
         if sh_ is not None:
@@ -925,7 +953,7 @@ def main():
                      u_v=keep["u"][0, j0:j1 + last, :, 0].cpu().numpy(), u_u=keep["u"][0, j0:j1, :, 1].cpu().numpy(), p=keep["p"][0, j0:j1, :, 0].cpu().numpy(),
                      du_v=keep["du"][0, j0:j1 + last, :, 0].cpu().numpy(), du_u=keep["du"][0, j0:j1, :, 1].cpu().numpy(),
                      dp=keep["dp"][0, j0:j1, :, 0].cpu().numpy())
-        del keep
+    del keep
     ms_sum = (C.c_double * 4)()
     cnt = (C.c_longlong * 4)()
     N.lib.piso_cg_profile_read(ms_sum, cnt)

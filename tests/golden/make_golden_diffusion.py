@@ -105,8 +105,10 @@ def make(name, res, h, per_yx, rng):
 
 def shift_cases(rng):
     out = {}
+    # (the *_wide cases: rows of whole 128-cell strips, which the persistent CG kernel tiles; drawn last, the others keep their numbers)
     for name, (res, boundaries) in {"periodic": ((10, 12), pf.PERIODIC), "closed": ((9, 11), pf.CLOSED),
-                                    "xper_ywall": ((16, 128), (pf.CLOSED, pf.PERIODIC))}.items():
+                                    "xper_ywall": ((16, 128), (pf.CLOSED, pf.PERIODIC)),
+                                    "periodic_wide": ((16, 128), pf.PERIODIC), "closed_wide": ((16, 128), pf.CLOSED)}.items():
         ny, nx = res
         domain = pf.Domain(list(res), boundaries=boundaries, box=pf.box[0:ny, 0:nx])
         fd = FluidDomain(domain, ())

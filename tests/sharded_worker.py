@@ -29,10 +29,6 @@ def build_case(case, device):
     import torch
     import diffpiso as dp
     kind, _, rest = case.partition(":")
-    if rest.endswith(":persist0"):                          # (more slab kernels than the ONE shared GPU holds side by side: two-kernel CG iteration)
-        import diffpiso._native as N
-        N.set_option("cg_persist", 0)
-        rest = rest[:-len(":persist0")]
     if kind == "fixture" and rest.startswith("bench"):
         import bench
         d = np.load(os.path.join(HERE, "golden", rest))

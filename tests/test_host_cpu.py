@@ -318,6 +318,30 @@ def test_build_from_a_tree_without_binaries(tmp_path):
     assert b"gfx950" in ctypes.cast(lib.piso_version, ctypes.CFUNCTYPE(ctypes.c_char_p))()
 
 
+def test_bench_dump_outputs_writes_whole_fields_or_the_same_seeded_sample_below_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs (bench.dump_outputs): fields that fit are written whole; fields over the byte cap as a sample that
+    keeps the cap, holds elements of the field in their order, and is the same elements on every call."""
+    import bench
+    gen = torch.Generator().manual_seed(3)
+    fields = {"velocity": torch.randn(1, 33, 33, 2, generator=gen), "pressure": torch.randn(1, 32, 32, 1, generator=gen, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "whole"), fields, 1.5)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["loss.npy", "pressure.npy", "velocity.npy"]
+    u, p, loss = (np.load(tmp_path / "whole" / (k + ".npy")) for k in ("velocity", "pressure", "loss"))
+    assert u.dtype == np.float32 and p.dtype == np.float64 and loss.dtype == np.float64 and loss.tolist() == [1.5]
+    assert np.array_equal(u, fields["velocity"].numpy()) and np.array_equal(p, fields["pressure"].numpy())
+    monkeypatch.setattr(bench, "DUMP_OUTPUTS_MAX_BYTES", 4096)
+    bench.dump_outputs(str(tmp_path / "s1"), fields, 1.5)
+    bench.dump_outputs(str(tmp_path / "s2"), {k: v.clone() for k, v in fields.items()}, 1.5)
+    assert sum(np.load(tmp_path / "s1" / (k + ".npy")).nbytes for k in fields) <= 4096
+    for k, v in fields.items():
+        a, b = np.load(tmp_path / "s1" / (k + ".npy")), np.load(tmp_path / "s2" / (k + ".npy"))
+        assert a.ndim == 1 and 0 < a.size < v.numel() and np.array_equal(a, b)
+        flat, at = v.numpy().reshape(-1), 0
+        for x in a:                                    # a subsequence of the flattened field
+            at += int(np.argmax(flat[at:] == x)) + 1
+            assert flat[at - 1] == x
+
+
 def test_bench_auto_policy_tries_peer_then_rccl_then_reports_replicas():
     """bench.py's `--decomp auto` policy for the N > 1 headline (bench.sharded_headline), with stub attempts: the peer transport
     first; the RCCL transport only if the environment REFUSES the peer transport and every rank has its own GPU; a refused transport
