@@ -32,6 +32,11 @@ static int g_persist_fallbacks = 0;            // solves that were restarted on 
 static thread_local int tl_xcd_map[kPersistMaxGrid];
 static thread_local int tl_xcd_map_n = 0;
 static long long g_tiny_solves = 0;            // solves that ran inside one workgroup (cg_tiny.h)
+// which kernel instance the calling thread's last solve was dispatched to (piso_cg_last_dispatch; fields: include/piso_hip.h)
+enum { DI_PATH = 0, DI_SIZEOF_T, DI_SIZEOF_CT, DI_V, DI_RECON, DI_SYMMETRIC, DI_ROWS_PER_WAVE, DI_K1_GRID, DI_K1_TILES, DI_R, DI_NQ,
+       DI_WAVES, DI_LAUNCH_GRID, DI_PADDED, DI_XCD_LOCAL, DI_FELL_BACK, DI_TINY_PER_X, DI_K2_GRID, DI_SEGMENTS, DI_COUNT };
+static thread_local int tl_dispatch[DI_COUNT];
+static thread_local int tl_dispatch_n = 0;
 static bool g_xcd_local_failed = false;        // an XCD-local launch gave up once (the device does not behave as assumed): not tried again
 static long long g_verify_runs = 0;            // solves whose final state was checked against the true residual (cg_verify_gap)
 static int g_verify_failures = 0;              // ... and failed: restarted on the two-kernel path
@@ -291,6 +296,15 @@ static int cg_run(CgArgs<T> a, unsigned* persist_ws, bool symmetric, float accur
       PISO_HIP_CHECK(hipMemsetAsync(pc.timing, 0, 12 * launch_grid * sizeof(unsigned long long), stream));
     }
   }
+  {
+    int* d = tl_dispatch;
+    for (int i = 0; i < DI_COUNT; ++i) d[i] = 0;
+    d[DI_PATH] = persist_R ? 3 : 2; d[DI_SIZEOF_T] = (int)sizeof(T); d[DI_SIZEOF_CT] = (int)sizeof(CT); d[DI_V] = V; d[DI_RECON] = RECON ? 1 : 0;
+    d[DI_SYMMETRIC] = symmetric ? 1 : 0; d[DI_ROWS_PER_WAVE] = rpw; d[DI_K1_GRID] = g1; d[DI_K1_TILES] = a.ntx * a.nty; d[DI_K2_GRID] = g2;
+    if (persist_R) { d[DI_R] = persist_R; d[DI_NQ] = persist_NQ; d[DI_WAVES] = pc.waves; d[DI_LAUNCH_GRID] = launch_grid; d[DI_XCD_LOCAL] = xcd_local ? 1 : 0; }
+    d[DI_PADDED] = ragged ? 1 : 0; d[DI_FELL_BACK] = allow_persist ? 0 : 1;
+    tl_dispatch_n = DI_COUNT;
+  }
   auto launch_segment = [&](int kb, int ke) -> int {
     // Tags are unique per launch (a 16-bit launch counter above a 16-bit exchange counter; a segment has < 2^15 exchanges): a
     // record left by an earlier launch - in memory or in some XCD's L2 - can never pass for one of this launch.  The records are
@@ -509,6 +523,7 @@ static int cg_run(CgArgs<T> a, unsigned* persist_ws, bool symmetric, float accur
     }
   }
   if (iterations_out) *iterations_out = finished ? stop_it : total;
+  tl_dispatch[DI_SEGMENTS] = segments_run;
   if (prof) {
     double ms[2] = {0, 0};
     for (int q = 0; q < 2; ++q)
@@ -544,6 +559,7 @@ template <typename T>
 static int cg_solve(int nx, int ny, int per_x, int per_y, const T* L, const T* b, T* x_out, float accuracy,
                     int max_iterations, int rank_deficient, int reset, int fixed, int* iterations_out,
                     float* kernel_ms_out, void* ws, size_t ws_bytes, piso_stream_t stream_, int* iterations_dev = nullptr) {
+  tl_dispatch_n = 0;
   if (nx < 1 || ny < 1 || !L || !b || !x_out || !ws || max_iterations < 0 || reset < 1) {
     set_error_msg("piso_cg_solve: invalid argument");
     return PISO_ERR_INVALID_ARG;
@@ -578,6 +594,10 @@ static int cg_solve(int nx, int ny, int per_x, int per_y, const T* L, const T* b
                                                  rank_deficient, st_dev, iterations_dev);
     PISO_LAUNCH_CHECK();
     ++g_tiny_solves;
+    for (int i = 0; i < DI_COUNT; ++i) tl_dispatch[i] = 0;
+    tl_dispatch[DI_PATH] = cols ? 1 : 0; tl_dispatch[DI_SIZEOF_T] = tl_dispatch[DI_SIZEOF_CT] = (int)sizeof(T);
+    tl_dispatch[DI_TINY_PER_X] = (cols && per_x) ? 1 : 0;
+    tl_dispatch_n = DI_COUNT;
     if (async) return PISO_OK;
     if (ev) PISO_HIP_CHECK(hipEventRecord(ev[1], stream));
     CgState hst;
@@ -734,6 +754,11 @@ int piso_cg_last_xcd_map(int* out, int capacity) {
   return tl_xcd_map_n;
 }
 long long piso_cg_tiny_solves(void) { return g_tiny_solves; }
+int piso_cg_last_dispatch(int* out, int capacity) {
+  const int n = tl_dispatch_n < capacity ? tl_dispatch_n : capacity;
+  for (int i = 0; i < n; ++i) out[i] = tl_dispatch[i];
+  return tl_dispatch_n;
+}
 void piso_cg_verify_stats(long long* runs_out, int* failures_out) {
   if (runs_out) *runs_out = g_verify_runs;
   if (failures_out) *failures_out = g_verify_failures;

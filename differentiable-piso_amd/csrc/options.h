@@ -1,7 +1,11 @@
 // Tuning / test knobs of libpiso_hip.so.  Every knob has a default taken ONCE, when the library is loaded, from the
 // environment variable PISO_<NAME> (upper case); afterwards only piso_set_option() changes it.  -1 = "not set / automatic".
-// None of them changes WHAT is computed: they pick between implementations that return bitwise the same result (kernel instance, staging,
-// launch shape) or switch a check / a measurement aid on and off.  Stores and loads are atomic; a call works on a snapshot (OptScope).
+// None of them changes WHAT is computed: they pick between implementations of the same arithmetic (kernel instance, staging, launch shape) or
+// switch a check / a measurement aid on and off.  Bitwise the same result: cg_no_compact, cg_no_recon, cg_no_sym, cg_nt and the bicg_* knobs
+// (same operations in the same order).  Equal to round-off only - they change which workgroup or block owns which cells, so the partial
+// sums of the dot products are grouped differently: cg_persist, cg_persist_r, cg_persist_half, cg_persist_nq, cg_xcd_local, cg_pad, cg_tiny,
+// cg_rpw, cg_maxblocks (tests/test_gpu_cg_dispatch.py holds both groups to their word).  Stores and loads are atomic; a call works on a
+// snapshot (OptScope).
 #pragma once
 
 namespace piso {

@@ -34,6 +34,8 @@ lib.piso_cg_persist_fallbacks.restype = _i
 lib.piso_cg_last_xcd_map.argtypes = [_ip, _i]
 lib.piso_cg_last_xcd_map.restype = _i
 lib.piso_cg_tiny_solves.restype = C.c_longlong
+lib.piso_cg_last_dispatch.argtypes = [_ip, _i]
+lib.piso_cg_last_dispatch.restype = _i
 lib.piso_cg_verify_stats.argtypes = [C.POINTER(C.c_longlong), _ip]
 lib.piso_cg_verify_stats.restype = None
 lib.piso_csr_nnz.argtypes = [_i, _i, _i, _i, _ip, _ip]
@@ -218,3 +220,17 @@ def cg_last_xcd_map():
     buf = (C.c_int * 256)()
     n = lib.piso_cg_last_xcd_map(buf, 256)
     return tuple(buf[i] for i in range(min(n, 256)))
+
+
+DISPATCH_FIELDS = ("path", "sizeof_T", "sizeof_CT", "V", "RECON", "symmetric", "rows_per_wave", "k1_grid", "k1_tiles", "R", "NQ", "waves",
+                   "launch_grid", "padded", "xcd_local", "fell_back", "tiny_per_x", "k2_grid", "segments")
+
+
+def cg_last_dispatch():
+    """Which kernel instance this thread's last pressure CG solve was dispatched to (include/piso_hip.h: piso_cg_last_dispatch),
+    as a dict; {} if the thread has not solved."""
+    buf = (C.c_int * 32)()
+    n = lib.piso_cg_last_dispatch(buf, 32)
+    if n != 0 and n != len(DISPATCH_FIELDS):
+        raise PisoNativeError("piso_cg_last_dispatch returned %d fields, this binding knows %d" % (n, len(DISPATCH_FIELDS)))
+    return {k: buf[i] for i, k in enumerate(DISPATCH_FIELDS[:n])}

@@ -266,6 +266,31 @@ int piso_cg_last_xcd_map(int* out, int capacity);
 /* Solves of grids of at most 4 608 cells run inside ONE workgroup, one launch for the whole solve (csrc/cg_tiny.h: the lid-driven
  * cavity of BASELINE.json's config 1); same iteration and control flow as the chip-wide paths.  Option "cg_tiny": 0 = never. */
 long long piso_cg_tiny_solves(void);
+/* Which kernel instance the calling thread's last piso_cg_solve_* / piso_cg_solve_async_* / piso_cg_fixed_iterations_* was dispatched
+ * to: out[0 .. min(return value, capacity)); returns the number of fields (0: this thread has not solved, or its last call was refused
+ * before it chose).  Read-only: the record is written on the host while the solve is set up and changes nothing that is computed.
+ * Fields, in this order (a field that does not apply to the path is 0):
+ *    0 path           0 cg_tiny, 1 cg_tiny_cols (one workgroup, cg_tiny.h), 2 the two-kernel iteration cg_k1 + cg_k2 only,
+ *                     3 persistent segments (cg_persist1) with the two-kernel pair for iteration 0 and every reset iteration
+ *    1 sizeof(T)      state type: 8 / 4
+ *    2 sizeof(CT)     type the off-diagonals are stored in: 4 when every one of them is exactly a float, else sizeof(T)
+ *    3 V              cells per lane of cg_k1 / cg_k2: 16 / sizeof(T) (rows a multiple of it, b and x 16-byte aligned) or 1
+ *    4 RECON          1: the diagonal is rebuilt from the off-diagonals instead of read
+ *    5 symmetric      1: the matrix passed the bit-for-bit symmetry check (and option cg_no_sym is off)
+ *    6 rows_per_wave  rows every wave of cg_k1 walks per tile (2 .. 16; option cg_rpw)
+ *    7 k1_grid        workgroups of cg_k1 (at most 1 024, option cg_maxblocks; rounded down to a multiple of 8 from 8 on)
+ *    8 k1_tiles       tiles of cg_k1 (column strips x groups of 4 * rows_per_wave rows): more than k1_grid -> some blocks walk several
+ *    9 R             persistent kernel: rows per region (2 / 4 / 16)
+ *   10 NQ             ... regions per working wave (1 / 2)
+ *   11 waves          ... working waves per workgroup (8, or 4: "half" workgroups, option cg_persist_half)
+ *   12 launch_grid    ... workgroups launched (XCD-local: 8 x the workgroups that work)
+ *   13 padded         1: a wall-bounded grid embedded in a larger one the persistent kernel can tile (option cg_pad)
+ *   14 xcd_local      1: the persistent solve runs on the workgroups of one XCD (option cg_xcd_local)
+ *   15 fell_back      1: the solve was restarted on the two-kernel path (exchange timed out / verification failed); path is then 2
+ *   16 tiny_per_x     cg_tiny_cols: 1 the periodic-x instance, 0 the wall-bounded one
+ *   17 k2_grid        workgroups of cg_k2
+ *   18 segments       persistent launches the solve made (0 with path 3: it ended before the first segment) */
+int piso_cg_last_dispatch(int* out, int capacity);
 /* Every fp64 solve that ran iterations inside the persistent kernel is VERIFIED before it returns: the recurrence residual r must
  * equal b - (L x + c sum x) for the returned x to 1e-5 max|b| (one extra stencil pass).  The persistent kernel publishes perimeter
  * rows without release / acquire fences; a value read before it was visible would break exactly this identity.  A failed check

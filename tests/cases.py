@@ -135,6 +135,38 @@ def product_setup(c, lin_tol=1e-5, lin_max_it=2000, lin_double=False, p_tol=1e-5
     return dict(domain=domain, sim=sim, velocity=velocity, pressure=pressure, lin=lin, ps=ps, vel_tensor=vel_t)
 
 
+def dev(a, dtype=None):
+    """A host array as a contiguous device tensor (optionally converted)."""
+    import torch
+    t = torch.as_tensor(np.ascontiguousarray(a))
+    if dtype is not None:
+        t = t.to(dtype)
+    return t.cuda()
+
+
+def laplace_case(name, ny, nx, seed, dtype=np.float64):
+    """The pressure system of a case at test size, on the host: (oracle set-up, L [nx * ny, 5] from the oracle's Laplace matrix
+    of random face weights in [0.5, 1.5), assembled in `dtype`; float64 right-hand side - zero-mean where the operator is rank
+    deficient)."""
+    from oracle import native as O, piso_ref as R
+    c = make_case(name, ny, nx, seed=seed)
+    s = oracle_setup(c)
+    rng = np.random.default_rng(seed)
+    a0_t = np.zeros((1, ny + 1, nx + 1, 2), f32)
+    a0_t[0, :, :nx, 0] = 0.5 + rng.random((ny + 1, nx))
+    a0_t[0, :ny, :, 1] = 0.5 + rng.random((ny, nx + 1))
+    if s.periodic_yx[1]:
+        a0_t[0, :ny, nx, 1] = a0_t[0, :ny, 0, 1]
+    if s.periodic_yx[0]:
+        a0_t[0, ny, :nx, 0] = a0_t[0, 0, :nx, 0]
+    L = O.laplace_matrix(nx, ny, s.active, s.accessible, R.flatten_staggered(a0_t, False), dtype)
+    act = s.active[0, 1:-1, 1:-1, 0]
+    b = rng.standard_normal((ny, nx)) * act
+    if s.rank_deficient:
+        b -= b.sum() / act.sum() * act
+    return s, L, b.ravel()
+
+
 def pressure_system(nx, ny, walls=False, seed=11):
     """A doubly periodic (or, walls=True, wall-bounded) pressure system at any size for the kernel-level CG tests and benchmarks:
     random A0 face weights in [0.5, 1.5) with consistent periodic duplicates (a symmetric matrix), the HIP Laplace matrix of it

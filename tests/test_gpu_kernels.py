@@ -7,18 +7,11 @@ import pytest
 import torch
 
 from oracle import native as O, piso_ref as R
-from tests.cases import make_case, oracle_setup
+from tests.cases import dev, laplace_case as _laplace_case, make_case, oracle_setup
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 CASES = ["periodic", "xper_ywall", "cavity", "spatial_ml"]
-
-
-def dev(a, dtype=None):
-    t = torch.as_tensor(np.ascontiguousarray(a))
-    if dtype is not None:
-        t = t.to(dtype)
-    return t.cuda()
 
 
 def assemble_gpu(c, beta):
@@ -75,36 +68,62 @@ def test_laplace_bit_exact(name, dtype):
     np.testing.assert_array_equal(L.cpu().numpy(), want)
 
 
-def _laplace_case(name, ny, nx, seed):
-    c = make_case(name, ny, nx, seed=seed)
-    s = oracle_setup(c)
-    rng = np.random.default_rng(seed)
-    a0_t = np.zeros((1, ny + 1, nx + 1, 2), f32)
-    a0_t[0, :, :nx, 0] = 0.5 + rng.random((ny + 1, nx))
-    a0_t[0, :ny, :, 1] = 0.5 + rng.random((ny, nx + 1))
-    if s.periodic_yx[1]:
-        a0_t[0, :ny, nx, 1] = a0_t[0, :ny, 0, 1]
-    if s.periodic_yx[0]:
-        a0_t[0, ny, :nx, 0] = a0_t[0, 0, :nx, 0]
-    L = O.laplace_matrix(nx, ny, s.active, s.accessible, R.flatten_staggered(a0_t, False))
-    act = s.active[0, 1:-1, 1:-1, 0]
-    b = rng.standard_normal((ny, nx)) * act
-    if s.rank_deficient:
-        b -= b.sum() / act.sum() * act
-    return s, L, b.ravel()
+def _expected_path(name, shape, path):
+    """Which kernels a solve of _laplace_case(name, *shape) runs (cg.hip: cg_solve; fields of piso_cg_last_dispatch).  path "two_kernel":
+    options cg_tiny 0 + cg_persist 0.  "default": grids of at most 4 608 cells run inside one workgroup (cg_tiny_cols where a column fits a
+    lane's registers: at most 64 columns, periodic in x only with exactly 64); above, a wall-bounded grid is padded for the persistent kernel,
+    which takes it if the diagonal can be rebuilt (not spatial_ml's), and everything else iterates on cg_k1 + cg_k2."""
+    ny, nx = shape
+    per_x = name in ("periodic", "xper_ywall")
+    recon = int(name != "spatial_ml")
+    two_kernel = dict(path=2, sizeof_T=8, sizeof_CT=4, V=2 if nx % 2 == 0 else 1, RECON=recon, symmetric=1, R=0, fell_back=0)
+    if path == "two_kernel":
+        return dict(two_kernel, padded=0)
+    if nx * ny <= 4608:
+        cols = nx <= 64 and ny <= 72 and (not per_x or nx == 64)
+        return dict(path=1 if cols else 0, sizeof_T=8, tiny_per_x=int(cols and per_x))
+    if per_x:
+        return dict(two_kernel, padded=0)
+    return dict(two_kernel, padded=1) if not recon else dict(path=3, sizeof_T=8, sizeof_CT=4, V=2, RECON=1, symmetric=1, padded=1, fell_back=0)
+
+
+def _assert_dispatch(expect):
+    from diffpiso import _native as N
+    rec = N.cg_last_dispatch()
+    assert {k: rec[k] for k in expect} == expect, rec
+
+
+def _select_path(path, piso_option):
+    if path == "two_kernel":
+        piso_option("cg_tiny", 0)
+        piso_option("cg_persist", 0)
+
+
+_TRAJECTORY_SHAPES = [((9, 8), 10), ((33, 70), 1000), ((64, 64), 200), ((65, 64), 1000), ((40, 130), 333)]
 
 
 @pytest.mark.parametrize("name", CASES)
-@pytest.mark.parametrize("shape,reset", [((9, 8), 10), ((33, 70), 1000), ((64, 64), 200), ((65, 64), 1000), ((40, 130), 333)])
-def test_cg_matches_oracle_trajectory(name, shape, reset):
+@pytest.mark.parametrize("shape,reset", _TRAJECTORY_SHAPES)
+def test_cg_matches_oracle_trajectory_two_kernel(name, shape, reset, piso_option):
+    """test_cg_matches_oracle_trajectory with every shape on cg_k1 + cg_k2 (options cg_tiny 0, cg_persist 0)."""
+    test_cg_matches_oracle_trajectory(name, shape, reset, piso_option, path="two_kernel")
+
+
+@pytest.mark.parametrize("name", CASES)
+@pytest.mark.parametrize("shape,reset", _TRAJECTORY_SHAPES)
+def test_cg_matches_oracle_trajectory(name, shape, reset, piso_option, path="default"):
     """Same algorithm, same control flow.  On the un-shifted (semi-definite, consistent) operator CG is numerically
     stable, so the GPU and the oracle follow the same trajectory: equal iteration counts (one 5-step test apart at most,
-    the fp64 dot products are summed in a different order) and equal solutions."""
+    the fp64 dot products are summed in a different order) and equal solutions.  path "default": whatever the library picks - the
+    single-workgroup kernels (cg_tiny.h) for every shape but 40 x 130; "two_kernel": the same shapes on cg_k1 + cg_k2.  Which one ran is
+    asserted from the dispatch record."""
     from diffpiso.solvers import cg_solve_native
     s, L, b = _laplace_case(name, shape[0], shape[1], seed=11)
     tol = 1e-9
     px, py = s.periodic_yx[1], s.periodic_yx[0]
+    _select_path(path, piso_option)
     x, it = cg_solve_native(s.nx, s.ny, px, py, dev(L), dev(b), tol, 3000, False, reset)
+    _assert_dispatch(_expected_path(name, shape, path))
     xo, ito = O.cg_solve(s.nx, s.ny, px, py, L, b, tol, 3000, False, reset)
     x = x.cpu().numpy()
     assert ito < 3000
@@ -116,24 +135,39 @@ def test_cg_matches_oracle_trajectory(name, shape, reset):
     assert np.abs(x - xo).max() <= 1e-6 * scale, (np.abs(x - xo).max(), scale)
     for nit in (1, 2, 7, 23):                                      # early trajectory: round-off level agreement
         x, it = cg_solve_native(s.nx, s.ny, px, py, dev(L), dev(b), 1e-30, nit, False, reset)
+        _assert_dispatch(_expected_path(name, shape, path))
         xo, ito = O.cg_solve(s.nx, s.ny, px, py, L, b, 1e-30, nit, False, reset)
         assert it == ito == nit
         assert np.abs(x.cpu().numpy() - xo).max() <= 1e-9 * np.abs(xo).max()
 
 
+_SHIFT_SHAPES = [((33, 70), 1000), ((64, 64), 10), ((65, 64), 1000)]
+
+
 @pytest.mark.parametrize("name", ["periodic", "xper_ywall"])
-@pytest.mark.parametrize("shape,reset", [((33, 70), 1000), ((64, 64), 10), ((65, 64), 1000)])
-def test_cg_rank_deficient_shift(name, shape, reset):
+@pytest.mark.parametrize("shape,reset", _SHIFT_SHAPES)
+def test_cg_rank_deficient_shift_two_kernel(name, shape, reset, piso_option):
+    """test_cg_rank_deficient_shift with every shape on cg_k1 + cg_k2 (options cg_tiny 0, cg_persist 0): the rank-1 shift of a periodic
+    grid on the two-kernel path at test size."""
+    test_cg_rank_deficient_shift(name, shape, reset, piso_option, path="two_kernel")
+
+
+@pytest.mark.parametrize("name", ["periodic", "xper_ywall"])
+@pytest.mark.parametrize("shape,reset", _SHIFT_SHAPES)
+def test_cg_rank_deficient_shift(name, shape, reset, piso_option, path="default"):
     """With the rank-1 shift the operator is indefinite (eigenvalue +cN on constants, <= 0 elsewhere): round-off in the
     constant mode is amplified and damped again along the way, so iteration counts are not reproducible between ANY two
     summation orders (cuBLAS included).  What is reproducible is the converged answer: compare that, the true residual,
-    the zero mean the shift enforces, and the stopping cadence."""
+    the zero mean the shift enforces, and the stopping cadence.  path "default": all three shapes run inside one workgroup (cg_tiny.h);
+    "two_kernel": the same shapes on cg_k1 + cg_k2 (asserted from the dispatch record)."""
     from diffpiso.solvers import cg_solve_native
     s, L, b = _laplace_case(name, shape[0], shape[1], seed=11)
     assert s.rank_deficient
     tol = 1e-9
     px, py = s.periodic_yx[1], s.periodic_yx[0]
+    _select_path(path, piso_option)
     x, it = cg_solve_native(s.nx, s.ny, px, py, dev(L), dev(b), tol, 6000, True, reset)
+    _assert_dispatch(_expected_path(name, shape, path))
     xo, ito = O.cg_solve(s.nx, s.ny, px, py, L, b, tol, 6000, True, reset)
     x = x.cpu().numpy()
     if ito < 6000:
@@ -186,6 +220,7 @@ def test_cg_persistent_segments_match_oracle(name, shape, reset, segment, rows, 
             # (beyond ~25 iterations the small grids are converged to round-off and the trajectories start to separate)
             assert np.abs(x.cpu().numpy() - xo).max() <= (1e-9 if nit <= 23 else 1e-6) * np.abs(xo).max(), nit
         assert _persist_iterations() >= 70, "the persistent kernel did not run"
+        _assert_dispatch(dict(path=3, R=rows, fell_back=0, **({} if nq < 0 else {"NQ": 1 if nq == 1 else 2})))     # ... and the instance that was forced
         tol = 1e-9
         x, it = cg_solve_native(s.nx, s.ny, px, py, dev(L), dev(b), tol, 6000, False, reset)
         xo, ito = O.cg_solve(s.nx, s.ny, px, py, L, b, tol, 6000, False, reset)
@@ -250,12 +285,21 @@ def test_cg_persistent_shift_nan_and_float32(piso_option):
         N.lib.piso_cg_profile_enable(0, 8)
 
 
+# above the single-workgroup threshold: cg_k1<float, float, 1 | 4, false> + cg_k2 (un-shifted: see test_cg_persistent_shift_nan_and_float32)
+@pytest.mark.parametrize("shape,persist,expect", [((70, 130), -1, dict(path=2, sizeof_T=4, sizeof_CT=4, V=1, RECON=0)),
+                                                  ((64, 256), 0, dict(path=2, sizeof_T=4, sizeof_CT=4, V=4, RECON=0))])
+def test_cg_float32_two_kernel_path(shape, persist, expect, piso_option):
+    test_cg_float32_path(np.float32, piso_option, shape, persist, False, expect)
+
+
 @pytest.mark.parametrize("dtype", [np.float32])
-def test_cg_float32_path(dtype):
+def test_cg_float32_path(dtype, piso_option, shape=(32, 32), persist=-1, shift=True, expect=dict(path=0, sizeof_T=4, tiny_per_x=0)):
     from diffpiso.solvers import cg_solve_native
-    s, L, b = _laplace_case("periodic", 32, 32, seed=2)
-    x, it = cg_solve_native(s.nx, s.ny, True, True, dev(L, torch.float32), dev(b, torch.float32), 1e-4, 2000, True, 1000)
-    xo, ito = O.cg_solve(s.nx, s.ny, True, True, L, b, 1e-4, 2000, True, 1000, dtype=np.float32)
+    s, L, b = _laplace_case("periodic", shape[0], shape[1], seed=2)
+    piso_option("cg_persist", persist)
+    x, it = cg_solve_native(s.nx, s.ny, True, True, dev(L, torch.float32), dev(b, torch.float32), 1e-4, 2000, shift, 1000)
+    _assert_dispatch(expect)
+    xo, ito = O.cg_solve(s.nx, s.ny, True, True, L, b, 1e-4, 2000, shift, 1000, dtype=np.float32)
     assert it < 2000 and ito < 2000
     assert np.abs(x.cpu().numpy() - xo).max() < 5e-3 * np.abs(xo).max()
 
@@ -574,3 +618,6 @@ def test_cg_persistent_float32_state_matches_oracle(name, shape, rows, segment, 
         N.lib.piso_cg_profile_enable(0, 8)
     # (one-sided couplings at open boundaries make a matrix unsymmetric: those systems iterate on the two-kernel path)
     assert ran >= 30 or rows == 16, "the persistent kernel did not run"
+    rec = N.cg_last_dispatch()
+    assert rec["sizeof_T"] == 4 and rec["V"] == 4 and rec["fell_back"] == 0
+    assert (rec["path"], rec["R"]) == (3, rows) or (rows == 16 and (rec["path"], rec["R"]) == (2, 0)), rec
