@@ -1,8 +1,7 @@
 // Host driver of the single-GPU pressure CG (kernels: cg_kernels.h).  See cg_kernels.h for the design.
 #include <atomic>
 #include "cg_kernels.h"
-#include "cg_persist.h"
-#include "cg_persist1.h"
+#include "cg_dispatch.h"
 #include "cg_tiny.h"
 #include "options.h"
 #include <cstdio>
@@ -19,12 +18,12 @@ struct CgProfile {
   long long count[4] = {0, 0, 0, 0};    // launches of K1, K2; ITERATIONS executed inside persistent segments; segment LAUNCHES
 };
 static CgProfile g_prof;
-constexpr size_t kPersistWsWords = kPersistWsWordsAll;   // exchange records + control words (cg_persist.h)
 
 struct HostPoll {
   CgState* pinned = nullptr;   // [2]
   hipEvent_t ev[2] = {nullptr, nullptr};
   hipEvent_t seg_ev[2] = {nullptr, nullptr};   // timing events around persistent segments (profiling only; created once)
+  int cus = 0;                                 // compute units of the device
 };
 static std::atomic<unsigned> g_persist_launches{0};   // persistent launches so far: the high half of their exchange tags
 static int g_persist_fallbacks = 0;            // solves that were restarted on the two-kernel path after an exchange timed out
@@ -55,6 +54,7 @@ static int ensure_poll() {
     PISO_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&tl_poll.pinned), 2 * sizeof(CgState), hipHostMallocDefault));
     PISO_HIP_CHECK(hipEventCreateWithFlags(&tl_poll.ev[0], hipEventDisableTiming));
     PISO_HIP_CHECK(hipEventCreateWithFlags(&tl_poll.ev[1], hipEventDisableTiming));
+    PISO_HIP_CHECK(hipDeviceGetAttribute(&tl_poll.cus, hipDeviceAttributeMultiprocessorCount, dev));
   }
   return PISO_OK;
 }
@@ -93,38 +93,22 @@ static size_t cg_workspace_bytes(int nx_in, int ny_in) {
   b += align_up(4 * n * sizeof(float), 256) + 256;        // float copy of the off-diagonals + flag
   b += 3 * align_up(3 * kMaxPartials * sizeof(T), 256);
   b += align_up(SC_COUNT * sizeof(T), 256) + align_up(2 * sizeof(CgState), 256) + 512;
-  b += align_up(kPersistWsWords * sizeof(unsigned), 256);  // exchange records of the persistent kernel
+  b += align_up(kPersistWsWordsAll * sizeof(unsigned), 256);  // exchange records of the persistent kernel
   return b + 4096;
 }
 
-// Which (state, coefficient, matrix) combinations have a 16-row instance at all: the ones that keep their registers.  fp32 state
-// without a symmetric matrix with rebuilt diagonals (26-84 spilled vector registers) and fp64 COEFFICIENTS (a general matrix: 8
-// spilled vector registers) are tiled with regions of 4 / 2 rows instead - those instances spill nothing - or iterate on the
-// two-kernel path; the spilling instances are not compiled.
-template <typename T, typename CT, bool RECON, bool SYMV>
-constexpr bool kHas16 = (sizeof(T) == 8 && sizeof(CT) == 4) || (sizeof(T) == 4 && sizeof(CT) == 4 && RECON && SYMV);
-
-template <typename T, typename CT, bool RECON, bool SYMV>
-static const void* persist_kernel(int R, bool ragged = false, int NQ = 0) {
-  if constexpr (sizeof(T) == 8 && RECON && SYMV) {
-    if (ragged) {
-      switch (R) {
-        case 2: return reinterpret_cast<const void*>(&cg_persist1<T, CT, 2, 2, RECON, SYMV, false, true>);
-        case 4: return reinterpret_cast<const void*>(&cg_persist1<T, CT, 4, 2, RECON, SYMV, false, true>);
-        default: return reinterpret_cast<const void*>(&cg_persist1<T, CT, 16, 1, RECON, SYMV, false, true>);
-      }
-    }
-  }
-  if constexpr (sizeof(T) == 8 && sizeof(CT) == 4 && SYMV) {
-    if (R == 2 && NQ == 1) return reinterpret_cast<const void*>(&cg_persist1<T, CT, 2, 1, RECON, SYMV>);
-  }
-  switch (R) {
-    case 2: return reinterpret_cast<const void*>(&cg_persist1<T, CT, 2, 2, RECON, SYMV>);
-    case 4: return reinterpret_cast<const void*>(&cg_persist1<T, CT, 4, 2, RECON, SYMV>);
-    default:
-      if constexpr (kHas16<T, CT, RECON, SYMV>) return reinterpret_cast<const void*>(&cg_persist1<T, CT, 16, 1, RECON, SYMV>);
-      else return nullptr;
-  }
+// The calling thread's dispatch record (fields: include/piso_hip.h).  One workgroup (cg_tiny.h): path 0 / 1, no tiling, no plan;
+// otherwise path 2 / 3 and the shape fields from the plan.
+static void record_dispatch(int path, size_t state_bytes, size_t coef_bytes, int tiny_per_x, int V = 0, bool recon = false, bool symmetric = false,
+                            const CgTiling* t = nullptr, const PersistPlan* p = nullptr, bool fell_back = false) {
+  int* d = tl_dispatch;
+  for (int i = 0; i < DI_COUNT; ++i) d[i] = 0;
+  d[DI_PATH] = path; d[DI_SIZEOF_T] = (int)state_bytes; d[DI_SIZEOF_CT] = (int)coef_bytes; d[DI_TINY_PER_X] = tiny_per_x;
+  d[DI_V] = V; d[DI_RECON] = recon ? 1 : 0; d[DI_SYMMETRIC] = symmetric ? 1 : 0; d[DI_FELL_BACK] = fell_back ? 1 : 0;
+  if (t) { d[DI_ROWS_PER_WAVE] = t->rows_per_wave; d[DI_K1_GRID] = t->g1; d[DI_K1_TILES] = t->k1_tiles; d[DI_K2_GRID] = t->g2; }
+  if (p) d[DI_PADDED] = p->ragged ? 1 : 0;
+  if (p && p->R) { d[DI_R] = p->R; d[DI_NQ] = p->NQ; d[DI_WAVES] = p->waves; d[DI_LAUNCH_GRID] = p->launch_grid; d[DI_XCD_LOCAL] = p->xcd_local ? 1 : 0; }
+  tl_dispatch_n = DI_COUNT;
 }
 
 struct EventPool {
@@ -134,279 +118,181 @@ struct EventPool {
   bool created = false;
 };
 static thread_local EventPool tl_events;
+struct SegmentTimes { double ms = 0; long long iters = 0, launches = 0; };   // profiling: persistent segments of one solve
 
+static int ensure_events(EventPool& ep) {
+  if (ep.created) return PISO_OK;
+  for (int q = 0; q < 2; ++q)
+    for (int i = 0; i < EventPool::kMax; ++i) {
+      PISO_HIP_CHECK(hipEventCreate(&ep.start[q][i]));
+      PISO_HIP_CHECK(hipEventCreate(&ep.stop[q][i]));
+    }
+  ep.created = true;
+  return PISO_OK;
+}
+
+// profiling: what the solve's sampled K1 / K2 launches and its persistent segments took -> kernel_ms_out (per launch / per iteration), g_prof
+static int read_profile(const EventPool& ep, const SegmentTimes& seg, float* kernel_ms_out) {
+  double ms[2] = {0, 0};
+  for (int q = 0; q < 2; ++q)
+    for (int i = 0; i < ep.used[q]; ++i) {
+      float t = 0;
+      PISO_HIP_CHECK(hipEventElapsedTime(&t, ep.start[q][i], ep.stop[q][i]));
+      ms[q] += t;
+    }
+  if (kernel_ms_out) {
+    kernel_ms_out[0] = ep.used[0] ? (float)(ms[0] / ep.used[0]) : 0.f;
+    kernel_ms_out[1] = ep.used[1] ? (float)(ms[1] / ep.used[1]) : 0.f;
+  }
+  if (g_prof.enabled) {
+    for (int q = 0; q < 2; ++q) { g_prof.ms[q] += ms[q]; g_prof.count[q] += ep.used[q]; }
+    g_prof.ms[2] += seg.ms; g_prof.count[2] += seg.iters; g_prof.count[3] += seg.launches;
+  }
+  if (kernel_ms_out && seg.iters > 0) { kernel_ms_out[0] = (float)(seg.ms / seg.iters); kernel_ms_out[1] = 0.f; }
+  return PISO_OK;
+}
+
+// diagnostic builds only (kPersistDiag, option cg_persist_timing): the per-phase clocks of every workgroup, freed with the solve
+struct PersistTiming {
+  unsigned long long* ticks = nullptr;
+  ~PersistTiming() { if (ticks) (void)hipFree(ticks); }
+};
+static int print_persist_timing(const unsigned long long* ticks, int grid, int k_last) {
+  std::vector<unsigned long long> h(12 * grid);
+  PISO_HIP_CHECK(hipMemcpy(h.data(), ticks, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  const char* names[9] = {"D (p update, stencil, sums, publish)", "exchange", "U (stencil, x / r update, ring)", "-", "-",
+                           "  exchange: wave sums + drain of the perimeter stores", "  exchange: first barrier", "  exchange: publish + polling",
+                           "  exchange: record sums + second barrier"};
+  const double f = 0.01 / (double)(k_last > 0 ? k_last : 1);   // 100 MHz ticks -> us per iteration
+  if (opt(OPT_CG_PERSIST_TIMING) >= 2) {                  // the whole table: one line per workgroup
+    for (int b = 0; b < grid; ++b)
+      fprintf(stderr, "cg_persist_wg %3d xcd %d band %3d  D %.2f  exchange %.2f  U %.2f  | drain %.2f  barrier1 %.2f  publish+poll %.2f  sums %.2f\n", b, (int)h[9 * grid + b], (int)h[10 * grid + b],
+              f * (double)h[0 * grid + b], f * (double)h[1 * grid + b], f * (double)h[2 * grid + b],
+              f * (double)h[5 * grid + b], f * (double)h[6 * grid + b], f * (double)h[7 * grid + b], f * (double)h[8 * grid + b]);
+  }
+  for (int q = 0; q < 9; ++q) {
+    double s = 0, mn = 1e300, mx = 0;
+    for (int b = 0; b < grid; ++b) { const double v = (double)h[q * grid + b]; s += v; mn = v < mn ? v : mn; mx = v > mx ? v : mx; }
+    fprintf(stderr, "cg_persist %s: avg %.2f us/iter  min %.2f  max %.2f\n", names[q], f * s / grid, f * mn, f * mx);
+  }
+  return PISO_OK;
+}
+
+// The persistent kernel lets workgroups read what others published without release / acquire fences (cg_persist1.h).  That is
+// checked at run time instead of being trusted: r - the CG recurrence - must still equal b - A^ x for the x the solve returns (to
+// eps * condition * |b|; a stale perimeter value would leave an O(alpha |z'|) gap that nothing removes before the next residual
+// reset).  One stencil pass per solve; the driver restarts a solve that fails on the two-kernel path and counts it.
+template <typename T, typename CT>
+static int verify_residual(const CgArgs<T>& a, const PersistCtl& pc, hipStream_t stream, bool* failed) {
+  unsigned* out2 = reinterpret_cast<unsigned*>(pc.err) + 4;
+  PISO_HIP_CHECK(hipMemsetAsync(out2, 0, 2 * sizeof(unsigned), stream));
+  const int gvf = grid_for((long long)a.nx * a.ny, kBlock * 4, 1024);
+  cg_verify_sum_x<T><<<gvf, kBlock, 0, stream>>>(a, a.partsA);
+  cg_verify_gap<T, CT><<<gvf, kBlock, 0, stream>>>(a, a.partsA, gvf, out2);
+  PISO_LAUNCH_CHECK();
+  unsigned h2[2] = {0, 0};
+  PISO_HIP_CHECK(hipMemcpyAsync(h2, out2, sizeof(h2), hipMemcpyDeviceToHost, stream));
+  PISO_HIP_CHECK(hipStreamSynchronize(stream));
+  float gap, scale;
+  memcpy(&gap, &h2[0], 4); memcpy(&scale, &h2[1], 4);
+  ++g_verify_runs;
+  *failed = (gap > 1e-5f * scale && gap > 1e-30f) || opt(OPT_CG_VERIFY) == 2;     // (2: test knob - treat the check as failed)
+  return PISO_OK;
+}
+
+// waits for poll `slot`: 1 if the solver reported done (*stop_it: at which iteration), 0 if not, -1 on an error
+static int inspect_poll(int slot, int* stop_it) {
+  hipError_t e = hipEventSynchronize(tl_poll.ev[slot]);
+  if (e != hipSuccess) { set_error("hipEventSynchronize", e); return -1; }
+  if (tl_poll.pinned[slot].done) { *stop_it = tl_poll.pinned[slot].iterations; return 1; }
+  return 0;
+}
+// poll cadence of the two-kernel iteration: about 1 ms of work between host looks, never fewer than 10 iterations
+static int poll_batch(size_t n) {
+  const double t_iter_us = (double)n * 120.0 / 4.0e6;    // ~4 TB/s
+  const int batch = (int)(1000.0 / (t_iter_us < 8.0 ? 8.0 : t_iter_us));
+  return batch < 10 ? 10 : (batch > 200 ? 200 : batch);
+}
+
+// returns PISO_OK, an error, or kPersistRetry: a persistent segment failed (an exchange gave up: some workgroups were not resident -
+// another kernel or process holds CUs; or the true-residual check) and its state is unusable -> the caller runs the whole solve again
+// with allow_persist = false: the two-kernel path needs no co-residency
 template <typename T, typename CT, int V, bool RECON>
 static int cg_run(CgArgs<T> a, unsigned* persist_ws, bool symmetric, float accuracy, int max_iterations, int rank_deficient, int reset, int fixed,
-                  int* iterations_out, float* kernel_ms_out, hipStream_t stream, bool allow_persist = true) {
-  const int nx = a.nx, ny = a.ny;
-  const size_t n = (size_t)nx * ny;
-  a.ntx = (nx + 64 * V - 1) / (64 * V);
-  int rpw = (int)(((long long)ny * a.ntx) / (4 * 1024));
-  rpw = rpw < 2 ? 2 : (rpw > 16 ? 16 : rpw);
-  if (opt(OPT_CG_RPW) > 0) rpw = opt(OPT_CG_RPW);                                             // tuning knob
-  a.rows_per_wave = rpw;
-  a.nty = (ny + 4 * rpw - 1) / (4 * rpw);
+                  int* iterations_out, float* kernel_ms_out, hipStream_t stream, bool allow_persist) {
+  const size_t n = (size_t)a.nx * a.ny;
+  const CgTiling tile = cg_tile(a, V, opt(OPT_CG_RPW), opt(OPT_CG_MAXBLOCKS));                   // tuning knobs
+  const int g1 = tile.g1, g2 = tile.g2, gflat = tile.gflat;
   a.accuracy = fixed ? -1.0f : accuracy;                 // fixed-work mode: the test can never succeed
-  int cap = 1024;
-  if (opt(OPT_CG_MAXBLOCKS) >= 8 && opt(OPT_CG_MAXBLOCKS) <= kMaxPartials) cap = opt(OPT_CG_MAXBLOCKS);
-  const int g1 = grid_for((long long)a.ntx * a.nty, 1, cap);
-  const int g2 = grid_for((long long)((n / V + kBlock - 1) / kBlock), 4);
-  a.nA = g1; a.nB = g2;
-  const int gflat = grid_for((long long)n, kBlock * 4);
 
   { const int rc = ensure_poll(); if (rc != PISO_OK) return rc; }
   const bool prof = (kernel_ms_out != nullptr) || g_prof.enabled;
   EventPool& ep = tl_events;
-  if (prof && !ep.created) {
-    for (int q = 0; q < 2; ++q)
-      for (int i = 0; i < EventPool::kMax; ++i) {
-        PISO_HIP_CHECK(hipEventCreate(&ep.start[q][i]));
-        PISO_HIP_CHECK(hipEventCreate(&ep.stop[q][i]));
-      }
-    ep.created = true;
-  }
+  if (prof) { const int rc = ensure_events(ep); if (rc != PISO_OK) return rc; }
   ep.used[0] = ep.used[1] = 0;
   const int prof_stride = g_prof.stride > 0 ? g_prof.stride : 8;
 
   cg_init<T><<<gflat, kBlock, 0, stream>>>(a, rank_deficient);
   PISO_LAUNCH_CHECK();
 
-  // poll cadence: about 1 ms of work between host looks, never fewer than 10 iterations
-  double t_iter_us = (double)n * 120.0 / 4.0e6;          // ~4 TB/s
-  if (t_iter_us < 8.0) t_iter_us = 8.0;
-  int batch = (int)(1000.0 / t_iter_us);
-  batch = batch < 10 ? 10 : (batch > 200 ? 200 : batch);
-
+  const int batch = poll_batch(n);
   int sv = 0, polls = 0, stop_it = -1;
   const int total = fixed ? fixed : max_iterations;
   bool finished = false;
-  auto inspect = [&](int slot) -> int {                  // wait for poll `slot`, return 1 if the solver reported done
-    hipError_t e = hipEventSynchronize(tl_poll.ev[slot]);
-    if (e != hipSuccess) { set_error("hipEventSynchronize", e); return -1; }
-    if (tl_poll.pinned[slot].done) { stop_it = tl_poll.pinned[slot].iterations; return 1; }
-    return 0;
-  };
   bool pending = false;                                  // x still lacks alpha_k p_k of the last executed iteration
   int k_last = -1;
-  // ---- persistent segments (cg_persist1.h): applicable when every wave's region fits on chip
-  int persist_R = 0, persist_NQ = 0, persist_grid = 0;
+  // ---- persistent segments: the plan, confirmed by the occupancy of the instance it names (cg_dispatch.h)
+  PersistPlan plan = persist_plan(PersistQuery{a.nx, a.ny, V, a.per_y, a.nx_true != 0, sizeof(T), sizeof(CT), RECON, symmetric, false, tl_poll.cus,
+                                               opt(OPT_CG_PERSIST), opt(OPT_CG_PERSIST_R), opt(OPT_CG_PERSIST_HALF), opt(OPT_CG_PERSIST_NQ),
+                                               opt(OPT_CG_XCD_LOCAL), g_xcd_local_failed, allow_persist});
   PersistCtl pc;
-  pc.rec = nullptr; pc.err = nullptr; pc.nreg = 0; pc.ntx = 0; pc.timing = nullptr; pc.epoch0 = 0; pc.xcd = nullptr; pc.local_n = 0; pc.waves = kPersistWaves;
-  bool xcd_local = false;                                // the solve runs on the workgroups of one XCD (cg_persist1<..., LOCAL>)
-  constexpr int kXcdCus = 32;                            // CUs of one MI355X XCD
-  const int force = opt(OPT_CG_PERSIST), force_r = opt(OPT_CG_PERSIST_R);   // -1: automatic
-  // fp32 state: the 16-row instance keeps its registers only for a symmetric matrix with rebuilt diagonals (the others spill
-  // 26-84 VGPRs); any other fp32 system is tiled with regions of 4 / 2 rows (no spills), or iterates on the two-kernel path
-  const bool f32_small_regions = (sizeof(T) != 8 && !(symmetric && RECON)) || sizeof(CT) == 8;     // (see kHas16)
-  if (V == 16 / (int)sizeof(T) && a.per_y != 2 && allow_persist && force != 0) {
-    int dev = 0, cus = 0;
-    PISO_HIP_CHECK(hipGetDevice(&dev));
-    PISO_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    PersistShape shape = persist_shape(nx, ny, V, cus, force_r);
-    if (f32_small_regions && shape.R == 16) {
-      shape = PersistShape();
-      if (force_r <= 0) { shape = persist_shape(nx, ny, V, cus, 4); if (!shape.R) shape = persist_shape(nx, ny, V, cus, 2); }
-    }
-    // XCD-local mode: symmetric compact coefficients, fp64, one exchange, at most one XCD's worth of workgroups
-    constexpr bool kLocalKernel = RECON && sizeof(CT) == 4 && sizeof(T) == 8;
-    const bool local_ok = kLocalKernel && symmetric && opt(OPT_CG_XCD_LOCAL) != 0 && !g_xcd_local_failed &&
-                          cus == kXcds * kXcdCus;
-    // (measured at 2048^2-class work per workgroup: regions of 4 rows to make a 64-workgroup grid fit one XCD lose more in the row
-    // loops than the shorter exchange wins - 512^2: 6.2 against 4.5 us per iteration; 256^2, 16 workgroups either way: 3.8 against 4.3)
-    persist_R = shape.R; persist_NQ = shape.NQ; persist_grid = shape.grid; pc.nreg = shape.nreg; pc.ntx = shape.ntx;
-
-    // Small regions: ONE wave with work per SIMD instead of two (waves 4-7 of a workgroup own nothing), twice the workgroups, wherever
-    // the doubled grid still fits the chip: a wave then never waits at the exchange's first barrier for the wave it shares a SIMD
-    // with (0.6 us of a ~4 us iteration).  Measured: 256^2 3.80 -> 3.47 us per iteration, 512^2 4.45 -> 4.08, 1024 x 256 4.48 -> 4.08,
-    // 1024 x 512 unchanged.  Option cg_persist_half 0: never, 1: wherever it fits.  Automatic (-1) leaves out the one case where the
-    // doubling would push a grid that fits ONE XCD (17-32 workgroups) out of it: since the XCD-local exchange polls its own XCD's
-    // records only, 32 full workgroups there beat 64 half ones chip-wide (512 x 256, round 4: 3.98 against 4.19 us per iteration).
-    {
-      const int half = opt(OPT_CG_PERSIST_HALF);
-      const bool fits = (persist_R == 2 || persist_R == 4) && persist_NQ == 2 && 2 * persist_grid <= cus;
-      const bool leaves_xcd = local_ok && persist_grid <= kXcdCus && 2 * persist_grid > kXcdCus;
-      if (fits && half != 0 && (half == 1 || !leaves_xcd)) {
-        pc.waves = kPersistWaves / 2;
-        persist_grid = (shape.nreg + pc.waves * persist_NQ - 1) / (pc.waves * persist_NQ);
-      }
-    }
-    xcd_local = local_ok && (persist_R == 2 || persist_R == 4) && persist_grid <= kXcdCus;
-    // Regions of 2 rows on a grid that runs chip-wide anyway (more than one XCD's worth of workgroups): ONE region per wave, all eight
-    // waves of a workgroup at work - the row work per SIMD of the half-occupancy shape (two waves x one region instead of one wave
-    // x two) with half its workgroups in the exchange.  Round 5, A/B on one box: 1024 x 256 (config 4) 3.73 -> 3.57 us per iteration,
-    // 512^2 3.72 -> 3.60; 256^2 stays on its XCD (2.69 against 3.41).  Option cg_persist_nq: 0 never, 1 wherever the chip holds it.
-    {
-      constexpr bool kHasNq1 = sizeof(T) == 8 && sizeof(CT) == 4;
-      const int nq = opt(OPT_CG_PERSIST_NQ);
-      if (kHasNq1 && symmetric && nq != 0 && persist_R == 2 && !a.nx_true && (!xcd_local || nq == 1) &&
-          (shape.nreg + kPersistWaves - 1) / kPersistWaves <= cus) {
-        persist_NQ = 1; pc.waves = kPersistWaves; xcd_local = false;
-        persist_grid = (shape.nreg + kPersistWaves - 1) / kPersistWaves;
-      }
-    }
-    {
-      // ... and inside ONE XCD as well, where that needs no more than its 32 workgroups: 256^2 (config 2) 2.74 -> 2.59 us per iteration
-      // (eight working waves x one region instead of four x two; 512 x 256 would need 64 workgroups and keeps two regions per wave)
-      constexpr bool kHasNq1L = sizeof(T) == 8 && sizeof(CT) == 4 && RECON;
-      if (kHasNq1L && opt(OPT_CG_PERSIST_NQ) != 0 && xcd_local && persist_R == 2 && persist_NQ == 2 && !a.nx_true &&
-          (shape.nreg + kPersistWaves - 1) / kPersistWaves <= kXcdCus) {
-        persist_NQ = 1; pc.waves = kPersistWaves;
-        persist_grid = (shape.nreg + kPersistWaves - 1) / kPersistWaves;
-      }
-    }
-    if (persist_R && n < 16384 && force != 1 && !a.nx_true) persist_R = 0;    // tiny grids: two-kernel path (a padded grid is here BECAUSE it is small)
+  { const int rc = persist_prepare<T, CT, RECON, false>(plan, tl_poll.cus, pc, persist_ws, stream); if (rc != PISO_OK) return rc; }
+  PersistTiming timing;
+  if (plan.R && kPersistDiag && opt_on(OPT_CG_PERSIST_TIMING)) {
+    PISO_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&timing.ticks), 12 * plan.launch_grid * sizeof(unsigned long long)));
+    PISO_HIP_CHECK(hipMemsetAsync(timing.ticks, 0, 12 * plan.launch_grid * sizeof(unsigned long long), stream));
+    pc.timing = timing.ticks;
   }
-  const bool ragged = a.nx_true != 0;
-  if (ragged && persist_R) {
-    // the padded-grid variant exists for the common case only: fp64 state, one exchange, exact-float symmetric coefficients
-    constexpr bool kRaggedKernel = RECON && sizeof(CT) == 4 && sizeof(T) == 8;
-    if (!kRaggedKernel || !symmetric) persist_R = 0;
-  }
-  if (!persist_R) xcd_local = false;
-  const int launch_grid = xcd_local ? kXcds * persist_grid : persist_grid;   // (XCD-local: some XCD is dealt a full group)
-  if (persist_R) {
-    // the exchanges spin: EVERY workgroup must be resident at the same time.  What the occupancy calculator says one CU can
-    // hold (LDS, registers) times the CUs of the device must cover the grid; what it cannot see (another process, a CU mask)
-    // is caught by the spin bound -> restart on the two-kernel path (below).
-    // (the symmetric variant - S and W streamed, N and E taken from the neighbours' S and W - also serves systems whose diagonal cannot
-    // be rebuilt from the off-diagonals: open boundaries, where the diagonal carries the face to the outside - BASELINE config 4.  It
-    // then streams the diagonal beside S and W: 16 instead of 24 bytes per cell and pass.  fp64 state only: the fp32 instances keep
-    // their registers only with rebuilt diagonals.)
-    constexpr bool kCanSymO = sizeof(CT) == 4 && (RECON || sizeof(T) == 8);
-    const void* kfn = persist_kernel<T, CT, RECON, false>(persist_R);
-    if constexpr (kCanSymO) { if (symmetric) kfn = persist_kernel<T, CT, RECON, true>(persist_R, ragged, persist_NQ); }
-    int per_cu = 0, dev = 0, cus = 0;
-    PISO_HIP_CHECK(hipGetDevice(&dev));
-    PISO_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    if (!kfn) persist_R = 0;                                 // (a forced 16-row shape for a combination that has no such instance: kHas16)
-    else {
-      PISO_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, kPersistThreads, 0));
-      if ((long long)per_cu * cus < launch_grid) persist_R = 0;
-    }
-  }
-  if (persist_R) {
-    pc.rec = reinterpret_cast<unsigned long long*>(persist_ws);
-    pc.err = reinterpret_cast<int*>(persist_ws + kPersistWsWords - 16);
-    PISO_HIP_CHECK(hipMemsetAsync(persist_ws, 0, kPersistWsWords * sizeof(unsigned), stream));
-    pc.xcd = reinterpret_cast<int*>(persist_ws + kPersistRecWords);   // 10 words behind the records, before the error flag
-    pc.local_n = xcd_local ? persist_grid : 0;
-    if (launch_grid > kPersistMaxGrid) persist_R = 0;
-    if (kPersistDiag && opt_on(OPT_CG_PERSIST_TIMING)) {   // diagnostic builds only: per-phase clocks of every workgroup
-      PISO_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&pc.timing), 12 * launch_grid * sizeof(unsigned long long)));
-      PISO_HIP_CHECK(hipMemsetAsync(pc.timing, 0, 12 * launch_grid * sizeof(unsigned long long), stream));
-    }
-  }
-  {
-    int* d = tl_dispatch;
-    for (int i = 0; i < DI_COUNT; ++i) d[i] = 0;
-    d[DI_PATH] = persist_R ? 3 : 2; d[DI_SIZEOF_T] = (int)sizeof(T); d[DI_SIZEOF_CT] = (int)sizeof(CT); d[DI_V] = V; d[DI_RECON] = RECON ? 1 : 0;
-    d[DI_SYMMETRIC] = symmetric ? 1 : 0; d[DI_ROWS_PER_WAVE] = rpw; d[DI_K1_GRID] = g1; d[DI_K1_TILES] = a.ntx * a.nty; d[DI_K2_GRID] = g2;
-    if (persist_R) { d[DI_R] = persist_R; d[DI_NQ] = persist_NQ; d[DI_WAVES] = pc.waves; d[DI_LAUNCH_GRID] = launch_grid; d[DI_XCD_LOCAL] = xcd_local ? 1 : 0; }
-    d[DI_PADDED] = ragged ? 1 : 0; d[DI_FELL_BACK] = allow_persist ? 0 : 1;
-    tl_dispatch_n = DI_COUNT;
-  }
-  auto launch_segment = [&](int kb, int ke) -> int {
-    // Tags are unique per launch (a 16-bit launch counter above a 16-bit exchange counter; a segment has < 2^15 exchanges): a
-    // record left by an earlier launch - in memory or in some XCD's L2 - can never pass for one of this launch.  The records are
-    // zeroed as well, which covers the counter's wrap.
-    pc.epoch0 = (g_persist_launches.fetch_add(1, std::memory_order_relaxed) & 0xffffu) << 16;
-    PISO_HIP_CHECK(hipMemsetAsync(pc.rec, 0, kPersistZeroBytes, stream));   // records (both levels) + XCD arrivals
-    constexpr bool kCanSym = RECON && sizeof(CT) == 4;     // the symmetric variant exists for the compact coefficient path
-    if constexpr (kCanSym && sizeof(T) == 8) {
-      if (xcd_local) {                                       // (symmetric, one exchange, regions of 2 / 4 rows: checked above)
-        if (ragged) {
-          if (persist_R == 2) cg_persist1<T, CT, 2, 2, RECON, true, false, true, true><<<launch_grid, kPersistThreads, 0, stream>>>(a, pc, kb, ke, sv, pending ? 1 : 0);
-          else cg_persist1<T, CT, 4, 2, RECON, true, false, true, true><<<launch_grid, kPersistThreads, 0, stream>>>(a, pc, kb, ke, sv, pending ? 1 : 0);
-        } else {
-          if (persist_R == 2 && persist_NQ == 1) cg_persist1<T, CT, 2, 1, RECON, true, false, false, true><<<launch_grid, kPersistThreads, 0, stream>>>(a, pc, kb, ke, sv, pending ? 1 : 0);
-          else if (persist_R == 2) cg_persist1<T, CT, 2, 2, RECON, true, false, false, true><<<launch_grid, kPersistThreads, 0, stream>>>(a, pc, kb, ke, sv, pending ? 1 : 0);
-          else cg_persist1<T, CT, 4, 2, RECON, true, false, false, true><<<launch_grid, kPersistThreads, 0, stream>>>(a, pc, kb, ke, sv, pending ? 1 : 0);
-        }
-        PISO_LAUNCH_CHECK();
-        return PISO_OK;
-      }
-      if (ragged) {                                          // padded-grid mode (symmetric, one exchange: checked above)
-        if (persist_R == 2) cg_persist1<T, CT, 2, 2, RECON, true, false, true><<<persist_grid, kPersistThreads, 0, stream>>>(a, pc, kb, ke, sv, pending ? 1 : 0);
-        else if (persist_R == 4) cg_persist1<T, CT, 4, 2, RECON, true, false, true><<<persist_grid, kPersistThreads, 0, stream>>>(a, pc, kb, ke, sv, pending ? 1 : 0);
-        else cg_persist1<T, CT, 16, 1, RECON, true, false, true><<<persist_grid, kPersistThreads, 0, stream>>>(a, pc, kb, ke, sv, pending ? 1 : 0);
-        PISO_LAUNCH_CHECK();
-        return PISO_OK;
-      }
-    }
-#define PISO_PERSIST_LAUNCH(SYMV)                                                                                            \
-    do {                                                                                                                     \
-      if constexpr (sizeof(T) == 8 && sizeof(CT) == 4 && SYMV) {                                                             \
-        if (persist_R == 2 && persist_NQ == 1) { cg_persist1<T, CT, 2, 1, RECON, SYMV><<<persist_grid, kPersistThreads, 0, stream>>>(a, pc, kb, ke, sv, pending ? 1 : 0); break; } \
-      }                                                                                                                      \
-      if (persist_R == 2) cg_persist1<T, CT, 2, 2, RECON, SYMV><<<persist_grid, kPersistThreads, 0, stream>>>(a, pc, kb, ke, sv, pending ? 1 : 0);        \
-      else if (persist_R == 4) cg_persist1<T, CT, 4, 2, RECON, SYMV><<<persist_grid, kPersistThreads, 0, stream>>>(a, pc, kb, ke, sv, pending ? 1 : 0);   \
-      else if constexpr (kHas16<T, CT, RECON, SYMV>) cg_persist1<T, CT, 16, 1, RECON, SYMV><<<persist_grid, kPersistThreads, 0, stream>>>(a, pc, kb, ke, sv, pending ? 1 : 0);  \
-    } while (0)
-    constexpr bool kCanSymPlain = sizeof(CT) == 4 && (RECON || sizeof(T) == 8);     // (see kCanSymO above)
-    if constexpr (kCanSymPlain) {
-      if (symmetric) {
-        PISO_PERSIST_LAUNCH(true);
-        PISO_LAUNCH_CHECK();
-        return PISO_OK;
-      }
-    }
-    PISO_PERSIST_LAUNCH(false);
-#undef PISO_PERSIST_LAUNCH
-    PISO_LAUNCH_CHECK();
-    return PISO_OK;
-  };
-  // ~10 ms of work per segment at 2048^2 (1 000 iterations; one host look per segment - a converged solve leaves its segment by
-  // itself).  Measured in the bench: segments of 500 / 1 000 / 2 000 iterations 4.41 / 4.44 / 4.46 steps/s - every launch pays its
-  // prologue, the state's trip from and to memory and a cold first iteration
-  int seg_len = (int)(40000.0 / ((double)n * 8.5e-6 + 4.0));
-  seg_len = seg_len < 50 ? 50 : (seg_len > 2000 ? 2000 : seg_len);
-  if (opt(OPT_CG_SEGMENT) > 0) seg_len = opt(OPT_CG_SEGMENT);
+  record_dispatch(plan.R ? 3 : 2, sizeof(T), sizeof(CT), 0, V, RECON, symmetric, &tile, &plan, !allow_persist);
+  const int seg_len = persist_segment_len(n, opt(OPT_CG_SEGMENT));
   hipEvent_t* seg_ev = tl_poll.seg_ev;
-  if (persist_R && prof && !seg_ev[0]) { PISO_HIP_CHECK(hipEventCreate(&seg_ev[0])); PISO_HIP_CHECK(hipEventCreate(&seg_ev[1])); }
-  double seg_ms = 0; long long seg_iters = 0, seg_launches = 0;
+  if (plan.R && prof && !seg_ev[0]) { PISO_HIP_CHECK(hipEventCreate(&seg_ev[0])); PISO_HIP_CHECK(hipEventCreate(&seg_ev[1])); }
+  SegmentTimes seg;
   int segments_run = 0, unsynced = 0;
   for (int k = 0; k < total && !finished; ++k) {
     const bool is_reset = !fixed && ((k + 1) % reset == 0);
-    if (persist_R && k > 0 && !is_reset) {
+    if (plan.R && k > 0 && !is_reset) {
       // run NORMAL iterations [k, ke) in one launch: up to the next reset iteration / the end / one segment length
       int ke = total;
       if (!fixed) { const int next_reset = ((k + 1 + reset - 1) / reset) * reset - 1; if (next_reset < ke) ke = next_reset; }
       if (ke > k + seg_len) ke = k + seg_len;
       if (ke > k) {
         if (prof) PISO_HIP_CHECK(hipEventRecord(seg_ev[0], stream));
-        { const int rc = launch_segment(k, ke); if (rc != PISO_OK) return rc; }
+        { const int rc = persist_launch<T, CT, RECON, false>(plan, a, pc, g_persist_launches.fetch_add(1, std::memory_order_relaxed), k, ke, sv, pending, NoSlab{}, stream);
+          if (rc != PISO_OK) return rc; }
         if (prof) PISO_HIP_CHECK(hipEventRecord(seg_ev[1], stream));
         // Short segments (frequent residual resets: the reference's default residual_reset = 10 leaves 9 iterations between two
         // resets) are not worth a host round trip each: the host looks again after ~250 iterations.  Everything queued behind a
         // converged or failed segment returns at once (every kernel checks the state record first), the error flag is sticky.
-        if (!prof && ke - k <= 32 && unsynced + (ke - k) <= 256 && ke < total) {
-          unsynced += ke - k;
-          ++segments_run;
-          k_last = ke - 1;
-          pending = false;
-          k = ke - 1;
-          continue;
+        const bool defer = !prof && ke - k <= 32 && unsynced + (ke - k) <= 256 && ke < total;
+        unsynced = defer ? unsynced + (ke - k) : 0;
+        if (!defer) {
+          PISO_HIP_CHECK(hipMemcpyAsync(&tl_poll.pinned[0], &a.state[0], sizeof(CgState), hipMemcpyDeviceToHost, stream));
+          int herr = 0;
+          PISO_HIP_CHECK(hipMemcpyAsync(&herr, pc.err, sizeof(int), hipMemcpyDeviceToHost, stream));
+          PISO_HIP_CHECK(hipStreamSynchronize(stream));
+          if (herr) {                                      // a grid-wide exchange gave up
+            ++g_persist_fallbacks;
+            if (plan.xcd_local) g_xcd_local_failed = true;
+            return kPersistRetry;
+          }
+          if (prof) {
+            // (a solve that converges inside the launch leaves it there: the iterations it RAN count, not the segment's length)
+            const int ran = tl_poll.pinned[0].done ? (tl_poll.pinned[0].iterations - k > 0 ? tl_poll.pinned[0].iterations - k : 0) : ke - k;
+            float t = 0; PISO_HIP_CHECK(hipEventElapsedTime(&t, seg_ev[0], seg_ev[1])); seg.ms += t; seg.iters += ran < ke - k ? ran : ke - k; ++seg.launches;
+          }
+          if (tl_poll.pinned[0].done) { finished = true; stop_it = tl_poll.pinned[0].iterations; }
         }
-        unsynced = 0;
-        PISO_HIP_CHECK(hipMemcpyAsync(&tl_poll.pinned[0], &a.state[0], sizeof(CgState), hipMemcpyDeviceToHost, stream));
-        int herr = 0;
-        PISO_HIP_CHECK(hipMemcpyAsync(&herr, pc.err, sizeof(int), hipMemcpyDeviceToHost, stream));
-        PISO_HIP_CHECK(hipStreamSynchronize(stream));
-        if (herr) {
-          // A grid-wide exchange gave up: some workgroups were not resident (another kernel or process holds CUs).  The
-          // segment's state is unusable; the two-kernel path needs no co-residency: run the whole solve again on it.
-          ++g_persist_fallbacks;
-          if (xcd_local) g_xcd_local_failed = true;
-          if (pc.timing) { PISO_HIP_CHECK(hipFree(pc.timing)); pc.timing = nullptr; }
-          return cg_run<T, CT, V, RECON>(a, persist_ws, symmetric, accuracy, max_iterations, rank_deficient, reset, fixed, iterations_out,
-                                         kernel_ms_out, stream, false);
-        }
-        if (prof) {
-          // (a solve that converges inside the launch leaves it there: the iterations it RAN count, not the segment's length)
-          const int ran = tl_poll.pinned[0].done ? (tl_poll.pinned[0].iterations - k > 0 ? tl_poll.pinned[0].iterations - k : 0) : ke - k;
-          float t = 0; PISO_HIP_CHECK(hipEventElapsedTime(&t, seg_ev[0], seg_ev[1])); seg_ms += t; seg_iters += ran < ke - k ? ran : ke - k; ++seg_launches;
-        }
-        if (tl_poll.pinned[0].done) { finished = true; stop_it = tl_poll.pinned[0].iterations; }
         ++segments_run;
         k_last = ke - 1;
         pending = false;                                   // the segment applies every x += alpha p itself
@@ -440,7 +326,7 @@ static int cg_run(CgArgs<T> a, unsigned* persist_ws, bool symmetric, float accur
       PISO_HIP_CHECK(hipMemcpyAsync(&tl_poll.pinned[slot], &a.state[sv & 1], sizeof(CgState), hipMemcpyDeviceToHost, stream));
       PISO_HIP_CHECK(hipEventRecord(tl_poll.ev[slot], stream));
       if (polls > 0) {                                   // look at the PREVIOUS poll while this batch is already queued
-        const int r = inspect((polls - 1) & 1);
+        const int r = inspect_poll((polls - 1) & 1, &stop_it);
         if (r < 0) return PISO_ERR_HIP;
         if (r > 0) finished = true;
       }
@@ -455,94 +341,32 @@ static int cg_run(CgArgs<T> a, unsigned* persist_ws, bool symmetric, float accur
     const int slot = polls & 1;
     PISO_HIP_CHECK(hipMemcpyAsync(&tl_poll.pinned[slot], &a.state[sv & 1], sizeof(CgState), hipMemcpyDeviceToHost, stream));
     PISO_HIP_CHECK(hipEventRecord(tl_poll.ev[slot], stream));
-    const int r = inspect(slot);
+    const int r = inspect_poll(slot, &stop_it);
     if (r < 0) return PISO_ERR_HIP;
     if (r > 0) finished = true;
   }
   PISO_HIP_CHECK(hipStreamSynchronize(stream));
   if (opt(OPT_CG_XCD_MAP) == 1) {
     tl_xcd_map_n = 0;
-    if (segments_run > 0 && persist_R && !xcd_local && persist_grid <= kPersistMaxGrid) {
-      PISO_HIP_CHECK(hipMemcpy(tl_xcd_map, pc.xcd + kPersistXcdTable, (size_t)persist_grid * sizeof(int), hipMemcpyDeviceToHost));
-      tl_xcd_map_n = persist_grid;
+    if (segments_run > 0 && !plan.xcd_local && plan.grid <= kPersistMaxGrid) {
+      PISO_HIP_CHECK(hipMemcpy(tl_xcd_map, pc.xcd + kPersistXcdTable, (size_t)plan.grid * sizeof(int), hipMemcpyDeviceToHost));
+      tl_xcd_map_n = plan.grid;
     }
   }
-  if (segments_run > 0 && allow_persist) {                 // (segments whose host look was deferred: did one of them give up?)
+  if (segments_run > 0) {                                  // (segments whose host look was deferred: did one of them give up?)
     int herr = 0;
     PISO_HIP_CHECK(hipMemcpy(&herr, pc.err, sizeof(int), hipMemcpyDeviceToHost));
-    if (herr) {
-      ++g_persist_fallbacks;
-      if (pc.timing) { PISO_HIP_CHECK(hipFree(pc.timing)); pc.timing = nullptr; }
-      return cg_run<T, CT, V, RECON>(a, persist_ws, symmetric, accuracy, max_iterations, rank_deficient, reset, fixed, iterations_out,
-                                     kernel_ms_out, stream, false);
-    }
+    if (herr) { ++g_persist_fallbacks; return kPersistRetry; }
   }
-  // ---- The persistent kernel lets workgroups read what others published without release / acquire fences (cg_persist1.h).  That
-  // is checked here at run time instead of being trusted: r - the CG recurrence - must still equal b - A^ x for the x the solve
-  // returns (to eps * condition * |b|; a stale perimeter value would leave an O(alpha |z'|) gap that nothing removes before the
-  // next residual reset).  One stencil pass per solve; a failure restarts the solve on the two-kernel path and is counted.
   if (segments_run > 0 && sizeof(T) == 8 && !fixed && opt(OPT_CG_VERIFY) != 0) {
-    unsigned* out2 = reinterpret_cast<unsigned*>(pc.err) + 4;
-    PISO_HIP_CHECK(hipMemsetAsync(out2, 0, 2 * sizeof(unsigned), stream));
-    const int gvf = grid_for((long long)n, kBlock * 4, 1024);
-    cg_verify_sum_x<T><<<gvf, kBlock, 0, stream>>>(a, a.partsA);
-    cg_verify_gap<T, CT><<<gvf, kBlock, 0, stream>>>(a, a.partsA, gvf, out2);
-    PISO_LAUNCH_CHECK();
-    unsigned h2[2] = {0, 0};
-    PISO_HIP_CHECK(hipMemcpyAsync(h2, out2, sizeof(h2), hipMemcpyDeviceToHost, stream));
-    PISO_HIP_CHECK(hipStreamSynchronize(stream));
-    float gap, scale;
-    memcpy(&gap, &h2[0], 4); memcpy(&scale, &h2[1], 4);
-    ++g_verify_runs;
-    if ((gap > 1e-5f * scale && gap > 1e-30f) || opt(OPT_CG_VERIFY) == 2) {     // (2: test knob - treat the check as failed)
-      ++g_verify_failures; ++g_persist_fallbacks;
-      if (pc.timing) { PISO_HIP_CHECK(hipFree(pc.timing)); pc.timing = nullptr; }
-      return cg_run<T, CT, V, RECON>(a, persist_ws, symmetric, accuracy, max_iterations, rank_deficient, reset, fixed, iterations_out,
-                                     kernel_ms_out, stream, false);
-    }
+    bool failed = false;
+    { const int rc = verify_residual<T, CT>(a, pc, stream, &failed); if (rc != PISO_OK) return rc; }
+    if (failed) { ++g_verify_failures; ++g_persist_fallbacks; return kPersistRetry; }
   }
-  if (pc.timing) {
-    std::vector<unsigned long long> h(12 * persist_grid);
-    PISO_HIP_CHECK(hipMemcpy(h.data(), pc.timing, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    PISO_HIP_CHECK(hipFree(pc.timing));
-    const char* names[9] = {"D (p update, stencil, sums, publish)", "exchange", "U (stencil, x / r update, ring)", "-", "-",
-                             "  exchange: wave sums + drain of the perimeter stores", "  exchange: first barrier", "  exchange: publish + polling",
-                             "  exchange: record sums + second barrier"};
-    if (opt(OPT_CG_PERSIST_TIMING) >= 2) {                  // the whole table: one line per workgroup (us per iteration)
-      const double f = 0.01 / (double)(k_last > 0 ? k_last : 1);
-      for (int b = 0; b < persist_grid; ++b)
-        fprintf(stderr, "cg_persist_wg %3d xcd %d band %3d  D %.2f  exchange %.2f  U %.2f  | drain %.2f  barrier1 %.2f  publish+poll %.2f  sums %.2f\n", b, (int)h[9 * persist_grid + b], (int)h[10 * persist_grid + b],
-                f * (double)h[0 * persist_grid + b], f * (double)h[1 * persist_grid + b], f * (double)h[2 * persist_grid + b],
-                f * (double)h[5 * persist_grid + b], f * (double)h[6 * persist_grid + b], f * (double)h[7 * persist_grid + b], f * (double)h[8 * persist_grid + b]);
-    }
-    for (int q = 0; q < 9; ++q) {
-      double s = 0, mn = 1e300, mx = 0;
-      for (int b = 0; b < persist_grid; ++b) { const double v = (double)h[q * persist_grid + b]; s += v; mn = v < mn ? v : mn; mx = v > mx ? v : mx; }
-      fprintf(stderr, "cg_persist %s: avg %.2f us/iter  min %.2f  max %.2f\n", names[q], 0.01 * s / persist_grid / (double)(k_last > 0 ? k_last : 1),
-              0.01 * mn / (double)(k_last > 0 ? k_last : 1), 0.01 * mx / (double)(k_last > 0 ? k_last : 1));
-    }
-  }
+  if (timing.ticks) { const int rc = print_persist_timing(timing.ticks, plan.grid, k_last); if (rc != PISO_OK) return rc; }
   if (iterations_out) *iterations_out = finished ? stop_it : total;
   tl_dispatch[DI_SEGMENTS] = segments_run;
-  if (prof) {
-    double ms[2] = {0, 0};
-    for (int q = 0; q < 2; ++q)
-      for (int i = 0; i < ep.used[q]; ++i) {
-        float t = 0;
-        PISO_HIP_CHECK(hipEventElapsedTime(&t, ep.start[q][i], ep.stop[q][i]));
-        ms[q] += t;
-      }
-    if (kernel_ms_out) {
-      kernel_ms_out[0] = ep.used[0] ? (float)(ms[0] / ep.used[0]) : 0.f;
-      kernel_ms_out[1] = ep.used[1] ? (float)(ms[1] / ep.used[1]) : 0.f;
-    }
-    if (g_prof.enabled) {
-      for (int q = 0; q < 2; ++q) { g_prof.ms[q] += ms[q]; g_prof.count[q] += ep.used[q]; }
-      g_prof.ms[2] += seg_ms; g_prof.count[2] += seg_iters; g_prof.count[3] += seg_launches;
-    }
-    if (kernel_ms_out && seg_iters > 0) { kernel_ms_out[0] = (float)(seg_ms / seg_iters); kernel_ms_out[1] = 0.f; }
-  }
-  return PISO_OK;
+  return prof ? read_profile(ep, seg, kernel_ms_out) : PISO_OK;
 }
 
 // rows of nx elements between arrays of different leading dimensions (padded-grid mode: b in, x out)
@@ -594,10 +418,7 @@ static int cg_solve(int nx, int ny, int per_x, int per_y, const T* L, const T* b
                                                  rank_deficient, st_dev, iterations_dev);
     PISO_LAUNCH_CHECK();
     ++g_tiny_solves;
-    for (int i = 0; i < DI_COUNT; ++i) tl_dispatch[i] = 0;
-    tl_dispatch[DI_PATH] = cols ? 1 : 0; tl_dispatch[DI_SIZEOF_T] = tl_dispatch[DI_SIZEOF_CT] = (int)sizeof(T);
-    tl_dispatch[DI_TINY_PER_X] = (cols && per_x) ? 1 : 0;
-    tl_dispatch_n = DI_COUNT;
+    record_dispatch(cols ? 1 : 0, sizeof(T), sizeof(T), (cols && per_x) ? 1 : 0);
     if (async) return PISO_OK;
     if (ev) PISO_HIP_CHECK(hipEventRecord(ev[1], stream));
     CgState hst;
@@ -630,7 +451,7 @@ static int cg_solve(int nx, int ny, int per_x, int per_y, const T* L, const T* b
   a.partsA = ar.take<T>(3 * kMaxPartials); a.partsB = ar.take<T>(3 * kMaxPartials); a.partsS = ar.take<T>(kMaxPartials);
   a.scal = ar.take<T>(SC_COUNT);
   a.state = ar.take<CgState>(2);
-  unsigned* persist_ws = ar.take<unsigned>(kPersistWsWords);
+  unsigned* persist_ws = ar.take<unsigned>(kPersistWsWordsAll);
   a.nx = nxp; a.ny = nyp; a.per_x = per_x; a.per_y = per_y;
   a.nx_true = padded ? nx : 0; a.ny_true = padded ? ny : 0; a.ncells = padded ? (double)n_true : 0.0;
   a.ntx = a.nty = a.rows_per_wave = 0; a.nA = a.nB = 0; a.accuracy = accuracy;
@@ -665,9 +486,11 @@ static int cg_solve(int nx, int ny, int per_x, int per_y, const T* L, const T* b
   constexpr int VMID = 16 / sizeof(T);
   const bool aligned = ((reinterpret_cast<uintptr_t>(a.b) | reinterpret_cast<uintptr_t>(a.x)) & 15) == 0;
   const bool vec = aligned && (nxp % VMID == 0);
-  int rc = PISO_OK;
-#define PISO_CG_RUN(CT, V, RECON) \
-  rc = cg_run<T, CT, V, RECON>(a, persist_ws, symmetric, accuracy, max_iterations, rank_deficient, reset, fixed, iterations_out, kernel_ms_out, stream)
+  int rc = kPersistRetry;
+  // (second attempt: a persistent segment failed - the whole solve again on the two-kernel iteration)
+#define PISO_CG_RUN(CT, V, RECON)                                              \
+  for (int attempt = 0; attempt < 2 && rc == kPersistRetry; ++attempt)         \
+    rc = cg_run<T, CT, V, RECON>(a, persist_ws, symmetric, accuracy, max_iterations, rank_deficient, reset, fixed, iterations_out, kernel_ms_out, stream, attempt == 0)
   if (!hflags[0]) {                                         // (fp32 state: trivially exact - the same path, so that the diagonal can be rebuilt there too)
     a.oS = oF; a.oW = oF + n; a.oE = oF + 2 * n; a.oN = oF + 3 * n;
     if (!hflags[1]) { if (vec) PISO_CG_RUN(float, VMID, true); else PISO_CG_RUN(float, 1, true); }
@@ -679,6 +502,7 @@ static int cg_solve(int nx, int ny, int per_x, int per_y, const T* L, const T* b
     else PISO_CG_RUN(T, 1, false);
   }
 #undef PISO_CG_RUN
+  if (rc == kPersistRetry) { set_error_msg("piso_cg_solve: persistent segment failed twice"); return PISO_ERR_HIP; }
   if (rc != PISO_OK) return rc;
   if (padded) {                                             // (cg_run has synchronised the stream: x_pad is final)
     cg_copy_rows<T><<<gs, kBlock, 0, stream>>>(x_pad, x_out, nx, ny, nxp, nx);

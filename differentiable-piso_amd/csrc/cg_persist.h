@@ -17,7 +17,7 @@ namespace piso {
 
 constexpr int kPersistThreads = 512;            // 8 waves per CU = 2 per SIMD -> 256 VGPRs per lane: state in registers without spills
 constexpr int kPersistWaves = kPersistThreads / 64;
-// region shapes (rows R x regions per wave NQ): 2 x 2, 4 x 2, 8 x 2 and 16 x 1 - at most 16 rows of 128 columns per wave
+// region shapes (rows R x regions per wave NQ): 2 x 1, 2 x 2, 4 x 2 and 16 x 1 - at most 16 rows of 128 columns per wave (cg_dispatch.h)
 
 struct PersistCtl {
   unsigned long long* rec;   // exchange records: [2 (parity)][kPersistMaxGrid][8] 8-byte words, zeroed before every launch

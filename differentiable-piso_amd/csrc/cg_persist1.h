@@ -48,34 +48,6 @@ namespace piso {
 //     same decisions; grid_exchange8_hier<..., XG>);
 //   * N of the slab's last row comes from the N array (its S twin lives on the neighbour), sums of the previous K2 from a.gB.
 struct NoSlab {};
-// region shape of the persistent kernels for an nx x ny grid (V cells per lane, `cus` compute units): one region of 16 rows per
-// wave has the smallest halo overhead and is taken when it keeps at least 3/4 of the waves busy (or when forced); else two
-// regions of 2 / 4 rows per wave (two regions of 8 rows do not fit the registers: such shapes - ny a multiple of 8 but not of 16 on
-// a grid too large for 4-row regions - iterate on the two-kernel path).  R = 0: the grid cannot be tiled (two-kernel iteration).
-struct PersistShape { int R = 0, NQ = 0, nreg = 0, ntx = 0, grid = 0; };
-inline PersistShape persist_shape(int nx, int ny, int V, int cus, int force_r) {
-  PersistShape s;
-  if (nx % (64 * V) != 0) return s;                         // every lane of a strip has cells
-  const int ntx = nx / (64 * V);
-  if (ny % 16 == 0 && (force_r <= 0 || force_r == 16)) {
-    const long long nreg = (long long)ntx * (ny / 16);
-    if (nreg <= (long long)cus * kPersistWaves && (force_r > 0 || 4 * nreg >= 3LL * cus * kPersistWaves)) {
-      s.R = 16; s.NQ = 1; s.nreg = (int)nreg; s.ntx = ntx;
-      s.grid = (int)((nreg + kPersistWaves - 1) / kPersistWaves);
-    }
-  }
-  for (int R : {2, 4}) {
-    if (s.R) break;
-    if (force_r > 0 && force_r != R) continue;
-    if (ny % R != 0) continue;                              // every region has R rows
-    const long long nreg = (long long)ntx * (ny / R);
-    if (nreg % 2 == 0 && nreg <= (long long)cus * kPersistWaves * 2) {   // a wave owns 2 regions or none
-      s.R = R; s.NQ = 2; s.nreg = (int)nreg; s.ntx = ntx;
-      s.grid = (int)((nreg + kPersistWaves * 2 - 1) / (kPersistWaves * 2));
-    }
-  }
-  return s;
-}
 struct SlabCtl {
   PeerView pv;
   double ncells;           // cells of the GLOBAL grid

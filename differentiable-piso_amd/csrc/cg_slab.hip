@@ -24,8 +24,8 @@
 
 #include <vector>
 
+#include "cg_dispatch.h"
 #include "cg_kernels.h"
-#include "cg_persist1.h"
 #include "options.h"
 #include "peer.h"
 #include "slab_comm.h"
@@ -118,7 +118,6 @@ __global__ void slab_gap_to_sum(const unsigned* out2, T* out, int force) {
     out[0] = (T)(((gap > 1e-5f * scale && gap > 1e-30f) || force) ? 1 : 0);
   }
 }
-constexpr size_t kSlabPersistWsWords = kPersistWsWordsAll;   // exchange records + control words (cg_persist.h)
 // loopback all-reduce: bufs of the G virtual ranks live `stride` apart; sum in rank order, write to all
 template <typename T>
 __global__ void loop_allreduce(T* base, int G, size_t stride, int count) {
@@ -293,41 +292,15 @@ static size_t slab_rank_bytes(int nx, int nyl) {
   b += align_up(n * sizeof(T), 256) * 2;                     // z' perimeter buffers of the persistent kernel
   b += 3 * align_up(3 * kMaxPartials * sizeof(T), 256);
   b += 4 * 256 + align_up(16 * sizeof(T), 256);
-  b += align_up(kSlabPersistWsWords * sizeof(unsigned), 256);
+  b += align_up(kPersistWsWordsAll * sizeof(unsigned), 256);
   return b + 4096;
 }
 
 struct SlabPinned { CgState st; int err; int pad[3]; double errsum; };
 static thread_local SlabPinned* tl_slab_pinned = nullptr;
 
-template <typename T, typename CT, bool RECON, bool SYMV>
-static void launch_slab_segment(int R, int grid, const CgArgs<T>& a, const PersistCtl& pc, int kb, int ke, int sv, int pend,
-                                const SlabCtl& sl, hipStream_t stream) {
-  if constexpr (sizeof(T) == 8) {
-    switch (R) {
-      case 2: cg_persist1<T, CT, 2, 2, RECON, SYMV, true><<<grid, kPersistThreads, 0, stream>>>(a, pc, kb, ke, sv, pend, sl); break;
-      case 4: cg_persist1<T, CT, 4, 2, RECON, SYMV, true><<<grid, kPersistThreads, 0, stream>>>(a, pc, kb, ke, sv, pend, sl); break;
-      default: if constexpr (sizeof(CT) == 4 && SYMV) cg_persist1<T, CT, 16, 1, RECON, SYMV, true><<<grid, kPersistThreads, 0, stream>>>(a, pc, kb, ke, sv, pend, sl); break;
-    }
-  }
-}
-template <typename T, typename CT, bool RECON, bool SYMV>
-static const void* slab_segment_kernel(int R) {
-  if constexpr (sizeof(T) == 8) {
-    switch (R) {
-      case 2: return reinterpret_cast<const void*>(&cg_persist1<T, CT, 2, 2, RECON, SYMV, true>);
-      case 4: return reinterpret_cast<const void*>(&cg_persist1<T, CT, 4, 2, RECON, SYMV, true>);
-      default:                                              // (fp64 coefficients or an unsymmetric matrix - a general system - have no 16-row instance: it spills; cg.hip kHas16)
-        if constexpr (sizeof(CT) == 4 && SYMV) return reinterpret_cast<const void*>(&cg_persist1<T, CT, 16, 1, RECON, SYMV, true>);
-        else return nullptr;
-    }
-  }
-  return nullptr;
-}
-
-// returns PISO_OK, an error, or kSlabRetry: a persistent segment failed on some rank -> the caller re-initialises the solve and
+// returns PISO_OK, an error, or kPersistRetry: a persistent segment failed on some rank -> the caller re-initialises the solve and
 // calls again with allow_persist = false
-constexpr int kSlabRetry = -1000;
 template <typename T, typename CT, int V, bool RECON>
 static int slab_iterate(std::vector<SlabRank<T>>& R, Comm<T>& comm, float accuracy, int max_iterations, int reset,
                         int* iterations_out, hipStream_t stream, bool symmetric, bool allow_persist, double global_cells,
@@ -336,66 +309,37 @@ static int slab_iterate(std::vector<SlabRank<T>>& R, Comm<T>& comm, float accura
   std::vector<int> g1(nloc), g2(nloc), gflat(nloc);
   for (int q = 0; q < nloc; ++q) {
     CgArgs<T>& a = R[q].a;
-    const size_t n = (size_t)a.nx * a.ny;
-    a.ntx = (a.nx + 64 * V - 1) / (64 * V);
-    int rpw = (int)(((long long)a.ny * a.ntx) / (4 * 1024));
-    rpw = rpw < 2 ? 2 : (rpw > 16 ? 16 : rpw);
-    a.rows_per_wave = rpw;
-    a.nty = (a.ny + 4 * rpw - 1) / (4 * rpw);
+    const CgTiling tile = cg_tile(a, V, 0, 0);               // (options cg_rpw / cg_maxblocks are the one-GPU driver's)
+    g1[q] = tile.g1; g2[q] = tile.g2; gflat[q] = tile.gflat;
     a.accuracy = accuracy;
-    g1[q] = grid_for((long long)a.ntx * a.nty, 1, 1024);
-    g2[q] = grid_for((long long)((n / V + kBlock - 1) / kBlock), 4);
-    gflat[q] = grid_for((long long)n, kBlock * 4);
-    a.nA = g1[q]; a.nB = g2[q];
     a.gA = R[q].g; a.gB = R[q].g + 4;
   }
   if (!tl_slab_pinned) PISO_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&tl_slab_pinned), sizeof(SlabPinned), hipHostMallocDefault));
 
   // ---- persistent segments (peer transport, one rank per process): the NORMAL iterations of the slab run inside
-  // cg_persist1<..., SLAB>; every rank takes the same decision (same shape, same options, failures are all-reduced)
-  PersistShape shape;
-  PersistCtl pc;
-  pc.rec = nullptr; pc.err = nullptr; pc.nreg = 0; pc.ntx = 0; pc.timing = nullptr; pc.epoch0 = 0; pc.xcd = nullptr; pc.local_n = 0; pc.waves = kPersistWaves;
-  SlabCtl sl;
-  constexpr bool kCanSym = RECON && sizeof(CT) == 4;
-  if (sizeof(T) == 8 && V == 16 / (int)sizeof(T) && allow_persist && comm.peer() && nloc == 1 && opt(OPT_CG_PERSIST) != 0 &&
-      R[0].a.nx <= (int)comm.rccl->row_cap) {
-    int dev = 0, cus = 0, per_cu = 0;
+  // cg_persist1<..., SLAB>; every rank takes the same decision (same shape, same options, failures are all-reduced).  The plan is the
+  // one-GPU driver's (cg_dispatch.h) with full workgroups: a slab has never honoured cg_persist_half / cg_persist_nq / cg_xcd_local
+  PersistPlan plan;
+  int cus = 0;
+  if (allow_persist && comm.peer() && nloc == 1 && R[0].a.nx <= (int)comm.rccl->row_cap) {
+    int dev = 0;
     PISO_HIP_CHECK(hipGetDevice(&dev));
     PISO_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    shape = persist_shape(R[0].a.nx, R[0].a.ny, V, cus, opt(OPT_CG_PERSIST_R));
-    if (shape.R == 8) shape.R = 0;                          // (two regions of 8 rows: cg_persist1 spills registers there)
-    if (shape.R == 16 && (sizeof(CT) == 8 || !(kCanSym && symmetric))) {     // (no 16-row slab instance for general matrices: regions of 4 / 2 rows, or two kernels)
-      shape = PersistShape();
-      if (opt(OPT_CG_PERSIST_R) <= 0) { shape = persist_shape(R[0].a.nx, R[0].a.ny, V, cus, 4); if (!shape.R) shape = persist_shape(R[0].a.nx, R[0].a.ny, V, cus, 2); }
-    }
-    if (shape.R && (size_t)R[0].a.nx * R[0].a.ny < 16384 && opt(OPT_CG_PERSIST) != 1) shape.R = 0;
-    if (shape.R) {
-      const void* kfn = slab_segment_kernel<T, CT, RECON, false>(shape.R);
-      if constexpr (kCanSym) { if (symmetric) kfn = slab_segment_kernel<T, CT, RECON, true>(shape.R); }
-      if (!kfn) shape.R = 0;
-      else {
-        PISO_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, kPersistThreads, 0));
-        if ((long long)per_cu * cus < shape.grid || shape.grid > kPersistMaxGrid) shape.R = 0;
-      }
-    }
-    if (shape.R) {
-      pc.rec = reinterpret_cast<unsigned long long*>(persist_ws);
-      pc.err = reinterpret_cast<int*>(persist_ws + kSlabPersistWsWords - 16);
-      pc.nreg = shape.nreg; pc.ntx = shape.ntx;
-      pc.xcd = reinterpret_cast<int*>(persist_ws + kPersistRecWords);
-      PISO_HIP_CHECK(hipMemsetAsync(persist_ws, 0, kSlabPersistWsWords * sizeof(unsigned), stream));
-      sl.pv = make_view(comm.rccl, comm.periodic_y);
-      sl.ncells = global_cells;
-      sl.rows_own = sl.pv.mbox[sl.pv.rank] + PeerLayout::kRows;
-      sl.rows_lo = sl.pv.mbox[sl.pv.lower >= 0 ? sl.pv.lower : sl.pv.rank] + PeerLayout::kRows;
-      sl.rows_hi = sl.pv.mbox[sl.pv.upper >= 0 ? sl.pv.upper : sl.pv.rank] + PeerLayout::kRows;
-      sl.hop_ticks = opt(OPT_SLAB_HOP_TICKS) > 0 ? (unsigned)opt(OPT_SLAB_HOP_TICKS) : 0u;
-    }
+    plan = persist_plan(PersistQuery{R[0].a.nx, R[0].a.ny, V, R[0].a.per_y, false, sizeof(T), sizeof(CT), RECON, symmetric, true, cus,
+                                     opt(OPT_CG_PERSIST), opt(OPT_CG_PERSIST_R), 0, 0, 0, false, true});
   }
-  int seg_len = (int)(40000.0 / ((double)R[0].a.nx * R[0].a.ny * 8.5e-6 + 4.0));   // ~10 ms of work per segment at 2048^2 per GPU (as cg.hip)
-  seg_len = seg_len < 50 ? 50 : (seg_len > 2000 ? 2000 : seg_len);
-  if (opt(OPT_CG_SEGMENT) > 0) seg_len = opt(OPT_CG_SEGMENT);
+  PersistCtl pc;
+  { const int rc = persist_prepare<T, CT, RECON, true>(plan, cus, pc, persist_ws, stream); if (rc != PISO_OK) return rc; }
+  SlabCtl sl;
+  if (plan.R) {
+    sl.pv = make_view(comm.rccl, comm.periodic_y);
+    sl.ncells = global_cells;
+    sl.rows_own = sl.pv.mbox[sl.pv.rank] + PeerLayout::kRows;
+    sl.rows_lo = sl.pv.mbox[sl.pv.lower >= 0 ? sl.pv.lower : sl.pv.rank] + PeerLayout::kRows;
+    sl.rows_hi = sl.pv.mbox[sl.pv.upper >= 0 ? sl.pv.upper : sl.pv.rank] + PeerLayout::kRows;
+    sl.hop_ticks = opt(OPT_SLAB_HOP_TICKS) > 0 ? (unsigned)opt(OPT_SLAB_HOP_TICKS) : 0u;
+  }
+  const int seg_len = persist_segment_len((size_t)R[0].a.nx * R[0].a.ny, opt(OPT_CG_SEGMENT));   // (per GPU)
 
   auto k1 = [&](int k, int mode, int sv, int chk, int pend) -> int {
     for (int q = 0; q < nloc; ++q) cg_k1<T, CT, V, RECON><<<g1[q], kBlock, 0, stream>>>(R[q].a, k, mode, sv, chk, pend);
@@ -416,7 +360,7 @@ static int slab_iterate(std::vector<SlabRank<T>>& R, Comm<T>& comm, float accura
   for (int k = 0; k < max_iterations && !finished; ++k) {
     const bool is_reset = ((k + 1) % reset == 0);
     int rc = PISO_OK;
-    if (shape.R && k > 0 && !is_reset) {
+    if (plan.R && k > 0 && !is_reset) {
       // NORMAL iterations [k, ke) in one launch: up to the next reset iteration / the end / one segment length
       int ke = max_iterations;
       { const int next_reset = ((k + 1 + reset - 1) / reset) * reset - 1; if (next_reset < ke) ke = next_reset; }
@@ -431,14 +375,8 @@ static int slab_iterate(std::vector<SlabRank<T>>& R, Comm<T>& comm, float accura
           if (rc == PISO_OK) rc = comm.allreduce(R, 12, 1, stream);
           if (rc != PISO_OK) return rc;
         }
-        pc.epoch0 = (c->launches++ & 0xffffu) << 16;
-        PISO_HIP_CHECK(hipMemsetAsync(pc.rec, 0, kPersistZeroBytes, stream));   // records (both levels) + XCD arrivals
-        bool launched = false;
-        if constexpr (kCanSym) {
-          if (symmetric) { launch_slab_segment<T, CT, RECON, true>(shape.R, shape.grid, R[0].a, pc, k, ke, sv, pending ? 1 : 0, sl, stream); launched = true; }
-        }
-        if (!launched) launch_slab_segment<T, CT, RECON, false>(shape.R, shape.grid, R[0].a, pc, k, ke, sv, pending ? 1 : 0, sl, stream);
-        PISO_LAUNCH_CHECK();
+        rc = persist_launch<T, CT, RECON, true>(plan, R[0].a, pc, c->launches++, k, ke, sv, pending, sl, stream);
+        if (rc != PISO_OK) return rc;
         // did the segment fail anywhere?  (g[12] = my error flag, summed over the ranks)
         slab_err_to_sum<T><<<1, 64, 0, stream>>>(pc.err, c->err, R[0].g + 12);
         rc = comm.allreduce(R, 12, 1, stream);
@@ -449,7 +387,7 @@ static int slab_iterate(std::vector<SlabRank<T>>& R, Comm<T>& comm, float accura
         if (tl_slab_pinned->errsum != 0) {
           ++c->persist_fallbacks;
           PISO_HIP_CHECK(hipMemsetAsync(c->err, 0, sizeof(int), stream));
-          return kSlabRetry;
+          return kPersistRetry;
         }
         c->persist_iterations += ke - k;
         ++segments_run;
@@ -511,7 +449,7 @@ static int slab_iterate(std::vector<SlabRank<T>>& R, Comm<T>& comm, float accura
       if (tl_slab_pinned->errsum != 0) {
         ++comm.rccl->verify_failures;
         ++comm.rccl->persist_fallbacks;
-        return kSlabRetry;
+        return kPersistRetry;
       }
     }
   }
@@ -555,7 +493,7 @@ static int slab_solve(std::vector<SlabRank<T>>& R, Comm<T>& comm, int nx, int ny
     CgArgs<T>& a = k.a;
     a.z = ar.take<T>(n);
     a.zp[0] = ar.take<T>(n); a.zp[1] = ar.take<T>(n);   // z' perimeters of the persistent kernel (agent-scope accesses only)
-    k.persist_ws = ar.take<unsigned>(kSlabPersistWsWords);
+    k.persist_ws = ar.take<unsigned>(kPersistWsWordsAll);
     a.partsA = ar.take<T>(3 * kMaxPartials); a.partsB = ar.take<T>(3 * kMaxPartials); a.partsS = ar.take<T>(kMaxPartials);
     a.scal = ar.take<T>(SC_COUNT);
     a.state = ar.take<CgState>(2);
@@ -616,7 +554,7 @@ static int slab_solve(std::vector<SlabRank<T>>& R, Comm<T>& comm, int nx, int ny
     else if (vec) PISO_SLAB_RUN(T, VMID, false);
     else PISO_SLAB_RUN(T, 1, false);
 #undef PISO_SLAB_RUN
-    if (rc != kSlabRetry) return rc;
+    if (rc != kPersistRetry) return rc;
   }
   set_error_msg("slab CG: persistent segment failed twice");
   return PISO_ERR_HIP;

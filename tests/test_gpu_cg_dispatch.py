@@ -2,7 +2,7 @@
 
 One call of piso_cg_solve_* ends in one of about thirty kernel instances, chosen from the grid, the DATA (are the off-diagonals exact
 floats, can the diagonal be rebuilt, is the matrix symmetric bit for bit) and the POINTERS (16-byte alignment of b and x) - cg.hip:
-cg_solve / cg_run.  Every row of ROWS below pins one instance class: the solve goes through the C ABI, the dispatch record
+cg_solve / cg_run over cg_dispatch.h: persist_plan.  Every row of ROWS below pins one instance class: the solve goes through the C ABI, the dispatch record
 (piso_cg_last_dispatch) must EQUAL the row's expectation - written from the dispatch code, not read back from the card - and the result
 is compared with the C oracle (never with another GPU path alone).  Run with `-m gpu` on an MI355X (256 CUs, 8 XCDs: the expected
 persistent shapes assume them).
@@ -115,7 +115,7 @@ ROWS = [
     row("deal-cap8-130x384", "xper_ywall", 130, 384, two(8, 4, 2, 1, rows_per_wave=2, k1_tiles=51, k1_grid=8, k2_grid=24),
         knobs=(("cg_maxblocks", 8), ("cg_persist", 0)), checks="TS"),
     row("deal-cap16-v1-70x131", "periodic", 70, 131, two(8, 4, 1, 1, k1_tiles=27, k1_grid=16), knobs=(("cg_maxblocks", 16),), checks="TS"),
-    # ---- persistent kernel: the instances the DATA picks.  CT = double means regions of 2 / 4 rows (f32_small_regions; a forced 16 has no
+    # ---- persistent kernel: the instances the DATA picks.  CT = double means regions of 2 / 4 rows (persist_instance_exists; a forced 16 has no
     # instance -> two-kernel); an unsymmetric matrix streams all four arrays (SYMV = false), with regions of 2 / 4 / 16 rows
     row("p-c-r2-32x256", "periodic", 32, 256, per(8, 8, 0, 1, 2, 2, 4, 4), cls="C", knobs=(("cg_persist", 1), ("cg_persist_r", 2))),
     row("p-c-r4-32x256", "cavity", 32, 256, per(8, 8, 0, 1, 4, 2, 4, 2), cls="C", knobs=(("cg_persist", 1), ("cg_persist_r", 4)), checks="TK"),
@@ -161,7 +161,7 @@ assert len(ROW) == len(ROWS)
 #   cg_persist1<double, float, 2, 1, ...>    p-r2-32x256 (XCD-local), p-sml-r2-32x256 (chip-wide); NQ = 2: p-nq2-chipwide-64x512
 #   cg_persist1<double, float, R, NQ, RECON, false>   p-u-r2 / p-u-r4 / p-u-r16 (SYMV = false: all four arrays)
 #   cg_persist1<double, double, 2 | 4, 2, false, false>   p-c-r2 / p-c-r4 / p-cu-r2 / p-cu-r4 (a symmetric CT = double system has no
-#                                            SYMV instance: kCanSymO); 16 rows: none exists (kHas16) -> p-c-r16-64x256 is two-kernel
+#                                            SYMV instance, and none of 16 rows: persist_instance_exists) -> p-c-r16-64x256 is two-kernel
 #   cg_persist1<..., RAGGED>                 pad-cavity-72x130 (LOCAL), pad-chipwide-cavity-72x130, pad-r4-cavity-70x130
 #   cg_persist1<..., LOCAL>                  p-r2 / p-r4-32x256, test_persistent_workgroup_knobs
 #   cg_persist1<float, ...>                  test_gpu_kernels.py: test_cg_persistent_float32_state_matches_oracle (record asserted there)
