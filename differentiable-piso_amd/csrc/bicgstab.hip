@@ -1018,10 +1018,18 @@ struct BiHost {
   int flags[2];
 };
 
+// which kernel instances the calling thread's last solve ran (piso_bicgstab_last_dispatch; fields: include/piso_hip.h)
+enum { BD_SIZEOF_T = 0, BD_E, BD_SWEEP_LDS, BD_FACTOR_LDS, BD_R, BD_BANDS_U, BD_BANDS_V, BD_BLOCKS, BD_FOLD, BD_FUSE_P, BD_TRANSPOSE,
+       BD_SLAB, BD_LOOK0, BD_PASSES, BD_HOST_LOOKS, BD_FAILED_MASK, BD_COUNT };
+static thread_local int tl_bi_dispatch[BD_COUNT];
+static thread_local int tl_bi_dispatch_n = 0;
+
 template <typename T, int E>
 static void launch_factor(const BiArgs<T>& a, dim3 gb, hipStream_t s) {
+  tl_bi_dispatch[BD_E] = E;
+  tl_bi_dispatch[BD_FACTOR_LDS] = 0;
   if constexpr (kSweepLds<T, E> && (size_t)5 * (E * kBlock + E * 8) * sizeof(T) <= (size_t)96 * 1024) {
-    if (opt(OPT_BICG_SWEEP_LDS) != 0) { bi_factor_lds<T, E><<<gb, kBlock, 0, s>>>(a); return; }
+    if (opt(OPT_BICG_SWEEP_LDS) != 0) { tl_bi_dispatch[BD_FACTOR_LDS] = 1; bi_factor_lds<T, E><<<gb, kBlock, 0, s>>>(a); return; }
   }
   bi_factor<T, E><<<gb, kBlock, 0, s>>>(a);
 }
@@ -1029,11 +1037,13 @@ template <typename T, int E>
 static void launch_sweeps(const BiArgs<T>& aL, const BiArgs<T>& aU, dim3 gb, const T* in, T* out, hipStream_t s) {
   if constexpr (kSweepLds<T, E>) {
     if (opt(OPT_BICG_SWEEP_LDS) != 0) {
+      tl_bi_dispatch[BD_SWEEP_LDS] = 1;
       bi_sweep_lds<T, E, true><<<gb, kBlock, 0, s>>>(aL, in, aL.y);
       bi_sweep_lds<T, E, false><<<gb, kBlock, 0, s>>>(aU, aU.y, out);
       return;
     }
   }
+  tl_bi_dispatch[BD_SWEEP_LDS] = 0;
   bi_sweep<T, E, true><<<gb, kBlock, 0, s>>>(aL, in, aL.y);
   bi_sweep<T, E, false><<<gb, kBlock, 0, s>>>(aU, aU.y, out);
 }
@@ -1046,6 +1056,7 @@ static int bi_solve(const T* val, const int* rowptr, const int* col, const T* rh
                     int ny, float tol, int max_it, int transpose, int band_rows, uint8_t* warning,
                     int* iterations_out, void* ws, size_t ws_bytes, piso_stream_t stream_, PisoComm* pc = nullptr,
                     const piso_slab_t* slab_rows = nullptr, int per_x = 0, int per_y = 0) {
+  tl_bi_dispatch_n = 0;                                      // (a call refused before it chose leaves no record)
   if (nx < 4 || ny < 4 || !val || !rowptr || !col || !rhs || !x0 || !x_out || !ws || max_it < 0 || !slab_ok(slab_rows, ny) || (slab_rows && !pc)) {
     set_error_msg("piso_multi_bicgstab_ilu: invalid argument (need nx, ny >= 4 and non-NULL arrays)");
     return PISO_ERR_INVALID_ARG;
@@ -1212,6 +1223,14 @@ static int bi_solve(const T* val, const int* rowptr, const int* col, const T* rh
   const int need = (Wmax + kBlock - 1) / kBlock;
   if (need > 32) { set_error_msg("piso_multi_bicgstab_ilu: nx > 8191 not supported"); return PISO_ERR_INVALID_ARG; }
 
+  const int look0 = ntot < 32768 ? 1 : 2;                    // first host look (tiny systems - the lid-driven cavity converges in one iteration: a second one is 13 launches for nothing)
+  {
+    int* d = tl_bi_dispatch;
+    for (int i = 0; i < BD_COUNT; ++i) d[i] = 0;
+    d[BD_SIZEOF_T] = (int)sizeof(T); d[BD_R] = g.R; d[BD_BANDS_U] = nb0; d[BD_BANDS_V] = nb1; d[BD_BLOCKS] = gv + ge;
+    d[BD_TRANSPOSE] = transpose & 3; d[BD_SLAB] = slab ? 1 : 0; d[BD_LOOK0] = look0;
+    tl_bi_dispatch_n = BD_COUNT;                             // (E and the LDS forms: launch_factor / launch_sweeps; the rest as the solve goes)
+  }
   bi_init_scalars<T><<<1, 256, 0, stream>>>(a);
   bi_convert<T><<<grid_v, kBlock, 0, stream>>>(a, val, rowptr, col, x0, transpose & 3);
   if (slab && rccl) { const int rc = comm_rccl_allreduce_i32(pc, a.flags, 2, stream); if (rc != PISO_OK) return rc; }   // (sums: non-zero = set)
@@ -1248,9 +1267,12 @@ static int bi_solve(const T* val, const int* rowptr, const int* col, const T* rh
   auto F = [&](int stage) -> int { return fold_ok ? stage + 1 : 0; };
   // p = r + beta (p - omega v) inside the forward sweep of p_hat (BiArgs::fuse_p): 9 -> 8 launches per iteration.  Option bicg_fuse_p 0: never.
   const int fuse_p = opt(OPT_BICG_FUSE_P) != 0;
+  tl_bi_dispatch[BD_FOLD] = fold_ok ? 1 : 0;
+  tl_bi_dispatch[BD_FUSE_P] = fuse_p;
 
   BiHost<T> host;
   auto fetch = [&]() -> int {
+    tl_bi_dispatch[BD_HOST_LOOKS] += 1;
     PISO_HIP_CHECK(hipMemcpyAsync(host.sc, scbuf0 + 2 * cur, 2 * sizeof(CompScalars<T>), hipMemcpyDeviceToHost, stream));
     PISO_HIP_CHECK(hipMemcpyAsync(host.flags, a.flags, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
     PISO_HIP_CHECK(hipStreamSynchronize(stream));
@@ -1260,12 +1282,13 @@ static int bi_solve(const T* val, const int* rowptr, const int* col, const T* rh
   int failed_mask = 0;      // components that already used their one restart and failed again
   bool pattern_checked = false;
   for (int restart = 0; restart < 2; ++restart) {
+    tl_bi_dispatch[BD_PASSES] = restart + 1;
     // r = b - B x, rh = r, p = v = 0, ||r|| test, first rho / beta
     { const int rc = halo(a.x); if (rc != PISO_OK) return rc; }
     bi_residual_init<T><<<grid_v, kBlock, 0, stream>>>(next(0, true));
     { const int rc = scalar(ST_INIT); if (rc != PISO_OK) return rc; }
     PISO_LAUNCH_CHECK();
-    int it = 0, look = ntot < 32768 ? 1 : 2;                 // (tiny systems - the lid-driven cavity converges in one iteration: a second one is 13 launches for nothing)
+    int it = 0, look = look0;
     bool all_done = false;
     while (it < max_it && !all_done) {
       // iterations between host looks: 2, 2, 4, 8, 16, 16, ... - a solve of 3 iterations (the 2048^2 benchmark) still stops at
@@ -1320,7 +1343,7 @@ static int bi_solve(const T* val, const int* rowptr, const int* col, const T* rh
       failed_mask = fail_now;
     }
   }
-  (void)failed_mask;
+  tl_bi_dispatch[BD_FAILED_MASK] = failed_mask;
   if (slab && !rccl) {
     int herr = 0;
     peer_agree_on_error<><<<1, 64, 0, stream>>>(bp.pv, pc->err, ++pc->seq_ar);      // every rank returns the same status
@@ -1382,6 +1405,12 @@ __global__ __launch_bounds__(kBlock) void csr_matvec_kernel(const float* __restr
 using namespace piso;
 
 extern "C" {
+
+int piso_bicgstab_last_dispatch(int* out, int capacity) {
+  const int n = tl_bi_dispatch_n < capacity ? tl_bi_dispatch_n : capacity;
+  for (int i = 0; i < n; ++i) out[i] = tl_bi_dispatch[i];
+  return tl_bi_dispatch_n;
+}
 
 size_t piso_bicgstab_workspace_bytes(int nx, int ny, int elem_size) {
   return elem_size == 8 ? bi_workspace_bytes<double>(nx, ny) : bi_workspace_bytes<float>(nx, ny);

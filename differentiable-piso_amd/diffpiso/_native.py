@@ -36,6 +36,8 @@ lib.piso_cg_last_xcd_map.restype = _i
 lib.piso_cg_tiny_solves.restype = C.c_longlong
 lib.piso_cg_last_dispatch.argtypes = [_ip, _i]
 lib.piso_cg_last_dispatch.restype = _i
+lib.piso_bicgstab_last_dispatch.argtypes = [_ip, _i]
+lib.piso_bicgstab_last_dispatch.restype = _i
 lib.piso_cg_verify_stats.argtypes = [C.POINTER(C.c_longlong), _ip]
 lib.piso_cg_verify_stats.restype = None
 lib.piso_csr_nnz.argtypes = [_i, _i, _i, _i, _ip, _ip]
@@ -234,3 +236,17 @@ def cg_last_dispatch():
     if n != 0 and n != len(DISPATCH_FIELDS):
         raise PisoNativeError("piso_cg_last_dispatch returned %d fields, this binding knows %d" % (n, len(DISPATCH_FIELDS)))
     return {k: buf[i] for i, k in enumerate(DISPATCH_FIELDS[:n])}
+
+
+BICGSTAB_DISPATCH_FIELDS = ("sizeof_T", "E", "sweep_lds", "factor_lds", "R", "bands_u", "bands_v", "blocks", "fold", "fuse_p", "transpose_flags",
+                            "slab", "look0", "passes", "host_looks", "failed_mask")
+
+
+def bicgstab_last_dispatch():
+    """Which kernel instances this thread's last ILU(0)-BiCGStab solve ran (include/piso_hip.h: piso_bicgstab_last_dispatch), as a dict;
+    {} if the thread has not solved or its last call was refused."""
+    buf = (C.c_int * 32)()
+    n = lib.piso_bicgstab_last_dispatch(buf, 32)
+    if n != 0 and n != len(BICGSTAB_DISPATCH_FIELDS):
+        raise PisoNativeError("piso_bicgstab_last_dispatch returned %d fields, this binding knows %d" % (n, len(BICGSTAB_DISPATCH_FIELDS)))
+    return {k: buf[i] for i, k in enumerate(BICGSTAB_DISPATCH_FIELDS[:n])}

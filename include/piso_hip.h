@@ -135,6 +135,28 @@ int piso_multi_bicgstab_ilu_f64(const double* csr_val, const int* csr_rowptr, co
                                 const double* x0, double* x_out, int nx, int ny, float tol, int max_it, int transpose,
                                 int band_rows, uint8_t* warning, int* iterations_out, void* workspace,
                                 size_t workspace_bytes, piso_stream_t stream);
+/* Which kernel instances the calling thread's last piso_multi_bicgstab_ilu_* solve (one GPU or slab: they share the driver) ran:
+ * out[0 .. min(return value, capacity)); returns the number of fields (0: this thread has not solved, or its last call was refused
+ * before it chose).  Read-only: the record is written on the host while the solve is set up - the last three fields when it returns -
+ * and changes nothing that is computed.  Fields, in this order:
+ *    0 sizeof(T)        8 / 4
+ *    1 E                row elements per thread of bi_factor / bi_sweep: the smallest of 1, 2, 3, 4, 5, 8, 9, 16, 32 with nx + 1 <= 256 E
+ *    2 sweep_lds        1: the sweeps that stage rows through LDS ran (bi_sweep_lds: float E = 5, 8, 9, 16, double E = 5, 8, 9; option
+ *                       bicg_sweep_lds 0: never)
+ *    3 factor_lds       1: likewise the factorisation (bi_factor_lds, the same instances)
+ *    4 R                band height in face rows after the automatic choice and the clamp to ny + 1
+ *    5 bands_u          bands (= workgroups of a sweep) of the u component this rank works on: ceil(ny / R) on one GPU
+ *    6 bands_v          ... of the v component: ceil((ny + 1) / R) - a last band of one row when R divides ny
+ *    7 blocks           workgroups per component of the vector kernels (a multiple of 8, at most 1 024; slab: interior + edge blocks)
+ *    8 fold             1: the scalar stages are folded into the kernels that consume them (one GPU; option bicg_fold 0: never)
+ *    9 fuse_p           1: the direction update runs inside the forward sweep (option bicg_fuse_p 0: never)
+ *   10 transpose_flags  the call's `transpose` argument: bit 0 A^T, bit 1 negated values
+ *   11 slab             1: the rows are split over the ranks of a communicator (or option slab_force)
+ *   12 look0            iterations before the host first fetches the scalar record: 1 below 32 768 rows in all, else 2 (then 2, 2, 4, 8, 16 ...)
+ *   13 passes           1, or 2 when a component ended above 100 tol (or at NaN), was zeroed and run again from x = 0
+ *   14 host_looks       device-to-host fetches of the scalar record over both passes
+ *   15 failed_mask      bit c: component c was above 100 tol after the second pass as well and was returned as zeros */
+int piso_bicgstab_last_dispatch(int* out, int capacity);
 
 /* y = A x (transpose == 0) or A^T x on the concatenated two-matrix CSR; the H-operator product of the second corrector
  * (diffpiso/piso_helpers.py:209-223 uses tf.gather/segment_sum for it). */

@@ -197,8 +197,10 @@ def ilu_apply(n, lu, rp, col, vec, keep=None):
     return out
 
 
-def bicgstab_ilu(val, rp, col, rhs, x0, tol, max_it, transpose=False, keep=None, dtype=np.float32):
-    """One component of MultiBicgstabIluLinearSolve on the CPU. Returns (x, warn, iterations)."""
+def bicgstab_ilu(val, rp, col, rhs, x0, tol, max_it, transpose=False, keep=None, dtype=np.float32, history=False):
+    """One component of MultiBicgstabIluLinearSolve on the CPU. Returns (x, warn, iterations).
+    history: a fourth value, (norms of the first pass, norms of the second pass) - every norm the stopping test looked at, in order:
+    ||r0||, then ||s|| and ||r|| of each iteration (oracle_bicgstab_ilu_hist_*; the second list is empty without a restart)."""
     ct, s = _ct(dtype)
     n = rp.size - 1
     val = np.ascontiguousarray(val, dtype)
@@ -209,6 +211,17 @@ def bicgstab_ilu(val, rp, col, rhs, x0, tol, max_it, transpose=False, keep=None,
     x = np.zeros(n, dtype)
     warn = np.zeros(1, np.uint8)
     kp = _p(np.ascontiguousarray(keep, np.uint8), C.c_uint8) if keep is not None else None
+    if history:
+        cap = 2 * (1 + 2 * int(max_it))
+        hist, info = np.zeros(cap, dtype), np.zeros(2, np.int32)
+        it = getattr(lib(), "oracle_bicgstab_ilu_hist_" + s)(n, _p(val, ct), _p(rp, C.c_int), _p(col, C.c_int), _p(rhs, ct),
+                                                             _p(x0, ct), _p(x, ct), C.c_float(tol), int(max_it),
+                                                             int(bool(transpose)), kp, _p(warn, C.c_uint8), _p(hist, ct), cap,
+                                                             _p(info, C.c_int))
+        n_h, second = int(info[0]), int(info[1])
+        assert n_h <= cap
+        first = hist[:n_h] if second < 0 else hist[:second]
+        return x, bool(warn[0]), it, (first.copy(), hist[second:n_h].copy() if second >= 0 else hist[:0].copy())
     it = getattr(lib(), "oracle_bicgstab_ilu_" + s)(n, _p(val, ct), _p(rp, C.c_int), _p(col, C.c_int), _p(rhs, ct),
                                                     _p(x0, ct), _p(x, ct), C.c_float(tol), int(max_it),
                                                     int(bool(transpose)), kp, _p(warn, C.c_uint8))
@@ -216,13 +229,14 @@ def bicgstab_ilu(val, rp, col, rhs, x0, tol, max_it, transpose=False, keep=None,
 
 
 def multi_bicgstab_ilu(val, rowptr, col, rhs, x0, n_u, n_v, tol, max_it, transpose=False, band_rows=None,
-                       grid=None, dtype=np.float32):
+                       grid=None, dtype=np.float32, history=False):
     """MultiBicgstabIluLinearSolveLauncher (multi_bicgstab_ilu_linear_solve_op.cu.cc:455-531): u then v component
-    on the concatenated CSR layout. band_rows/grid=(nx, ny) switch on the structured-block drop mask. Returns (x, warn, its)."""
+    on the concatenated CSR layout. band_rows/grid=(nx, ny) switch on the structured-block drop mask. Returns (x, warn, its);
+    history: a fourth value, the two components' norm histories (see bicgstab_ilu)."""
     nnz_u = int(rowptr[n_u])
     out = np.zeros(n_u + n_v, dtype)
     warn = False
-    its = []
+    its, hists = [], []
     segs = [(0, n_u, 0, nnz_u, rowptr[:n_u + 1]), (n_u, n_v, nnz_u, int(rowptr[n_u + 1 + n_v]), rowptr[n_u + 1:])]
     for c, (r0, n, k0, nnz, rp) in enumerate(segs):
         v, cl = val[k0:k0 + nnz], col[k0:k0 + nnz]
@@ -235,8 +249,10 @@ def multi_bicgstab_ilu(val, rowptr, col, rhs, x0, n_u, n_v, tol, max_it, transpo
                 keep = band_keep_mask(W, H, band_rows, trp, tcl)
             else:
                 keep = band_keep_mask(W, H, band_rows, rp, cl)
-        x, w, it = bicgstab_ilu(v, rp, cl, rhs[r0:r0 + n], x0[r0:r0 + n], tol, max_it, transpose, keep, dtype)
+        res = bicgstab_ilu(v, rp, cl, rhs[r0:r0 + n], x0[r0:r0 + n], tol, max_it, transpose, keep, dtype, history)
+        x, w, it = res[:3]
         out[r0:r0 + n] = x
         warn = warn or w
         its.append(it)
-    return out, warn, its
+        hists.append(res[3] if history else None)
+    return (out, warn, its, hists) if history else (out, warn, its)

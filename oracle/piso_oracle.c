@@ -369,15 +369,22 @@ DEFINE_CSR(double, f64)
  * one component.  x0 = initial guess, result in x.  warning[0] is set on NaN input norms (:245-256).
  * keep: optional preconditioner drop mask on the entries of the matrix actually factorised (the transposed
  * one when transpose != 0); NULL == reference.  Returns the total iteration count (it_count). */
+#define BICG_HIST(v) do { if (hist && hn < hist_cap) hist[hn] = (v); ++hn; } while (0)
 #define DEFINE_BICG(T, S, SQRT)                                                                            \
   static T bicg_dot_##S(int n, const T* a, const T* b) {                                                   \
     T s = 0;                                                                                               \
     for (int k = 0; k < n; ++k) s += a[k] * b[k];                                                          \
     return s;                                                                                              \
   }                                                                                                        \
-  ORACLE_API int oracle_bicgstab_ilu_##S(int n, const T* val_in, const int* rp_in, const int* col_in,      \
-                                         const T* rhs, const T* x0, T* x, float tol, int max_it,           \
-                                         int transpose, const uint8_t* keep, uint8_t* warning) {           \
+  /* hist (may be NULL): every norm the stopping test looked at, in order - per pass ||r0||, then per iteration  \
+   * ||s|| and ||r|| (a pass that breaks at ||s|| has no ||r|| for that iteration); at most hist_cap are stored. \
+   * hist_info[0] = how many there were, hist_info[1] = index of the second pass's ||r0||, or -1.  Observation   \
+   * only: nothing computed depends on it. */                                                              \
+  ORACLE_API int oracle_bicgstab_ilu_hist_##S(int n, const T* val_in, const int* rp_in, const int* col_in, \
+                                              const T* rhs, const T* x0, T* x, float tol, int max_it,      \
+                                              int transpose, const uint8_t* keep, uint8_t* warning,        \
+                                              T* hist, int hist_cap, int* hist_info) {                     \
+    int hn = 0, h2 = -1;                                                                                   \
     const int nnz = rp_in[n];                                                                              \
     T* val = (T*)malloc(sizeof(T) * (size_t)nnz);                                                          \
     int* rp = (int*)malloc(sizeof(int) * (size_t)(n + 1));                                                 \
@@ -406,6 +413,8 @@ DEFINE_CSR(double, f64)
       oracle_csr_spmv_##S(n, val, rp, col, x, r);                                                          \
       for (int k = 0; k < n; ++k) r[k] = rhs[k] - r[k];                                                    \
       nrm_r = SQRT(bicg_dot_##S(n, r, r));                                                                 \
+      if (restart) h2 = hn;                                                                                \
+      BICG_HIST(nrm_r);                                                                                    \
       if (nrm_r < tol) break; /* goto endofloop :290-292 */                                                \
       for (int k = 0; k < n; ++k) { rh[k] = r[k]; v[k] = 0; p[k] = 0; }                                    \
       for (int i = 0; i < max_it; i++) {                                                                   \
@@ -420,6 +429,7 @@ DEFINE_CSR(double, f64)
         for (int k = 0; k < n; ++k) x[k] += alpha * p_hat[k];                                              \
         for (int k = 0; k < n; ++k) r[k] -= alpha * v[k];                                                  \
         nrm_r = SQRT(bicg_dot_##S(n, r, r));                                                               \
+        BICG_HIST(nrm_r);                                                                                  \
         if (nrm_r < tol) break;                                                                            \
         oracle_ilu_apply_##S(n, lu, rp, col, keep, r, z, s_hat);                                           \
         oracle_csr_spmv_##S(n, val, rp, col, s_hat, t);                                                    \
@@ -427,6 +437,7 @@ DEFINE_CSR(double, f64)
         for (int k = 0; k < n; ++k) x[k] += omega * s_hat[k];                                              \
         for (int k = 0; k < n; ++k) r[k] -= omega * t[k];                                                  \
         nrm_r = SQRT(bicg_dot_##S(n, r, r));                                                               \
+        BICG_HIST(nrm_r);                                                                                  \
         if (nrm_r < tol) break;                                                                            \
       }                                                                                                    \
       if (nrm_r > tol * 100 || isnan(nrm_r)) { /* :392-407: zero the solution, retry once */               \
@@ -434,7 +445,14 @@ DEFINE_CSR(double, f64)
       } else break;                                                                                        \
     }                                                                                                      \
     free(w); free(lu); free(val); free(rp); free(col);                                                     \
+    if (hist_info) { hist_info[0] = hn; hist_info[1] = h2; }                                               \
     return it_count;                                                                                       \
+  }                                                                                                        \
+  ORACLE_API int oracle_bicgstab_ilu_##S(int n, const T* val_in, const int* rp_in, const int* col_in,      \
+                                         const T* rhs, const T* x0, T* x, float tol, int max_it,           \
+                                         int transpose, const uint8_t* keep, uint8_t* warning) {           \
+    return oracle_bicgstab_ilu_hist_##S(n, val_in, rp_in, col_in, rhs, x0, x, tol, max_it, transpose, keep, \
+                                        warning, NULL, 0, NULL);                                           \
   }
 DEFINE_BICG(float, f32, sqrtf)
 DEFINE_BICG(double, f64, sqrt)

@@ -393,6 +393,9 @@ def test_bicgstab_folded_scalar_stages_are_bitwise_neutral(name, shape, transpos
 _KERNEL_VARIANT_CASES = [("periodic", (40, 36), False, 1e-5, 200), ("cavity", (40, 36), True, 1e-30, 5), ("spatial_ml", (40, 36), False, 1e-30, 3),
                          ("periodic", (64, 1300), False, 1e-6, 50), ("xper_ywall", (48, 1280), True, 1e-30, 4),      # rows of > 1 024 faces: bi_sweep_lds
                          ("periodic", (16, 2304), False, 1e-30, 3)]                                                # E = 10 -> the 16-element instance (padded LDS slots)
+# (float64 has no LDS instance at E = 16 - four staged rows would need 132 KB - so the float64 leg of the last case compares bi_sweep with
+# itself under bicg_sweep_lds and is a real comparison for bicg_fuse_p only; float64's LDS forms are compared at 64 x 1300 and 48 x 1280,
+# E = 8, and every instance is held to the oracle in test_gpu_bicgstab_dispatch.py)
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
