@@ -52,12 +52,12 @@ __global__ __launch_bounds__(kBlock) void conv_forward_kernel(ConvGeom g, const 
 #pragma unroll
     for (int n = 0; n < NT; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
   if constexpr (CINP >= 16) {
-    // Software pipeline over the K-blocks (tap row, tap column, block of 16 channels): the operands of block s + 1 are loaded while
+    // Software pipeline over the K-blocks (tap row, block of 16 channels, tap column): the operands of block s + 1 are loaded while
     // the 16 MT NT / 4 MFMAs of block s run - issued and consumed in the same block the loop ran at the latency of one L2 round
     // trip per block (forward 3 x 3, 64 -> 64: 264 us at 256 x 896, 40 % of the fp32 MFMA peak).
     constexpr int CB = CINP / 16, NSEQ = KS * CB;
     auto load_ab = [&](int yy, int sidx, f32x4 (&a)[MT], f32x4 (&b)[NT], int ky) __attribute__((always_inline)) {
-      const int kx = sidx / CB, cb = sidx - kx * CB;
+      const int cb = sidx / KS, kx = sidx - cb * KS;         // (block of 16 channels outside, tap column inside: the staged kernel's K order)
 #pragma unroll
       for (int m = 0; m < MT; ++m) {
         const int xx = x0 + 16 * m + ai + kx - g.pad;
@@ -144,7 +144,8 @@ __global__ __launch_bounds__(kBlock) void conv_forward_kernel(ConvGeom g, const 
 //     wave; the tap columns read it at pixel offsets 0 .. KS - 1 (a lane's 16-byte reads cover a contiguous KB: conflict-free).
 // L2 traffic per stage and wave: (64 + KS - 1) 64 B + KS NT KB / 4 instead of KS (4 + NT) KB (3 x 3, 64 -> 64: 7.2 instead of 24 KB).
 // Double-buffered: the next stage's operands travel from L2 into registers while the MFMAs of this stage run, are written to the
-// other LDS buffer behind them, one barrier per stage.  Same K order per output as the kernel above: the same bits.
+// other LDS buffer behind them, one barrier per stage.  Same K order per output as the kernel above (tap row, block of 16 channels, tap
+// column, channel): the same bits - tests/test_gpu_conv_dispatch.py compares them.
 template <int KS, int CINP, int NT, bool LEAKY_OUT>
 __global__ __launch_bounds__(kBlock) void conv_forward_lds_kernel(ConvGeom g, const float* __restrict__ in, const float* __restrict__ w,
                                                                    float* __restrict__ out) {
@@ -329,10 +330,11 @@ __global__ __launch_bounds__(kBlock) void conv_wgrad_lds_kernel(ConvGeom g, cons
   constexpr int CINP16 = 16 * MTI, COUTP = 16 * NT;
   constexpr int GV = CH * COUTP / 4, IV = KS * PA * CINP16 / 4;            // 16-byte words of a staged chunk
   constexpr int NG = (GV + kBlock - 1) / kBlock, NI = (IV + kBlock - 1) / kBlock;
-  __shared__ f32x4 Gs[2][GV], Is[2][IV];
+  __shared__ f32x4 Gs[2][GV], Is[2][IV + 1];                // (Is[.][IV]: a word of zeros, never overwritten - see `live` below)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int ai = lane & 15, ak = lane >> 4;
   const int item0 = (blockIdx.y * 4 + wave) * IPW;
+  if (threadIdx.x < 2) Is[threadIdx.x][IV] = (f32x4){0.f, 0.f, 0.f, 0.f};
   f32x4 acc[IPW][NT];
 #pragma unroll
   for (int t = 0; t < IPW; ++t)
@@ -362,7 +364,8 @@ __global__ __launch_bounds__(kBlock) void conv_wgrad_lds_kernel(ConvGeom g, cons
       const int c4 = (i % (CINP16 / 4)) * 4, rest = i / (CINP16 / 4), px = rest % PA, ky = rest / PA;
       const int yy = y + ky - g.pad, xx = x0 + px - g.pad;
       ri[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      // (a pixel of `in` beyond the output row's last pixel + KS - 1 is never paired with a non-zero gout: the chunk's own bound suffices)
+      // (a pixel of `in` beyond the output row's last pixel + KS - 1 is only ever paired with output pixels that do not exist: the inner
+      // loop masks those, the chunk's own bound suffices here)
       if (i < IV && yy >= 0 && yy < g.H && xx >= 0 && xx < g.W && c4 < g.cin) ri[t] = *reinterpret_cast<const f32x4*>(in + ((size_t)yy * g.W + xx) * g.cin + c4);
     }
   };
@@ -381,6 +384,7 @@ __global__ __launch_bounds__(kBlock) void conv_wgrad_lds_kernel(ConvGeom g, cons
     if (working) {
       const float* gs = reinterpret_cast<const float*>(Gs[buf]);
       const float* is = reinterpret_cast<const float*>(Is[buf]);
+      const int live = g.Wo - (s - (s / chunks_x) * chunks_x) * CH;      // output pixels of this chunk that exist
 #pragma unroll
       for (int q = 0; q < CH / 16; ++q) {
         float a[4][IPW], b[4][NT];
@@ -389,8 +393,11 @@ __global__ __launch_bounds__(kBlock) void conv_wgrad_lds_kernel(ConvGeom g, cons
           const int px = 16 * q + 4 * u + ak;
 #pragma unroll
           for (int n = 0; n < NT; ++n) b[u][n] = gs[px * COUTP + 16 * n + ai];
+          // (beyond the row's last output pixel gout is staged as zero, but the pixel of `in` a tap pairs with it may be a real one: it takes
+          // no part in this weight's sum, so it must not reach the MFMA - 0 x NaN is NaN.  The direct kernel's `x < g.Wo` says the same;
+          // here the ADDRESS is switched to the word of zeros: one select per operand, no second copy of it in registers)
 #pragma unroll
-          for (int t = 0; t < IPW; ++t) a[u][t] = is[px * CINP16 + aoff[t]];
+          for (int t = 0; t < IPW; ++t) a[u][t] = is[px < live ? px * CINP16 + aoff[t] : 4 * IV];
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u)
@@ -479,10 +486,11 @@ __global__ __launch_bounds__(64 * KS) void conv_wgrad64_lds_kernel(ConvGeom g, c
                                                                     float* __restrict__ part, int rows_per_block) {
   constexpr int TAPS = KS * KS, CH = 32, PA = CH + KS - 1, NTH = 64 * KS;   // (chunks of 32 pixels: 33 KB of LDS, four workgroups = 12 waves per CU)
   constexpr int NLB = (CH * 16 + NTH - 1) / NTH, NLA = (PA * 16 + NTH - 1) / NTH;       // 16-byte loads per thread: gout chunk, in chunk
-  __shared__ f32x4 Gs[2][CH * 16], Is[2][PA * 16];          // [pixel][16 groups of 4 channels]
+  __shared__ f32x4 Gs[2][CH * 16], Is[2][PA * 16 + 1];      // [pixel][16 groups of 4 channels]; Is[.][PA * 16]: zeros, never overwritten
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int ai = lane & 15, ak = lane >> 4;
   const int ky = blockIdx.y, kx = wave;                      // (one workgroup = one tap row, one wave per tap column)
+  if (threadIdx.x < 2) Is[threadIdx.x][PA * 16] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const int tap = ky * KS + kx;
   f32x4 acc[4][4];
 #pragma unroll
@@ -521,6 +529,7 @@ __global__ __launch_bounds__(64 * KS) void conv_wgrad64_lds_kernel(ConvGeom g, c
     const int buf = s & 1;
     if (s + 1 < nsteps) { const int yn = y_begin + (s + 1) / chunks_x, cn = (s + 1) - ((s + 1) / chunks_x) * chunks_x; fetch(yn, cn); }
     // (a tap row outside the image was staged as zeros: its products vanish; same as the `continue` of the direct kernel)
+    const int live = g.Wo - (s - (s / chunks_x) * chunks_x) * CH;        // output pixels of this chunk that exist
 #pragma unroll
     for (int q = 0; q < CH / 16; ++q) {                     // 16 pixels = 4 x (4 pixels, one per lane group ak)
       f32x4 a[4], b[4];
@@ -528,7 +537,9 @@ __global__ __launch_bounds__(64 * KS) void conv_wgrad64_lds_kernel(ConvGeom g, c
       for (int u = 0; u < 4; ++u) {
         const int px = 16 * q + 4 * u + ak;
         b[u] = Gs[buf][px * 16 + ai];
-        a[u] = Is[buf][(px + kx) * 16 + ai];
+        // (a pixel of `in` paired with an output pixel beyond the row's end takes no part in the sum: 0 x NaN is NaN; as `x < g.Wo` above.
+        // The address is switched to the word of zeros)
+        a[u] = Is[buf][px < live ? (px + kx) * 16 + ai : PA * 16];
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u)
@@ -594,15 +605,38 @@ __global__ __launch_bounds__(kBlock) void conv_wgrad_reduce4_kernel(const float*
   __syncthreads();
   if (wave == 0 && k4 < n4) *reinterpret_cast<f32x4*>(dw + (size_t)k4 * 4) = ((sm[threadIdx.x] + sm[64 + threadIdx.x]) + sm[128 + threadIdx.x]) + sm[192 + threadIdx.x];
 }
-static void launch_wgrad_reduce(const float* part, float* dw, int nblocks, int taps, int cinp16, int coutp, int cin, int cout, hipStream_t stream) {
+// (returns the reducer that ran, as piso_conv_last_dispatch reports it: 4 the 4-wide one, 1 the scalar one)
+static int launch_wgrad_reduce(const float* part, float* dw, int nblocks, int taps, int cinp16, int coutp, int cin, int cout, hipStream_t stream) {
   const int n = taps * cin * cout;
-  if (cout % 4 == 0 && coutp % 4 == 0) conv_wgrad_reduce4_kernel<<<(n / 4 + 63) / 64, kBlock, 0, stream>>>(part, dw, nblocks, taps, cinp16, coutp, cin, cout);
-  else conv_wgrad_reduce_kernel<<<(n + 63) / 64, kBlock, 0, stream>>>(part, dw, nblocks, taps, cinp16, coutp, cin, cout);
+  if (cout % 4 == 0 && coutp % 4 == 0) {
+    conv_wgrad_reduce4_kernel<<<(n / 4 + 63) / 64, kBlock, 0, stream>>>(part, dw, nblocks, taps, cinp16, coutp, cin, cout);
+    return 4;
+  }
+  conv_wgrad_reduce_kernel<<<(n + 63) / 64, kBlock, 0, stream>>>(part, dw, nblocks, taps, cinp16, coutp, cin, cout);
+  return 1;
 }
 
 // row bands = partial sums per weight: what the second stage has to add (and re-read).  256: one output row per band at config 4's
 // size - with bands of two rows the 9 x 126 waves of the 64 -> 64 layer left SIMDs with two waves next to SIMDs with one
 constexpr int kWgradMaxBlocks = 256;
+
+// which kernel instance the calling thread's last convolution ran (piso_conv_last_dispatch; fields: include/piso_hip.h)
+enum { CD_ENTRY = 0, CD_KS, CD_C, CD_NT, CD_IPW, CD_FAMILY, CD_LEAKY, CD_GRID_X, CD_GRID_Y, CD_BLOCK, CD_ROWS_PER_BLOCK, CD_NBLOCKS, CD_REDUCER,
+       CD_HO, CD_WO, CD_COUNT };
+enum { CF_FWD_DIRECT = 0, CF_FWD_LDS, CF_WG_GENERIC, CF_WG_GENERIC_LDS, CF_WG_PACK4, CF_WG_64, CF_WG_64_LDS };
+static thread_local int tl_conv_dispatch[CD_COUNT];
+static thread_local int tl_conv_dispatch_n = 0;
+static void record_forward(const ConvGeom& g, int ks, int cinp, int nt, int family, int leaky, int grid) {
+  const int r[CD_COUNT] = {1, ks, cinp, nt, 0, family, leaky != 0, grid, 1, kBlock, 0, 0, 0, g.Ho, g.Wo};
+  for (int i = 0; i < CD_COUNT; ++i) tl_conv_dispatch[i] = r[i];
+  tl_conv_dispatch_n = CD_COUNT;
+}
+static void record_wgrad(const ConvGeom& g, int ks, int mti, int nt, int ipw, int family, int grid_y, int block, int rows_per_block, int nblocks,
+                         int reducer) {
+  const int r[CD_COUNT] = {2, ks, mti, nt, ipw, family, 0, nblocks, grid_y, block, rows_per_block, nblocks, reducer, g.Ho, g.Wo};
+  for (int i = 0; i < CD_COUNT; ++i) tl_conv_dispatch[i] = r[i];
+  tl_conv_dispatch_n = CD_COUNT;
+}
 
 template <int KS, int CINP, int NT>
 static int launch_forward(const ConvGeom& g, const float* in, const float* w, float* out, int leaky, hipStream_t stream) {
@@ -612,6 +646,7 @@ static int launch_forward(const ConvGeom& g, const float* in, const float* w, fl
       if (leaky) conv_forward_lds_kernel<KS, CINP, NT, true><<<grid2, kBlock, 0, stream>>>(g, in, w, out);
       else conv_forward_lds_kernel<KS, CINP, NT, false><<<grid2, kBlock, 0, stream>>>(g, in, w, out);
       PISO_LAUNCH_CHECK();
+      record_forward(g, KS, CINP, NT, CF_FWD_LDS, leaky, grid2);
       return PISO_OK;
     }
   }
@@ -620,6 +655,7 @@ static int launch_forward(const ConvGeom& g, const float* in, const float* w, fl
   if (leaky) conv_forward_kernel<KS, CINP, NT, true><<<grid, kBlock, 0, stream>>>(g, in, w, out);
   else conv_forward_kernel<KS, CINP, NT, false><<<grid, kBlock, 0, stream>>>(g, in, w, out);
   PISO_LAUNCH_CHECK();
+  record_forward(g, KS, CINP, NT, CF_FWD_DIRECT, leaky, grid);
   return PISO_OK;
 }
 
@@ -638,8 +674,9 @@ static int launch_wgrad(const ConvGeom& g, const float* in, const float* gout, f
   }
   if (!staged) conv_wgrad_kernel<KS, MTI, NT, IPW, PACK4><<<dim3(nblocks, groups), kBlock, 0, stream>>>(g, in, gout, part, rows_per_block);
   PISO_LAUNCH_CHECK();
-  launch_wgrad_reduce(part, dw, nblocks, KS * KS, 16 * MTI, 16 * NT, g.cin, g.cout, stream);
+  const int reducer = launch_wgrad_reduce(part, dw, nblocks, KS * KS, 16 * MTI, 16 * NT, g.cin, g.cout, stream);
   PISO_LAUNCH_CHECK();
+  record_wgrad(g, KS, MTI, NT, IPW, PACK4 ? CF_WG_PACK4 : staged ? CF_WG_GENERIC_LDS : CF_WG_GENERIC, groups, kBlock, rows_per_block, nblocks, reducer);
   return PISO_OK;
 }
 
@@ -668,6 +705,12 @@ __global__ __launch_bounds__(kBlock) void leaky_backward_tail_kernel(const float
 }  // namespace piso
 
 extern "C" {
+int piso_conv_last_dispatch(int* out, int capacity) {
+  const int n = tl_conv_dispatch_n < capacity ? tl_conv_dispatch_n : capacity;
+  for (int i = 0; i < n; ++i) out[i] = tl_conv_dispatch[i];
+  return tl_conv_dispatch_n;
+}
+
 int piso_leaky_relu_backward(const float* grad_out, const float* out, float* grad_pre, size_t n, piso_stream_t stream_) {
   using namespace piso;
   if (!grad_out || !out || !grad_pre) { set_error_msg("piso_leaky_relu_backward: invalid argument"); return PISO_ERR_INVALID_ARG; }
@@ -681,6 +724,7 @@ int piso_leaky_relu_backward(const float* grad_out, const float* out, float* gra
 }
 
 static inline int padded_cin(int cin) { return cin <= 4 ? 4 : round_up(cin, 16); }
+static inline bool misaligned16(const void* a, const void* b) { return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) != 0; }
 
 // Weight layout expected by piso_conv2d_forward (zero filled beyond the true channel counts), COUTP = round_up(cout, 16):
 //   cin <= 4 : [ks][ks][4][COUTP]                                 (HWIO, channels padded to 4)
@@ -699,6 +743,10 @@ int piso_conv2d_forward(const float* in, const float* w_laid_out, float* out, in
   g.Ho = H + 2 * pad - ks + 1; g.Wo = W + 2 * pad - ks + 1;
   if (!in || !w_laid_out || !out || g.Ho < 1 || g.Wo < 1 || cin < 1 || cout < 1 || cout > 64 || cin > 64 || (cin > 4 && cin % 16 != 0)) {
     set_error_msg("piso_conv2d_forward: invalid argument (channels: 1..4 or a multiple of 16 up to 64 in, 1..64 out; kernel size 1 | 3 | 5 | 7)");
+    return PISO_ERR_INVALID_ARG;
+  }
+  if (cin > 4 && misaligned16(in, w_laid_out)) {           // (16 channels and more: every operand is a 16-byte load)
+    set_error_msg("piso_conv2d_forward: invalid argument (with more than 4 input channels `in` and `w_laid_out` must be 16-byte aligned)");
     return PISO_ERR_INVALID_ARG;
   }
   hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -726,6 +774,12 @@ int piso_conv2d_wgrad(const float* in, const float* grad_out, float* dw, int H, 
     set_error_msg("piso_conv2d_wgrad: invalid argument");
     return PISO_ERR_INVALID_ARG;
   }
+  // (cout % 4 == 0: the 4-wide reducer reads the partials and writes dw with 16-byte accesses; cin % 4 == 0 as well: the staged kernels
+  // and the 64 -> 64 kernels load `in` and `grad_out` that way)
+  if ((cout % 4 == 0 && misaligned16(dw, workspace)) || (cin % 4 == 0 && cout % 4 == 0 && misaligned16(in, grad_out))) {
+    set_error_msg("piso_conv2d_wgrad: invalid argument (cout % 4 == 0: `dw` and `workspace` must be 16-byte aligned; cin % 4 == 0 as well: `in` and `grad_out` too)");
+    return PISO_ERR_INVALID_ARG;
+  }
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   float* part = static_cast<float*>(workspace);
   const int mti = round_up(cin, 16) / 16, nt = round_up(cout, 16) / 16;
@@ -734,11 +788,13 @@ int piso_conv2d_wgrad(const float* in, const float* grad_out, float* dw, int H, 
   if (cin == 64 && cout == 64 && ks == 3) {      // (measured: 304 us against 329 us for the generic kernel at 250 x 876; the 1 x 1
     // layer has a single tap, i.e. one busy wave per workgroup here, and stays on the generic kernel: 130 us against 219 us)
     const int rows_per_block = (g.Ho + kWgradMaxBlocks - 1) / kWgradMaxBlocks, nblocks = (g.Ho + rows_per_block - 1) / rows_per_block;
-    if (opt(OPT_CONV_LDS) != 0) conv_wgrad64_lds_kernel<3><<<dim3(nblocks, 3), 192, 0, stream>>>(g, in, grad_out, part, rows_per_block);
+    const bool staged = opt(OPT_CONV_LDS) != 0;
+    if (staged) conv_wgrad64_lds_kernel<3><<<dim3(nblocks, 3), 192, 0, stream>>>(g, in, grad_out, part, rows_per_block);
     else conv_wgrad64_kernel<3><<<dim3(nblocks, 3), 192, 0, stream>>>(g, in, grad_out, part, rows_per_block);
     PISO_LAUNCH_CHECK();
-    launch_wgrad_reduce(part, dw, nblocks, ks * ks, 64, 64, 64, 64, stream);
+    const int reducer = launch_wgrad_reduce(part, dw, nblocks, ks * ks, 64, 64, 64, 64, stream);
     PISO_LAUNCH_CHECK();
+    record_wgrad(g, 3, 4, 4, 1, staged ? CF_WG_64_LDS : CF_WG_64, 3, 192, rows_per_block, nblocks, reducer);
     return PISO_OK;
   }
   // (items per wave: enough waves to fill the chip, few enough registers for the 4 x 4-pixel prefetch)

@@ -1,8 +1,8 @@
 // Tuning / test knobs of libpiso_hip.so.  Every knob has a default taken ONCE, when the library is loaded, from the
 // environment variable PISO_<NAME> (upper case); afterwards only piso_set_option() changes it.  -1 = "not set / automatic".
 // None of them changes WHAT is computed: they pick between implementations of the same arithmetic (kernel instance, staging, launch shape) or
-// switch a check / a measurement aid on and off.  Bitwise the same result: cg_no_compact, cg_no_recon, cg_no_sym, cg_nt and the bicg_* knobs
-// (same operations in the same order).  Equal to round-off only - they change which workgroup or block owns which cells, so the partial
+// switch a check / a measurement aid on and off.  Bitwise the same result: cg_no_compact, cg_no_recon, cg_no_sym, cg_nt, the bicg_* knobs and
+// conv_lds (same operations in the same order; tests/test_gpu_conv_dispatch.py holds conv_lds to it, non-finite inputs included).  Equal to round-off only - they change which workgroup or block owns which cells, so the partial
 // sums of the dot products are grouped differently: cg_persist, cg_persist_r, cg_persist_half, cg_persist_nq, cg_xcd_local, cg_pad, cg_tiny,
 // cg_rpw, cg_maxblocks (tests/test_gpu_cg_dispatch.py holds both groups to their word).  Stores and loads are atomic; a call works on a
 // snapshot (OptScope).
@@ -28,7 +28,7 @@ enum Opt {
   OPT_CG_XCD_LOCAL,        // 0: never run a small grid's persistent solve on the workgroups of ONE XCD (default: on)
   OPT_CG_TINY,             // 0: never solve a tiny grid (<= 4 608 cells) inside one workgroup (cg_tiny.h; default: on)
   OPT_CG_XCD_MAP,          // 1 (tests): keep the XCD of every workgroup of a solve's last chip-wide persistent launch for piso_cg_last_xcd_map
-  OPT_CONV_LDS,            // 0: the closure's forward / input-gradient convolutions read their operands straight from L2 (default: staged through LDS)
+  OPT_CONV_LDS,            // 0: the closure's convolutions - forward / input gradient (CINP >= 16, KS >= 3) AND weight gradient (cin, cout multiples of 4; the 64 -> 64 kernel) - read their operands straight from L2 (default: staged through LDS)
   OPT_BICG_FOLD,           // 0: the BiCGStab scalar stages always run as launches of their own (default: folded into their consumers on one GPU)
   OPT_BICG_SWEEP_LDS,      // 0: the triangular sweeps address memory in scan order (bi_sweep) instead of staging rows through LDS (bi_sweep_lds)
   OPT_BICG_FUSE_P,         // 0: the direction update of BiCGStab runs as a launch of its own (bi_update_p) instead of inside the forward sweep that reads it

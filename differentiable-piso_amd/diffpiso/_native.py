@@ -38,6 +38,8 @@ lib.piso_cg_last_dispatch.argtypes = [_ip, _i]
 lib.piso_cg_last_dispatch.restype = _i
 lib.piso_bicgstab_last_dispatch.argtypes = [_ip, _i]
 lib.piso_bicgstab_last_dispatch.restype = _i
+lib.piso_conv_last_dispatch.argtypes = [_ip, _i]
+lib.piso_conv_last_dispatch.restype = _i
 lib.piso_cg_verify_stats.argtypes = [C.POINTER(C.c_longlong), _ip]
 lib.piso_cg_verify_stats.restype = None
 lib.piso_csr_nnz.argtypes = [_i, _i, _i, _i, _ip, _ip]
@@ -250,3 +252,17 @@ def bicgstab_last_dispatch():
     if n != 0 and n != len(BICGSTAB_DISPATCH_FIELDS):
         raise PisoNativeError("piso_bicgstab_last_dispatch returned %d fields, this binding knows %d" % (n, len(BICGSTAB_DISPATCH_FIELDS)))
     return {k: buf[i] for i, k in enumerate(BICGSTAB_DISPATCH_FIELDS[:n])}
+
+
+CONV_DISPATCH_FIELDS = ("entry", "KS", "C", "NT", "IPW", "family", "leaky", "grid_x", "grid_y", "block", "rows_per_block", "nblocks", "reducer",
+                        "Ho", "Wo")
+
+
+def conv_last_dispatch():
+    """Which kernel instance this thread's last piso_conv2d_forward / piso_conv2d_wgrad ran (include/piso_hip.h: piso_conv_last_dispatch),
+    as a dict; {} if the thread has not run a convolution."""
+    buf = (C.c_int * 32)()
+    n = lib.piso_conv_last_dispatch(buf, 32)
+    if n != 0 and n != len(CONV_DISPATCH_FIELDS):
+        raise PisoNativeError("piso_conv_last_dispatch returned %d fields, this binding knows %d" % (n, len(CONV_DISPATCH_FIELDS)))
+    return {k: buf[i] for i, k in enumerate(CONV_DISPATCH_FIELDS[:n])}

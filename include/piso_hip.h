@@ -333,6 +333,9 @@ void piso_cg_verify_stats(long long* runs_out, int* failures_out);
  * Input gradient = piso_conv2d_forward(grad of the pre-activation output, flipped + transposed weights, pad = ks - 1 - pad).
  * piso_conv2d_wgrad: dw [ks][ks][cin][cout] (HWIO, true sizes) = sum over pixels of in (x) grad_out (pre-activation);
  * deterministic two-stage reduction through the caller's workspace.
+ * Alignment (checked, PISO_ERR_INVALID_ARG): forward with cin > 4: `in` and `w_laid_out` 16-byte aligned;  wgrad with cout % 4 == 0:
+ * `dw` and `workspace`, with cin % 4 == 0 as well: `in` and `grad_out` too (the kernels use 16-byte accesses there).
+ * Non-finite values stay where the definition puts them: an output (a weight gradient) is NaN exactly if a term of ITS sum is.
  * ------------------------------------------------------------------------------------------------------------- */
 size_t piso_conv2d_weight_elems(int ks, int cin, int cout);
 size_t piso_conv2d_wgrad_workspace_bytes(int ks, int cin, int cout);
@@ -342,6 +345,28 @@ int piso_conv2d_wgrad(const float* in, const float* grad_out, float* dw, int H, 
                       void* workspace, size_t workspace_bytes, piso_stream_t stream);
 /* grad_pre = grad_out * leaky_relu'(pre-activation) (slope 0.2), from the layer's saved output (same sign as the pre-activation). */
 int piso_leaky_relu_backward(const float* grad_out, const float* out, float* grad_pre, size_t n, piso_stream_t stream);
+/* Which kernel instance the calling thread's last piso_conv2d_forward / piso_conv2d_wgrad ran: out[0 .. min(return value, capacity));
+ * returns the number of fields (0: this thread has not run a convolution).  Read-only: the record is written on the host after the
+ * launches of a call succeeded and changes nothing that is computed; a refused call (PISO_ERR_INVALID_ARG) leaves it as it was.
+ * Fields, in this order:
+ *    0 entry           1 piso_conv2d_forward, 2 piso_conv2d_wgrad
+ *    1 KS              kernel size of the instance
+ *    2 C               forward: CINP, the input channels of the instance (4 for cin <= 4, else cin);  wgrad: MTI, tiles of 16 input channels
+ *    3 NT              tiles of 16 output channels
+ *    4 IPW             wgrad: work items (tap, tile of input channels) per wave (the 64 -> 64 kernels: 1, one tap);  forward: 0
+ *    5 family          forward: 0 conv_forward_kernel (operands from L2), 1 conv_forward_lds_kernel;  wgrad: 2 conv_wgrad_kernel, 3
+ *                      conv_wgrad_lds_kernel (cin % 4 == 0 and cout % 4 == 0), 4 conv_wgrad_kernel PACK4 (7 x 7, cin <= 4, cout <= 16), 5
+ *                      conv_wgrad64_kernel (3 x 3, 64 -> 64), 6 conv_wgrad64_lds_kernel.  Option conv_lds 0: never 1, 3 or 6
+ *    6 leaky           forward: 1 the instance applies the leaky ReLU;  wgrad: 0
+ *    7 grid_x          forward: workgroups of four 64-pixel tiles, ceil(ceil(Wo / 64) Ho / 4);  wgrad: nblocks
+ *    8 grid_y          wgrad: groups of waves over the work items (the 64 -> 64 kernels: 3, one per tap row);  forward: 1
+ *    9 block           threads per workgroup: 256 (the 64 -> 64 wgrad kernels: 192)
+ *   10 rows_per_block  wgrad: output rows per row band, ceil(Ho / 256);  forward: 0
+ *   11 nblocks         wgrad: row bands = partial sums per weight, ceil(Ho / rows_per_block) <= 256;  forward: 0
+ *   12 reducer         wgrad: 4 conv_wgrad_reduce4_kernel (cout % 4 == 0), 1 conv_wgrad_reduce_kernel;  forward: 0
+ *   13 Ho              output rows (wgrad: rows of grad_out)
+ *   14 Wo              output columns */
+int piso_conv_last_dispatch(int* out, int capacity);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Slab-decomposed pressure CG (no counterpart in the reference, which is single-GPU).
