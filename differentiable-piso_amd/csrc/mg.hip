@@ -1,0 +1,696 @@
+// Multigrid-preconditioned CG for the pressure system (fp64): an OPT-IN second pressure solver next to the plain CG of cg.hip.
+// The reference has no such solver; it solves the same system, (L + c 1 1^T) x = b, to the same stopping rule (max|r| < accuracy on
+// the recurred residual) in tens of iterations where plain CG needs thousands.  tests/mg_reference.py is the numpy twin.
+//
+// Matrix.  L [N][5] = (-y, -x, diag, +x, +y), diagonal <= 0, symmetric, periodic wrap per axis.  A cell with a ZERO diagonal is ABSENT
+// (solid cells, padding): x = 0 there, it joins no aggregate, couplings into it are dropped.  A non-zero border entry in a
+// non-periodic direction (which makes the reference stencil read the neighbouring row) is refused, and so is a zero-diagonal row that
+// still has entries, and rank_deficient = 1 on a matrix whose rows do not sum to zero: PISO_ERR_UNSUPPORTED_PATTERN, never another system.
+//
+// Hierarchy.  2 x 2 aggregation (ceil), piecewise-constant P, A_c = kGalerkin P^T A P built on the device level by level, every level
+// in the same five-array layout (couplings across an aggregate face are summed into the coarse off-diagonal, couplings inside go to the
+// diagonal, from both sides).  Coarsening stops before a dimension would fall below kMinDim.
+//
+// Cycle.  V(nu, nu), damped Jacobi (kOmega) from a zero guess; the coarsest level gets kCoarsestSweeps sweeps.  A fixed, symmetric
+// linear operator M^-1 ~ L^-1 (negative definite on the present cells), so plain PCG and "the adjoint is the same solve" hold.
+// Passes over a level per cycle at nu = 2: [sweep 1 + sweep 2] (the first sweep from zero is pointwise, so both come out of one
+// stencil pass over r), [residual + restriction], [prolongation + correction + post-sweep 1], [post-sweep 2].  All levels of at most
+// kTailCells cells run inside ONE workgroup (mg_tail: vectors in LDS, coefficients from L2) - without it a cycle on a small grid is
+// dozens of launches of nothing.  The per-level kernels and the tail call the same per-cell code: their results are identical.
+//
+// Constant mode.  On a rank-deficient system L 1_present = 0 (checked), so the rank-one term c 1 1^T couples nothing but the means:
+// with x = y + mu 1, b = b' + mean(b) 1 the system splits into L y = b' and c N mu = mean(b).  The solver therefore projects the mean
+// out of b once, runs PCG on L alone (q = L p and (p, q) do not see a constant in p, and r stays mean-free because the columns of L sum
+// to zero), and at the end replaces the mean of x over the present cells by sum(b) / (c n_present^2) - mean(b) / (c N) without absent
+// cells.  With solid cells the shifted system is singular along one direction and plain CG from x0 = 0 converges to the member with
+// x = 0 on the solid cells and that same mean: the same x.
+//
+// Reductions are two-stage, fixed order (per-block partials, re-added in index order): a solve is reproducible bit for bit.  alpha,
+// beta and the sums stay on the device; the host queues check_every iterations, then reads the state through a pinned word; kernels of
+// iterations queued after convergence see the device flag and return at once, so neither x nor the count depends on the cadence.
+#include "piso_common.h"
+#include "options.h"
+
+namespace piso {
+
+constexpr double kGalerkin = 0.5;      // constant transfers under-correct by ~2 on cell-centred grids (measured counts)
+constexpr double kOmega = 0.8;         // Jacobi damping
+constexpr int kMinDim = 4;             // no level has fewer cells than this in a dimension
+constexpr int kCoarsestSweeps = 16;    // the coarsest level is "solved" by a FIXED number of sweeps
+constexpr double kGuard = 1e-10;       // a coarse diagonal this small against its aggregate's diagonals is round-off: the coarse cell is absent
+constexpr int kTailCells = 4096;       // levels of at most this many cells run inside one workgroup
+constexpr int kTailLds = 6144;         // cells of all tail levels together (r and z of every tail level live in LDS)
+constexpr int kTailThreads = 1024;
+constexpr int kTailMaxLevels = 8;
+constexpr int kMgMaxLevels = 16;
+constexpr int kMgGrid = 1024;          // grid cap of every kernel that publishes partials (4 workgroups per CU)
+constexpr int kCheckEvery = 4;         // iterations queued between two host looks
+constexpr double kRowSumTol = 1e-9;    // rank_deficient = 1: max|row sum| must stay below this times mean|diag|
+
+struct MgState { int done, iterations, flags, pad; };
+enum { MG_FLAG_BORDER = 1, MG_FLAG_ZERO_DIAG_ROW = 2, MG_FLAG_NOT_SINGULAR = 4 };
+enum { SC_RZ0 = 0, SC_RZ1, SC_SUM_DIAG, SC_NPRESENT, SC_MEAN_B, SC_COUNT_MG = 8 };
+
+struct Lv {
+  int nx, ny, n, per_x, per_y;
+  double* c[5];        // S, W, C, E, N
+  double* dinv;        // kOmega / diag, 0 on absent cells
+};
+
+struct Walk { int begin, step; };
+__device__ __forceinline__ Walk grid_walk() { return Walk{(int)(blockIdx.x * blockDim.x + threadIdx.x), (int)(gridDim.x * blockDim.x)}; }
+__device__ __forceinline__ Walk block_walk() { return Walk{(int)threadIdx.x, (int)blockDim.x}; }
+
+struct Nb { int s, w, e, n; };
+// neighbours with wrap; where the axis is not periodic the coefficient of a wrapped neighbour is zero (checked at level 0, inherited below)
+__device__ __forceinline__ Nb neighbours(int c, int i, int j, int nx, int ny) {
+  Nb q;
+  q.s = j > 0 ? c - nx : c + (ny - 1) * nx;
+  q.w = i > 0 ? c - 1 : c + (nx - 1);
+  q.e = i < nx - 1 ? c + 1 : c - (nx - 1);
+  q.n = j < ny - 1 ? c + nx : c - (ny - 1) * nx;
+  return q;
+}
+// summation order of the reference stencil: S, W, C, E, N
+__device__ __forceinline__ double stencil(const Lv& L, int c, double vs, double vw, double vc, double ve, double vn) {
+  double t = L.c[0][c] * vs;
+  t += L.c[1][c] * vw;
+  t += L.c[2][c] * vc;
+  t += L.c[3][c] * ve;
+  t += L.c[4][c] * vn;
+  return t;
+}
+
+// ---- the per-cell passes, shared by the per-level kernels (grid_walk) and the one-workgroup tail (block_walk) -------------------------
+// first sweep from a zero guess
+__device__ __forceinline__ void ph_pre1(const Lv& L, const double* r, double* z, Walk w) {
+  for (int c = w.begin; c < L.n; c += w.step) z[c] = L.dinv[c] * r[c];
+}
+// sweeps 1 and 2 from a zero guess in one stencil pass: z1 = dinv r is pointwise, z2 = z1 + dinv (r - A z1)
+__device__ __forceinline__ void ph_pre2(const Lv& L, const double* r, double* z, Walk w) {
+  for (int c = w.begin; c < L.n; c += w.step) {
+    const int j = c / L.nx, i = c - j * L.nx;
+    const Nb q = neighbours(c, i, j, L.nx, L.ny);
+    const double di = L.dinv[c], rc = r[c], z1 = di * rc;
+    const double az = stencil(L, c, L.dinv[q.s] * r[q.s], L.dinv[q.w] * r[q.w], z1, L.dinv[q.e] * r[q.e], L.dinv[q.n] * r[q.n]);
+    z[c] = z1 + di * (rc - az);
+  }
+}
+// one sweep zout = z' + dinv (r - A z'), z' = zin (+ P e on the present cells where e is given); returns the thread's part of (r, zout)
+__device__ __forceinline__ double ph_jac(const Lv& L, const double* r, const double* zin, double* zout, const double* e, int nxc, Walk w) {
+  double acc = 0;
+  for (int c = w.begin; c < L.n; c += w.step) {
+    const int j = c / L.nx, i = c - j * L.nx;
+    const Nb q = neighbours(c, i, j, L.nx, L.ny);
+    const double di = L.dinv[c], rc = r[c];
+    double vs = zin[q.s], vw = zin[q.w], vc = zin[c], ve = zin[q.e], vn = zin[q.n];
+    if (e) {
+      const int iw = i > 0 ? i - 1 : L.nx - 1, ie = i < L.nx - 1 ? i + 1 : 0;
+      const int js = j > 0 ? j - 1 : L.ny - 1, jn = j < L.ny - 1 ? j + 1 : 0;
+      const int row = (j >> 1) * nxc, col = i >> 1;
+      if (L.dinv[q.s] != 0) vs += e[(js >> 1) * nxc + col];
+      if (L.dinv[q.w] != 0) vw += e[row + (iw >> 1)];
+      if (di != 0) vc += e[row + col];
+      if (L.dinv[q.e] != 0) ve += e[row + (ie >> 1)];
+      if (L.dinv[q.n] != 0) vn += e[(jn >> 1) * nxc + col];
+    }
+    const double zo = di != 0 ? vc + di * (rc - stencil(L, c, vs, vw, vc, ve, vn)) : 0.0;
+    zout[c] = zo;
+    acc += rc * zo;
+  }
+  return acc;
+}
+// residual of the present cells, summed over each 2 x 2 aggregate: rc = P^T (r - A z)
+__device__ __forceinline__ void ph_restrict(const Lv& L, const double* r, const double* z, double* rc, int nxc, int nyc, Walk w) {
+  for (int k = w.begin; k < nxc * nyc; k += w.step) {
+    const int J = k / nxc, I = k - J * nxc;
+    double s = 0;
+    for (int dj = 0; dj < 2; ++dj)
+      for (int di = 0; di < 2; ++di) {
+        const int i = 2 * I + di, j = 2 * J + dj;
+        if (i >= L.nx || j >= L.ny) continue;
+        const int c = j * L.nx + i;
+        if (L.dinv[c] == 0) continue;
+        const Nb q = neighbours(c, i, j, L.nx, L.ny);
+        s += r[c] - stencil(L, c, z[q.s], z[q.w], z[c], z[q.e], z[q.n]);
+      }
+    rc[k] = s;
+  }
+}
+
+// sum over a block of any size up to 1024 threads, the same bits in every thread (lanes by butterfly, then the waves in order)
+__device__ __forceinline__ double mg_block_sum(double v, double* smem /* [16] */) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+  v = wave_sum(v);
+  __syncthreads();
+  if (lane == 0) smem[wave] = v;
+  __syncthreads();
+  double s = 0;
+  for (int q = 0; q < nw; ++q) s += smem[q];
+  return s;
+}
+__device__ __forceinline__ double mg_block_max_nan(double v, double* smem /* [16] */) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+  v = wave_max_nan(v);
+  __syncthreads();
+  if (lane == 0) smem[wave] = v;
+  __syncthreads();
+  double s = smem[0];
+  for (int q = 1; q < nw; ++q) s = nanmax(s, smem[q]);
+  return s;
+}
+// fixed-order sum of `count` partials written by the previous kernel; every block does it redundantly (L2-served)
+__device__ __forceinline__ double mg_sum_partials(const double* part, int count, double* smem) {
+  double s = 0;
+  for (int b = threadIdx.x; b < count; b += blockDim.x) s += part[b];
+  return mg_block_sum(s, smem);
+}
+
+// ---- hierarchy ------------------------------------------------------------------------------------------------------------------------
+// level 0: [N][5] -> five arrays + dinv; couplings into absent cells dropped; pattern checks; partials of sum|diag| (ALL rows, as the
+// reference's shift has it), the number of present cells, sum of b over them, max|row sum|
+__global__ __launch_bounds__(kBlock) void mg_setup0(const double* __restrict__ Lin, Lv L, const double* __restrict__ b, double* parts, MgState* st) {
+  __shared__ double smem[16];
+  double sd = 0, np = 0, sb = 0, mr = 0;
+  int flags = 0;
+  const Walk w = grid_walk();
+  for (int c = w.begin; c < L.n; c += w.step) {
+    const int j = c / L.nx, i = c - j * L.nx;
+    const Nb q = neighbours(c, i, j, L.nx, L.ny);
+    double v[5];
+#pragma unroll
+    for (int s = 0; s < 5; ++s) v[s] = Lin[(size_t)c * 5 + s];
+    const bool present = v[2] != 0;
+    // (a NaN there is no pattern: it flows into the solve and comes back as NaN)
+    if ((!L.per_y && ((j == 0 && v[0] != 0 && v[0] == v[0]) || (j == L.ny - 1 && v[4] != 0 && v[4] == v[4]))) ||
+        (!L.per_x && ((i == 0 && v[1] != 0 && v[1] == v[1]) || (i == L.nx - 1 && v[3] != 0 && v[3] == v[3]))))
+      flags |= MG_FLAG_BORDER;
+    if (!present && (v[0] != 0 || v[1] != 0 || v[3] != 0 || v[4] != 0)) flags |= MG_FLAG_ZERO_DIAG_ROW;
+    const int nb[5] = {q.s, q.w, c, q.e, q.n};
+#pragma unroll
+    for (int s = 0; s < 5; ++s)
+      if (s != 2 && (!present || Lin[(size_t)nb[s] * 5 + 2] == 0)) v[s] = 0;
+#pragma unroll
+    for (int s = 0; s < 5; ++s) L.c[s][c] = v[s];
+    L.dinv[c] = present ? kOmega / v[2] : 0.0;
+    sd += fabs(v[2]);
+    if (present) {
+      np += 1.0;
+      if (b) sb += b[c];
+      mr = nanmax(mr, fabs((((v[0] + v[1]) + v[2]) + v[3]) + v[4]));
+    }
+  }
+  sd = mg_block_sum(sd, smem); np = mg_block_sum(np, smem); sb = mg_block_sum(sb, smem); mr = mg_block_max_nan(mr, smem);
+  if (threadIdx.x == 0) {
+    parts[blockIdx.x] = sd; parts[kMgGrid + blockIdx.x] = np; parts[2 * kMgGrid + blockIdx.x] = sb; parts[3 * kMgGrid + blockIdx.x] = mr;
+  }
+  if (flags) atomicOr(&st->flags, flags);
+}
+__global__ __launch_bounds__(kBlock) void mg_setup_fin(const double* parts, int count, double* scal, int rank_deficient, int ncells, MgState* st) {
+  __shared__ double smem[16];
+  const double sd = mg_sum_partials(parts, count, smem), np = mg_sum_partials(parts + kMgGrid, count, smem);
+  const double sb = mg_sum_partials(parts + 2 * kMgGrid, count, smem);
+  double mr = 0;
+  for (int b = threadIdx.x; b < count; b += blockDim.x) mr = nanmax(mr, parts[3 * kMgGrid + b]);
+  mr = mg_block_max_nan(mr, smem);
+  if (threadIdx.x == 0) {
+    scal[SC_SUM_DIAG] = sd; scal[SC_NPRESENT] = np;
+    scal[SC_MEAN_B] = (rank_deficient && np > 0) ? sb / np : 0.0;
+    scal[SC_RZ0] = 0; scal[SC_RZ1] = 0;
+    if (rank_deficient && np > 0 && mr > kRowSumTol * (sd / np)) atomicOr(&st->flags, MG_FLAG_NOT_SINGULAR);
+    (void)ncells;
+  }
+}
+// A_c = kGalerkin P^T A P, one coarse cell per thread
+__global__ __launch_bounds__(kBlock) void mg_coarsen(Lv F, Lv Cc) {
+  const Walk w = grid_walk();
+  for (int k = w.begin; k < Cc.n; k += w.step) {
+    const int J = k / Cc.nx, I = k - J * Cc.nx;
+    double dg = 0, oS = 0, oW = 0, oE = 0, oN = 0, scale = 0;
+    for (int dj = 0; dj < 2; ++dj)
+      for (int di = 0; di < 2; ++di) {
+        const int i = 2 * I + di, j = 2 * J + dj;
+        if (i >= F.nx || j >= F.ny) continue;
+        const int c = j * F.nx + i;
+        const double cc = F.c[2][c];
+        if (cc == 0) continue;
+        const Nb q = neighbours(c, i, j, F.nx, F.ny);
+        scale += fabs(cc);
+        dg += cc;
+        const double s = F.c[2][q.s] != 0 ? F.c[0][c] : 0.0, ww = F.c[2][q.w] != 0 ? F.c[1][c] : 0.0;
+        const double e = F.c[2][q.e] != 0 ? F.c[3][c] : 0.0, n = F.c[2][q.n] != 0 ? F.c[4][c] : 0.0;
+        if (dj == 1) dg += s; else oS += s;
+        if (di == 1) dg += ww; else oW += ww;
+        if (di == 0 && i + 1 < F.nx) dg += e; else oE += e;
+        if (dj == 0 && j + 1 < F.ny) dg += n; else oN += n;
+      }
+    dg *= kGalerkin; oS *= kGalerkin; oW *= kGalerkin; oE *= kGalerkin; oN *= kGalerkin;
+    if (!(fabs(dg) > kGuard * kGalerkin * scale)) dg = oS = oW = oE = oN = 0;
+    Cc.c[0][k] = oS; Cc.c[1][k] = oW; Cc.c[2][k] = dg; Cc.c[3][k] = oE; Cc.c[4][k] = oN;
+    Cc.dinv[k] = dg != 0 ? kOmega / dg : 0.0;
+  }
+}
+__global__ __launch_bounds__(kBlock) void mg_export(Lv L, double* __restrict__ out) {
+  const Walk w = grid_walk();
+  for (int c = w.begin; c < L.n; c += w.step)
+    for (int s = 0; s < 5; ++s) out[(size_t)c * 5 + s] = L.c[s][c];
+}
+
+// ---- per-level cycle kernels -----------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void mg_pre1(Lv L, const double* r, double* z, const MgState* st) {
+  if (st->done) return;
+  ph_pre1(L, r, z, grid_walk());
+}
+__global__ __launch_bounds__(kBlock) void mg_pre2(Lv L, const double* r, double* z, const MgState* st) {
+  if (st->done) return;
+  ph_pre2(L, r, z, grid_walk());
+}
+__global__ __launch_bounds__(kBlock) void mg_jacobi(Lv L, const double* r, const double* zin, double* zout, const double* e, int nxc, double* part_rz,
+                                                    const MgState* st) {
+  if (st->done) return;
+  __shared__ double smem[16];
+  double acc = ph_jac(L, r, zin, zout, e, nxc, grid_walk());
+  if (part_rz) {
+    acc = mg_block_sum(acc, smem);
+    if (threadIdx.x == 0) part_rz[blockIdx.x] = acc;
+  }
+}
+__global__ __launch_bounds__(kBlock) void mg_restrict(Lv L, const double* r, const double* z, double* rc, int nxc, int nyc, const MgState* st) {
+  if (st->done) return;
+  ph_restrict(L, r, z, rc, nxc, nyc, grid_walk());
+}
+
+// ---- the coarse tail: levels [0, nlev) of `T` inside one workgroup ----------------------------------------------------------------------
+struct MgTail {
+  int nlev;
+  Lv lv[kTailMaxLevels];
+  int off[kTailMaxLevels];
+};
+// nu sweeps from a zero guess into `dst` (scratch `tmp`)
+__device__ __forceinline__ void tail_first_sweeps(const Lv& L, const double* r, double* dst, double* tmp, int nu, Walk w) {
+  const int rest = nu >= 2 ? nu - 2 : 0;
+  double* cur = (rest & 1) ? tmp : dst;
+  if (nu >= 2) ph_pre2(L, r, cur, w); else ph_pre1(L, r, cur, w);
+  __syncthreads();
+  for (int s = 0; s < rest; ++s) {
+    double* nxt = cur == dst ? tmp : dst;
+    ph_jac(L, r, cur, nxt, nullptr, 0, w);
+    __syncthreads();
+    cur = nxt;
+  }
+}
+__global__ __launch_bounds__(kTailThreads) void mg_tail(MgTail T, const double* r_in, double* z_out, double* part_rz, int nu, const MgState* st) {
+  if (st->done) return;
+  __shared__ double rbuf[kTailLds], zbuf[kTailLds], tbuf[kTailCells];
+  __shared__ double smem[16];
+  const Walk w = block_walk();
+  for (int c = w.begin; c < T.lv[0].n; c += w.step) rbuf[c] = r_in[c];
+  __syncthreads();
+  const int last = T.nlev - 1;
+  for (int l = 0; l < last; ++l) {                                      // down
+    const Lv& L = T.lv[l];
+    tail_first_sweeps(L, rbuf + T.off[l], zbuf + T.off[l], tbuf, nu, w);
+    ph_restrict(L, rbuf + T.off[l], zbuf + T.off[l], rbuf + T.off[l + 1], T.lv[l + 1].nx, T.lv[l + 1].ny, w);
+    __syncthreads();
+  }
+  tail_first_sweeps(T.lv[last], rbuf + T.off[last], zbuf + T.off[last], tbuf, kCoarsestSweeps, w);
+  double acc = 0;
+  for (int l = last - 1; l >= 0; --l) {                                  // up
+    const Lv& L = T.lv[l];
+    double *cur = zbuf + T.off[l], *nxt = tbuf;
+    for (int s = 0; s < nu; ++s) {
+      acc = ph_jac(L, rbuf + T.off[l], cur, nxt, s == 0 ? zbuf + T.off[l + 1] : nullptr, T.lv[l + 1].nx, w);
+      __syncthreads();
+      double* t = cur; cur = nxt; nxt = t;
+    }
+    if (cur != zbuf + T.off[l]) {                                       // odd nu: the result sits in the scratch the next level needs
+      for (int c = w.begin; c < L.n; c += w.step) zbuf[T.off[l] + c] = tbuf[c];
+      __syncthreads();
+    }
+  }
+  if (last == 0) {                                                       // (a one-level tail: the sum was never formed)
+    acc = 0;
+    for (int c = w.begin; c < T.lv[0].n; c += w.step) acc += rbuf[c] * zbuf[c];
+  }
+  for (int c = w.begin; c < T.lv[0].n; c += w.step) z_out[c] = zbuf[c];
+  if (part_rz) {
+    acc = mg_block_sum(acc, smem);
+    if (threadIdx.x == 0) part_rz[0] = acc;
+  }
+}
+
+// ---- outer iteration ------------------------------------------------------------------------------------------------------------------
+// r = b' on the present cells (b' = b - mean over the present cells where rank deficient), 0 elsewhere; x = 0
+__global__ __launch_bounds__(kBlock) void mg_init(Lv L, const double* __restrict__ b, double* __restrict__ x, double* __restrict__ r, const double* scal) {
+  const double mean = scal[SC_MEAN_B];
+  const Walk w = grid_walk();
+  for (int c = w.begin; c < L.n; c += w.step) {
+    x[c] = 0;
+    r[c] = L.dinv[c] != 0 ? b[c] - mean : 0.0;
+  }
+}
+// the true residual r = b' - L x
+__global__ __launch_bounds__(kBlock) void mg_residual(Lv L, const double* __restrict__ b, const double* __restrict__ x, double* __restrict__ r, const double* scal,
+                                                      const MgState* st) {
+  if (st->done) return;
+  const double mean = scal[SC_MEAN_B];
+  const Walk w = grid_walk();
+  for (int c = w.begin; c < L.n; c += w.step) {
+    const int j = c / L.nx, i = c - j * L.nx;
+    const Nb q = neighbours(c, i, j, L.nx, L.ny);
+    r[c] = L.dinv[c] != 0 ? (b[c] - mean) - stencil(L, c, x[q.s], x[q.w], x[c], x[q.e], x[q.n]) : 0.0;
+  }
+}
+// p' = z + beta p, q = L p', partials of (p', q); block 0 publishes (r, z) for the update kernel and the next beta
+__global__ __launch_bounds__(kBlock) void mg_direction(Lv L, const double* z, const double* pold, double* pnew, double* q, const double* part_rz, int n_rz,
+                                                       double* scal, int k, int restart, double* part_pq, const MgState* st) {
+  if (st->done) return;
+  __shared__ double smem[16];
+  const double rz = mg_sum_partials(part_rz, n_rz, smem);
+  const double rz_old = scal[SC_RZ0 + ((k + 1) & 1)];
+  const double beta = (restart || rz_old == 0) ? 0.0 : rz / rz_old;
+  if (blockIdx.x == 0 && threadIdx.x == 0) scal[SC_RZ0 + (k & 1)] = rz;
+  double acc = 0;
+  const Walk w = grid_walk();
+  for (int c = w.begin; c < L.n; c += w.step) {
+    const int j = c / L.nx, i = c - j * L.nx;
+    const Nb nb = neighbours(c, i, j, L.nx, L.ny);
+    double ps, pw, pc, pe, pn;
+    if (restart) { ps = z[nb.s]; pw = z[nb.w]; pc = z[c]; pe = z[nb.e]; pn = z[nb.n]; }     // (beta = 0 must not touch an unset p)
+    else {
+      ps = z[nb.s] + beta * pold[nb.s]; pw = z[nb.w] + beta * pold[nb.w]; pc = z[c] + beta * pold[c];
+      pe = z[nb.e] + beta * pold[nb.e]; pn = z[nb.n] + beta * pold[nb.n];
+    }
+    const double qc = stencil(L, c, ps, pw, pc, pe, pn);
+    pnew[c] = pc; q[c] = qc;
+    acc += pc * qc;
+  }
+  acc = mg_block_sum(acc, smem);
+  if (threadIdx.x == 0) part_pq[blockIdx.x] = acc;
+}
+// x += alpha p, r -= alpha q, partials of max|r|
+__global__ __launch_bounds__(kBlock) void mg_update(int n, double* __restrict__ x, double* __restrict__ r, const double* __restrict__ p, const double* __restrict__ q,
+                                                    const double* scal, int k, const double* part_pq, int n_pq, double* part_max, const MgState* st) {
+  if (st->done) return;
+  __shared__ double smem[16];
+  const double pq = mg_sum_partials(part_pq, n_pq, smem);
+  const double rz = scal[SC_RZ0 + (k & 1)];
+  const double alpha = pq != 0 ? rz / pq : 0.0;                          // (guarded like the reference's alpha)
+  double m = 0;
+  const Walk w = grid_walk();
+  for (int c = w.begin; c < n; c += w.step) {
+    x[c] += alpha * p[c];
+    const double rc = r[c] - alpha * q[c];
+    r[c] = rc;
+    m = nanmax(m, fabs(rc));
+  }
+  m = mg_block_max_nan(m, smem);
+  if (threadIdx.x == 0) part_max[blockIdx.x] = m;
+}
+__global__ __launch_bounds__(kBlock) void mg_check(const double* part_max, int count, float accuracy, int iterations, MgState* st) {
+  if (st->done) return;
+  __shared__ double smem[16];
+  double m = 0;
+  for (int b = threadIdx.x; b < count; b += blockDim.x) m = nanmax(m, part_max[b]);
+  m = mg_block_max_nan(m, smem);
+  if (threadIdx.x == 0 && m < (double)accuracy) { st->iterations = iterations; st->done = 1; }    // (false for NaN)
+}
+__global__ __launch_bounds__(kBlock) void mg_sum_x(Lv L, const double* __restrict__ x, double* part) {
+  __shared__ double smem[16];
+  double s = 0;
+  const Walk w = grid_walk();
+  for (int c = w.begin; c < L.n; c += w.step) s += L.dinv[c] != 0 ? x[c] : 0.0;
+  s = mg_block_sum(s, smem);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+// the constant mode of the shifted system: mean of x over the present cells := sum(b) / (c n_present^2), c = 0.1 sum|diag| / N
+__global__ __launch_bounds__(kBlock) void mg_finish(Lv L, double* __restrict__ x, const double* part, int count, const double* scal) {
+  __shared__ double smem[16];
+  const double sx = mg_sum_partials(part, count, smem);
+  const double np = scal[SC_NPRESENT], cshift = 0.1 * scal[SC_SUM_DIAG] / (double)L.n;
+  const double add = (np > 0 && cshift != 0) ? scal[SC_MEAN_B] / (cshift * np) - sx / np : 0.0;
+  const Walk w = grid_walk();
+  for (int c = w.begin; c < L.n; c += w.step) x[c] = L.dinv[c] != 0 ? x[c] + add : 0.0;
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------------
+struct MgPlan {
+  int nlev = 0, tail_first = -1;          // tail_first: first level of the one-workgroup tail (-1: none fits)
+  Lv lv[kMgMaxLevels];
+  double *r[kMgMaxLevels], *z[kMgMaxLevels], *t[kMgMaxLevels];
+  double *p[2], *q, *parts, *part_rz, *part_pq, *part_max, *scal;
+  MgState* st;
+};
+static int mg_grid(int n) { return grid_for(n, kBlock, kMgGrid); }
+
+// carves the workspace (the same walk sizes it: piso_mg_workspace_bytes)
+static bool mg_plan(int nx, int ny, int per_x, int per_y, Arena& ar, MgPlan& P) {
+  int l = 0;
+  for (;; ++l) {
+    Lv& L = P.lv[l];
+    L.nx = nx; L.ny = ny; L.n = nx * ny; L.per_x = per_x; L.per_y = per_y;
+    for (int s = 0; s < 5; ++s) L.c[s] = ar.take<double>(L.n);
+    L.dinv = ar.take<double>(L.n);
+    P.r[l] = ar.take<double>(L.n); P.z[l] = ar.take<double>(L.n); P.t[l] = ar.take<double>(L.n);
+    const int nxc = (nx + 1) / 2, nyc = (ny + 1) / 2;
+    if (nxc < kMinDim || nyc < kMinDim || l + 1 == kMgMaxLevels) break;
+    nx = nxc; ny = nyc;
+  }
+  P.nlev = l + 1;
+  P.tail_first = -1;
+  for (int f = 0; f < P.nlev; ++f) {
+    int cells = 0;
+    for (int k = f; k < P.nlev; ++k) cells += P.lv[k].n;
+    if (P.lv[f].n <= kTailCells && cells <= kTailLds && P.nlev - f <= kTailMaxLevels) { P.tail_first = f; break; }
+  }
+  const int n0 = P.lv[0].n;
+  P.p[0] = ar.take<double>(n0); P.p[1] = ar.take<double>(n0); P.q = ar.take<double>(n0);
+  P.parts = ar.take<double>(4 * kMgGrid);
+  P.part_rz = ar.take<double>(kMgGrid); P.part_pq = ar.take<double>(kMgGrid); P.part_max = ar.take<double>(kMgGrid);
+  P.scal = ar.take<double>(SC_COUNT_MG);
+  P.st = ar.take<MgState>(1);
+  return ar.ok();
+}
+static bool mg_dims_ok(int nx, int ny) { return nx >= kMinDim && ny >= kMinDim && (long long)nx * ny <= (1ll << 30); }
+
+// which shape the calling thread's last solve / cycle had (piso_mg_last_dispatch)
+enum { MD_LEVELS = 0, MD_TAIL_FIRST, MD_SWEEPS, MD_ITERATIONS, MD_CYCLES, MD_RESIDUAL_RECOMPUTATIONS, MD_COUNT };
+static thread_local int tl_mg_dispatch[MD_COUNT];
+static thread_local int tl_mg_dispatch_n = 0;
+
+struct MgPoll { MgState* pinned = nullptr; };
+constexpr int kMgPollDevices = 16;
+static thread_local MgPoll tl_mg_poll[kMgPollDevices];
+static int mg_pinned(MgState** out) {
+  int dev = 0;
+  PISO_HIP_CHECK(hipGetDevice(&dev));
+  if (dev < 0 || dev >= kMgPollDevices) { set_error_msg("piso_mg: device ordinal out of range"); return PISO_ERR_INVALID_ARG; }
+  if (!tl_mg_poll[dev].pinned) PISO_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&tl_mg_poll[dev].pinned), sizeof(MgState), hipHostMallocDefault));
+  *out = tl_mg_poll[dev].pinned;
+  return PISO_OK;
+}
+
+// builds every level from the caller's matrix and refuses what the solver does not solve (one host look, as the plain CG's set-up has)
+static int mg_build(const MgPlan& P, const double* laplace, const double* b, int rank_deficient, hipStream_t stream) {
+  MgState* pinned = nullptr;
+  if (int rc = mg_pinned(&pinned)) return rc;
+  PISO_HIP_CHECK(hipMemsetAsync(P.st, 0, sizeof(MgState), stream));
+  const int g0 = mg_grid(P.lv[0].n);
+  mg_setup0<<<g0, kBlock, 0, stream>>>(laplace, P.lv[0], b, P.parts, P.st);
+  mg_setup_fin<<<1, kBlock, 0, stream>>>(P.parts, g0, P.scal, rank_deficient, P.lv[0].n, P.st);
+  for (int l = 0; l + 1 < P.nlev; ++l) mg_coarsen<<<mg_grid(P.lv[l + 1].n), kBlock, 0, stream>>>(P.lv[l], P.lv[l + 1]);
+  PISO_LAUNCH_CHECK();
+  PISO_HIP_CHECK(hipMemcpyAsync(pinned, P.st, sizeof(MgState), hipMemcpyDeviceToHost, stream));
+  PISO_HIP_CHECK(hipStreamSynchronize(stream));
+  if (pinned->flags & MG_FLAG_BORDER) {
+    set_error_msg("piso_mg: non-zero border entry in a non-periodic direction (the reference stencil reads the neighbouring row there); use the plain CG");
+    return PISO_ERR_UNSUPPORTED_PATTERN;
+  }
+  if (pinned->flags & MG_FLAG_ZERO_DIAG_ROW) {
+    set_error_msg("piso_mg: a row with a zero diagonal has non-zero entries; use the plain CG");
+    return PISO_ERR_UNSUPPORTED_PATTERN;
+  }
+  if (pinned->flags & MG_FLAG_NOT_SINGULAR) {
+    set_error_msg("piso_mg: rank_deficient = 1 but the rows of the matrix do not sum to zero; use the plain CG");
+    return PISO_ERR_UNSUPPORTED_PATTERN;
+  }
+  return PISO_OK;
+}
+
+// nu sweeps from a zero guess on level l; returns where the result is
+static double* mg_first_sweeps(const MgPlan& P, int l, const double* r, int nu, hipStream_t stream) {
+  const Lv& L = P.lv[l];
+  const int g = mg_grid(L.n);
+  double* cur = P.z[l];
+  if (nu >= 2) mg_pre2<<<g, kBlock, 0, stream>>>(L, r, cur, P.st); else mg_pre1<<<g, kBlock, 0, stream>>>(L, r, cur, P.st);
+  for (int s = 2; s < nu; ++s) {
+    double* nxt = cur == P.z[l] ? P.t[l] : P.z[l];
+    mg_jacobi<<<g, kBlock, 0, stream>>>(L, r, cur, nxt, nullptr, 0, nullptr, P.st);
+    cur = nxt;
+  }
+  return cur;
+}
+// z = M^-1 r0: returns where z of level 0 is; the last kernel leaves the partials of (r0, z) in P.part_rz (*n_rz of them)
+static double* mg_cycle(const MgPlan& P, const double* r0, int nu, bool use_tail, int* n_rz, hipStream_t stream) {
+  const int end = use_tail ? P.tail_first : P.nlev - 1;      // levels [0, end) have a coarser level and run as kernels of their own
+  double* zc[kMgMaxLevels];
+  for (int l = 0; l < end; ++l) {
+    const double* r = l == 0 ? r0 : P.r[l];
+    zc[l] = mg_first_sweeps(P, l, r, nu, stream);
+    mg_restrict<<<mg_grid(P.lv[l + 1].n), kBlock, 0, stream>>>(P.lv[l], r, zc[l], P.r[l + 1], P.lv[l + 1].nx, P.lv[l + 1].ny, P.st);
+  }
+  const double* rend = end == 0 ? r0 : P.r[end];
+  if (use_tail) {
+    MgTail T;
+    T.nlev = P.nlev - end;
+    int off = 0;
+    for (int k = 0; k < T.nlev; ++k) { T.lv[k] = P.lv[end + k]; T.off[k] = off; off += T.lv[k].n; }
+    mg_tail<<<1, kTailThreads, 0, stream>>>(T, rend, P.z[end], end == 0 ? P.part_rz : nullptr, nu, P.st);
+    zc[end] = P.z[end];
+    *n_rz = 1;
+  } else {
+    double* cur = mg_first_sweeps(P, end, rend, kCoarsestSweeps - 1, stream);
+    double* nxt = cur == P.z[end] ? P.t[end] : P.z[end];
+    const int g = mg_grid(P.lv[end].n);
+    mg_jacobi<<<g, kBlock, 0, stream>>>(P.lv[end], rend, cur, nxt, nullptr, 0, end == 0 ? P.part_rz : nullptr, P.st);
+    zc[end] = nxt;
+    *n_rz = g;
+  }
+  for (int l = end - 1; l >= 0; --l) {
+    const Lv& L = P.lv[l];
+    const double* r = l == 0 ? r0 : P.r[l];
+    const int g = mg_grid(L.n);
+    double* cur = zc[l];
+    for (int s = 0; s < nu; ++s) {
+      double* nxt = cur == P.z[l] ? P.t[l] : P.z[l];
+      mg_jacobi<<<g, kBlock, 0, stream>>>(L, r, cur, nxt, s == 0 ? zc[l + 1] : nullptr, P.lv[l + 1].nx, (l == 0 && s == nu - 1) ? P.part_rz : nullptr, P.st);
+      cur = nxt;
+    }
+    zc[l] = cur;
+    if (l == 0) *n_rz = g;
+  }
+  return zc[0];
+}
+static bool mg_use_tail(const MgPlan& P) { return P.tail_first >= 0 && opt(OPT_MG_TAIL) != 0; }
+
+static int mg_common_args(const char* who, int nx, int ny, const void* a, const void* b, const void* c, const void* ws, int sweeps) {
+  char msg[160];
+  if (!mg_dims_ok(nx, ny)) { snprintf(msg, sizeof(msg), "%s: needs at least %d cells in each dimension", who, kMinDim); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
+  if (!a || !b || !c || !ws) { snprintf(msg, sizeof(msg), "%s: NULL pointer", who); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
+  if (sweeps < 1 || sweeps > 8) { snprintf(msg, sizeof(msg), "%s: sweeps must be 1 .. 8", who); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
+  return PISO_OK;
+}
+
+}  // namespace piso
+
+using namespace piso;
+
+extern "C" {
+
+size_t piso_mg_workspace_bytes(int nx, int ny) {
+  if (!mg_dims_ok(nx, ny)) return 0;
+  Arena ar(reinterpret_cast<void*>(256), ~(size_t)0);
+  MgPlan P;
+  mg_plan(nx, ny, 0, 0, ar, P);
+  return ar.used;
+}
+
+int piso_mg_pcg_solve_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence, double* x_out,
+                          float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps, int* iterations_out,
+                          void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
+  const piso::OptScope knobs;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (int rc = mg_common_args("piso_mg_pcg_solve", nx, ny, laplace, divergence, x_out, workspace, sweeps)) return rc;
+  if (max_iterations < 1 || residual_reset < 1) { set_error_msg("piso_mg_pcg_solve: max_iterations and residual_reset must be positive"); return PISO_ERR_INVALID_ARG; }
+  Arena ar(workspace, workspace_bytes);
+  MgPlan P;
+  if (!mg_plan(nx, ny, periodic_x ? 1 : 0, periodic_y ? 1 : 0, ar, P)) { set_error_msg("piso_mg_pcg_solve: workspace too small"); return PISO_ERR_INVALID_ARG; }
+  if (int rc = mg_build(P, laplace, divergence, rank_deficient ? 1 : 0, stream)) return rc;
+  MgState* pinned = nullptr;
+  if (int rc = mg_pinned(&pinned)) return rc;
+  const Lv& L0 = P.lv[0];
+  const int n = L0.n, g0 = mg_grid(n);
+  const bool use_tail = mg_use_tail(P);
+  const int check_every = opt(OPT_MG_CHECK_EVERY) > 0 ? opt(OPT_MG_CHECK_EVERY) : kCheckEvery;
+  double* r = P.r[0];
+  mg_init<<<g0, kBlock, 0, stream>>>(L0, divergence, x_out, r, P.scal);
+  bool done = false;
+  int iterations = max_iterations;
+  for (int k = 0; k < max_iterations && !done; ++k) {
+    const bool restart = k > 0 && (k + 1) % residual_reset == 0;
+    if (restart) mg_residual<<<g0, kBlock, 0, stream>>>(L0, divergence, x_out, r, P.scal, P.st);
+    int n_rz = 0;
+    const double* z = mg_cycle(P, r, sweeps, use_tail, &n_rz, stream);
+    mg_direction<<<g0, kBlock, 0, stream>>>(L0, z, P.p[k & 1], P.p[(k + 1) & 1], P.q, P.part_rz, n_rz, P.scal, k, (restart || k == 0) ? 1 : 0, P.part_pq, P.st);
+    mg_update<<<g0, kBlock, 0, stream>>>(n, x_out, r, P.p[(k + 1) & 1], P.q, P.scal, k, P.part_pq, g0, P.part_max, P.st);
+    mg_check<<<1, kBlock, 0, stream>>>(P.part_max, g0, accuracy, k + 1, P.st);
+    PISO_LAUNCH_CHECK();
+    if ((k + 1) % check_every == 0 || k + 1 == max_iterations) {
+      PISO_HIP_CHECK(hipMemcpyAsync(pinned, P.st, sizeof(MgState), hipMemcpyDeviceToHost, stream));
+      PISO_HIP_CHECK(hipStreamSynchronize(stream));
+      if (pinned->done) { done = true; iterations = pinned->iterations; }
+    }
+  }
+  if (rank_deficient) {
+    mg_sum_x<<<g0, kBlock, 0, stream>>>(L0, x_out, P.parts);
+    mg_finish<<<g0, kBlock, 0, stream>>>(L0, x_out, P.parts, g0, P.scal);
+    PISO_LAUNCH_CHECK();
+  }
+  PISO_HIP_CHECK(hipStreamSynchronize(stream));
+  if (iterations_out) *iterations_out = iterations;
+  int recomputed = 0;
+  for (int k = 1; k < iterations; ++k) recomputed += (k + 1) % residual_reset == 0;
+  int* d = tl_mg_dispatch;
+  d[MD_LEVELS] = P.nlev; d[MD_TAIL_FIRST] = use_tail ? P.tail_first : -1; d[MD_SWEEPS] = sweeps; d[MD_ITERATIONS] = iterations;
+  d[MD_CYCLES] = iterations; d[MD_RESIDUAL_RECOMPUTATIONS] = recomputed;
+  tl_mg_dispatch_n = MD_COUNT;
+  return PISO_OK;
+}
+
+int piso_mg_vcycle_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* r_in, double* z_out, int sweeps,
+                       void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
+  const piso::OptScope knobs;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (int rc = mg_common_args("piso_mg_vcycle", nx, ny, laplace, r_in, z_out, workspace, sweeps)) return rc;
+  Arena ar(workspace, workspace_bytes);
+  MgPlan P;
+  if (!mg_plan(nx, ny, periodic_x ? 1 : 0, periodic_y ? 1 : 0, ar, P)) { set_error_msg("piso_mg_vcycle: workspace too small"); return PISO_ERR_INVALID_ARG; }
+  if (int rc = mg_build(P, laplace, nullptr, 0, stream)) return rc;
+  const bool use_tail = mg_use_tail(P);
+  int n_rz = 0;
+  const double* z = mg_cycle(P, r_in, sweeps, use_tail, &n_rz, stream);
+  PISO_LAUNCH_CHECK();
+  PISO_HIP_CHECK(hipMemcpyAsync(z_out, z, (size_t)P.lv[0].n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+  PISO_HIP_CHECK(hipStreamSynchronize(stream));
+  int* d = tl_mg_dispatch;
+  d[MD_LEVELS] = P.nlev; d[MD_TAIL_FIRST] = use_tail ? P.tail_first : -1; d[MD_SWEEPS] = sweeps; d[MD_ITERATIONS] = 0; d[MD_CYCLES] = 1;
+  d[MD_RESIDUAL_RECOMPUTATIONS] = 0;
+  tl_mg_dispatch_n = MD_COUNT;
+  return PISO_OK;
+}
+
+int piso_mg_level_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, int level, int* nx_out, int* ny_out,
+                      double* laplace_level_out, void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
+  const piso::OptScope knobs;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (int rc = mg_common_args("piso_mg_level", nx, ny, laplace, nx_out, ny_out, workspace, 1)) return rc;
+  Arena ar(workspace, workspace_bytes);
+  MgPlan P;
+  if (!mg_plan(nx, ny, periodic_x ? 1 : 0, periodic_y ? 1 : 0, ar, P)) { set_error_msg("piso_mg_level: workspace too small"); return PISO_ERR_INVALID_ARG; }
+  if (level < 0 || level >= P.nlev) { *nx_out = 0; *ny_out = 0; set_error_msg("piso_mg_level: no such level"); return PISO_ERR_INVALID_ARG; }
+  *nx_out = P.lv[level].nx; *ny_out = P.lv[level].ny;
+  if (!laplace_level_out) return PISO_OK;                     // (sizes only)
+  if (int rc = mg_build(P, laplace, nullptr, 0, stream)) return rc;
+  mg_export<<<mg_grid(P.lv[level].n), kBlock, 0, stream>>>(P.lv[level], laplace_level_out);
+  PISO_LAUNCH_CHECK();
+  PISO_HIP_CHECK(hipStreamSynchronize(stream));
+  return PISO_OK;
+}
+
+int piso_mg_last_dispatch(int* out, int capacity) {
+  const int n = tl_mg_dispatch_n < capacity ? tl_mg_dispatch_n : capacity;
+  for (int i = 0; i < n; ++i) out[i] = tl_mg_dispatch[i];
+  return tl_mg_dispatch_n;
+}
+
+}  // extern "C"

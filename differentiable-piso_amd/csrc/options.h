@@ -2,7 +2,7 @@
 // environment variable PISO_<NAME> (upper case); afterwards only piso_set_option() changes it.  -1 = "not set / automatic".
 // None of them changes WHAT is computed: they pick between implementations of the same arithmetic (kernel instance, staging, launch shape) or
 // switch a check / a measurement aid on and off.  Bitwise the same result: cg_no_compact, cg_no_recon, cg_no_sym, cg_nt, the bicg_* knobs and
-// conv_lds (same operations in the same order; tests/test_gpu_conv_dispatch.py holds conv_lds to it, non-finite inputs included).  Equal to round-off only - they change which workgroup or block owns which cells, so the partial
+// conv_lds, mg_tail and mg_check_every (same operations in the same order; tests/test_gpu_conv_dispatch.py holds conv_lds to it, non-finite inputs included).  Equal to round-off only - they change which workgroup or block owns which cells, so the partial
 // sums of the dot products are grouped differently: cg_persist, cg_persist_r, cg_persist_half, cg_persist_nq, cg_xcd_local, cg_pad, cg_tiny,
 // cg_rpw, cg_maxblocks (tests/test_gpu_cg_dispatch.py holds both groups to their word).  Stores and loads are atomic; a call works on a
 // snapshot (OptScope).
@@ -34,6 +34,8 @@ enum Opt {
   OPT_BICG_FUSE_P,         // 0: the direction update of BiCGStab runs as a launch of its own (bi_update_p) instead of inside the forward sweep that reads it
   OPT_SLAB_FORCE,          // 1: a communicator of ONE rank still runs the slab code paths (ring of one: halo messages and sums to itself; tests)
   OPT_SLAB_HOP_TICKS,      // measurements only: the persistent slab kernel's cross-GPU records leave this many 10 ns ticks late (an emulated link latency)
+  OPT_MG_TAIL,             // 0: the multigrid cycle (mg.hip) runs its coarse levels as launches of their own instead of inside one workgroup (the same arithmetic per cell)
+  OPT_MG_CHECK_EVERY,      // multigrid PCG: iterations queued between two host looks (default 4; result and count do not depend on it)
   OPT_COUNT
 };
 

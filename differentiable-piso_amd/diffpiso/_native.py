@@ -58,6 +58,17 @@ for _n in ("piso_cg_solve_async_f64", "piso_cg_solve_async_f32"):
     getattr(lib, _n).argtypes = [_i, _i, _i, _i, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _vp, _sz, _vp]
     getattr(lib, _n).restype = _i
 ERR_NEEDS_HOST = 5      # include/piso_hip.h: PISO_ERR_NEEDS_HOST
+ERR_UNSUPPORTED_PATTERN = 3
+lib.piso_mg_workspace_bytes.argtypes = [_i, _i]
+lib.piso_mg_workspace_bytes.restype = _sz
+lib.piso_mg_pcg_solve_f64.argtypes = [_i, _i, _i, _i, _vp, _vp, _vp, _f, _i, _i, _i, _i, _ip, _vp, _sz, _vp]
+lib.piso_mg_pcg_solve_f64.restype = _i
+lib.piso_mg_vcycle_f64.argtypes = [_i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]
+lib.piso_mg_vcycle_f64.restype = _i
+lib.piso_mg_level_f64.argtypes = [_i, _i, _i, _i, _vp, _i, _ip, _ip, _vp, _vp, _sz, _vp]
+lib.piso_mg_level_f64.restype = _i
+lib.piso_mg_last_dispatch.argtypes = [_ip, _i]
+lib.piso_mg_last_dispatch.restype = _i
 lib.piso_cg_fixed_iterations_f64.argtypes = [_i, _i, _i, _i, _vp, _vp, _vp, _i, _i, C.POINTER(C.c_float), _vp, _sz, _vp]
 lib.piso_cg_fixed_iterations_f64.restype = _i
 lib.piso_cg_profile_enable.argtypes = [_i, _i]
@@ -266,3 +277,15 @@ def conv_last_dispatch():
     if n != 0 and n != len(CONV_DISPATCH_FIELDS):
         raise PisoNativeError("piso_conv_last_dispatch returned %d fields, this binding knows %d" % (n, len(CONV_DISPATCH_FIELDS)))
     return {k: buf[i] for i, k in enumerate(CONV_DISPATCH_FIELDS[:n])}
+
+
+MG_DISPATCH_FIELDS = ("levels", "tail_first", "sweeps", "iterations", "cycles", "residual_recomputations")
+
+
+def mg_last_dispatch():
+    """What this thread's last multigrid solve / cycle ran (include/piso_hip.h: piso_mg_last_dispatch), as a dict; {} if none."""
+    buf = (C.c_int * 32)()
+    n = lib.piso_mg_last_dispatch(buf, 32)
+    if n != 0 and n != len(MG_DISPATCH_FIELDS):
+        raise PisoNativeError("piso_mg_last_dispatch returned %d fields, this binding knows %d" % (n, len(MG_DISPATCH_FIELDS)))
+    return {k: buf[i] for i, k in enumerate(MG_DISPATCH_FIELDS[:n])}

@@ -321,6 +321,38 @@ int piso_cg_last_dispatch(int* out, int capacity);
 void piso_cg_verify_stats(long long* runs_out, int* failures_out);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Multigrid-preconditioned CG for the pressure system (csrc/mg.hip; fp64; opt-in - the reference has no such solver, and
+ * piso_cg_solve_* stays what every default path calls).  Solves the system piso_cg_solve_f64 solves, (L + c 1 1^T) x = b with
+ * c = 0.1 mean|diag L| when rank_deficient, from x0 = 0, and stops when max|r| < accuracy on the recurred residual, tested on the
+ * device after EVERY iteration; the true residual is recomputed every residual_reset iterations.  Preconditioner: one V(sweeps,
+ * sweeps) cycle of damped Jacobi on a hierarchy of 2 x 2 aggregates, A_c = 1/2 P^T A P, rebuilt from `laplace` in every call.
+ * A cell with a zero diagonal is absent (x = 0 there).  Iteration counts are tens where plain CG needs thousands, independent of the
+ * polling cadence, and a solve is reproducible bit for bit.  NaN input never counts as converged: max_iterations, NaN in x.
+ * Refused with PISO_ERR_UNSUPPORTED_PATTERN: a non-zero border entry in a non-periodic direction, a zero-diagonal row with entries,
+ * rank_deficient = 1 on a matrix whose rows do not sum to zero.  nx, ny >= 4; workspace too small: PISO_ERR_INVALID_ARG.
+ * Options: "mg_tail" 0 runs the coarse levels as launches of their own instead of inside one workgroup (same result),
+ * "mg_check_every" sets the iterations queued between two host looks (default 4; same result and count). */
+size_t piso_mg_workspace_bytes(int nx, int ny);
+int piso_mg_pcg_solve_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence,
+                          double* x_out, float accuracy, int max_iterations, int rank_deficient, int residual_reset,
+                          int sweeps, int* iterations_out, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+/* test / measurement entries.  z_out = M^-1 r_in: one cycle, an approximation of L^-1 r_in (symmetric, negative definite on the
+ * present cells).  piso_mg_level_f64 copies the operator of `level` out as [nx_out * ny_out][5] (laplace_level_out NULL: sizes only;
+ * level 0 is `laplace` with couplings into absent cells dropped). */
+int piso_mg_vcycle_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* r_in, double* z_out,
+                       int sweeps, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+int piso_mg_level_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, int level, int* nx_out, int* ny_out,
+                      double* laplace_level_out, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+/* What the calling thread's last piso_mg_pcg_solve_f64 / piso_mg_vcycle_f64 ran; returns the number of fields (6):
+ *    0 levels         levels of the hierarchy
+ *    1 tail_first     first level that ran inside the one-workgroup tail kernel (-1: none)
+ *    2 sweeps
+ *    3 iterations     0 after piso_mg_vcycle_f64
+ *    4 cycles         V-cycles that contributed to the result
+ *    5 residual_recomputations */
+int piso_mg_last_dispatch(int* out, int capacity);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Convolutions of the CNN turbulence closure on the matrix cores (csrc/conv.hip; exact fp32 MFMA).  Replaces the
  * tf.nn.conv2d / tf.nn.leaky_relu calls of diffpiso/networks.py:3-57 (NHWC activations, batch 1, stride 1, no bias, kernel
  * sizes and channel counts of the closure: 7x7 4->16, 5x5 16->16, 5x5 16->32, 3x3 32->64, 3x3 64->64, 1x1 64->64, 1x1 64->2 and
