@@ -22,24 +22,13 @@
 #include "piso_common.h"
 #include "options.h"
 #include "slab_comm.h"
+#include "bicgstab_dispatch.h"    // Geo, kBiParts, kEdgeRows; the plan of a solve and which LDS instances exist
 
 namespace piso {
 
-constexpr int kBiParts = 1024;    // max blocks per component of a partial-producing kernel
+static_assert(kBiBlock == kBlock, "the plan sizes rows, grids and LDS stages for workgroups of kBlock threads");
 constexpr int kExcSlots = 4;      // exception (wrap) entries per frame row
 
-struct Geo {
-  int nx, ny;
-  int W[2], H[2], n[2], r0[2];    // face-array dims, rows, row offset of each component in the concatenated vectors
-  int xw[2], yw[2];               // periodic wrap distances in x / y (skip the duplicate face in the own direction)
-  int F[2], f0[2];                // frame rows (within 2 of a border) and their offset in the exception tables
-  int R, nb[2];                   // band height (face rows) and number of bands
-};
-
-__host__ __device__ inline int frame_rows(int W, int H) {
-  const int wi = W > 4 ? W - 4 : 0, hi = H > 4 ? H - 4 : 0;
-  return W * H - wi * hi;
-}
 // ordinal of a frame row, -1 for interior rows
 __device__ __forceinline__ int frame_ordinal(int i, int j, int W, int H) {
   if (H <= 4 || W <= 4) return j * W + i;
@@ -368,8 +357,7 @@ __global__ __launch_bounds__(kBlock) void bi_factor(BiArgs<T> a) {
 template <int E>
 __device__ __forceinline__ int sweep_slot(int s) { return (E % 2 == 0) ? s + (s >> 5) : s; }
 template <typename T, int E>
-// (rows of up to 1 024 faces - E <= 4 - are no faster this way: 512^2 89.6 against 97.1 us per iteration, 1024^2 166.0 against 160.9)
-constexpr bool kSweepLds = E >= 5 && (size_t)4 * (E * kBlock + E * 8) * sizeof(T) <= (size_t)96 * 1024;
+constexpr bool kSweepLds = bi_lds_instance(sizeof(T), E);   // (bicgstab_dispatch.h: the one statement of which instances exist)
 
 // bi_factor with coalesced memory accesses (see bi_sweep_lds): a row's five coefficients come in element order, are staged in LDS,
 // read back E consecutive elements per thread; the five results go the same way back.  Bitwise bi_factor's results.
@@ -761,7 +749,6 @@ __global__ __launch_bounds__(kBlock) void bi_update_p(BiArgs<T> a) {
 // part 0: all owned rows.  Slab mode splits the product so that the halo exchange of `in` overlaps the bulk of it: part 1 = the
 // interior (owned rows minus kEdgeRows face rows at either end: they read owned rows only), part 2 = those edge rows (they read
 // the neighbours' rows - and, across the periodic seam, the wrap partners v[ny] / v[0] / v[1] / v[ny - 1] of rows 1 / ny - 1 / ny / 0).
-constexpr int kEdgeRows = 2;
 // Four rows per thread and pass, 256 rows apart (every access of a wave is one run of consecutive elements): all loads of the four
 // rows - five coefficients, five values of `in` at clamped addresses, the dot product's partner - are issued before anything is
 // consumed, the store of a row cannot stand between the loads of the next (round 5: with one row per pass, a division per row and the
@@ -957,42 +944,11 @@ __global__ void bi_set_done(BiArgs<T> a, int done0, int done1) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// host driver
+// host driver (which instances, bands, grids a solve runs - and the shapes it refuses - are decided in bicgstab_dispatch.h: bi_plan)
 // ------------------------------------------------------------------------------------------------------------------
-static Geo make_geo(int nx, int ny, int band_rows) {
-  Geo g;
-  g.nx = nx; g.ny = ny;
-  g.W[0] = nx + 1; g.H[0] = ny; g.W[1] = nx; g.H[1] = ny + 1;
-  for (int c = 0; c < 2; ++c) {
-    g.n[c] = g.W[c] * g.H[c];
-    g.xw[c] = g.W[c] - 1 - (c == 0);
-    g.yw[c] = g.W[c] * (g.H[c] - 1 - (c == 1));
-    g.F[c] = frame_rows(g.W[c], g.H[c]);
-  }
-  g.r0[0] = 0; g.r0[1] = g.n[0];
-  g.f0[0] = 0; g.f0[1] = g.F[0];
-  int R = band_rows;
-  if (R < 0) R = (ny + 1);                                   // one band: global structured ILU(0)
-  // automatic (2048^2: 8 rows).  The rows of a band are sequential and a band is one workgroup: 2048^2 has 257 bands of 16 rows = ONE workgroup
-  // of four waves per CU, and a sweep is then bound by the latency of its row chain (75 / 100 us); 513 bands of 8 rows keep two
-  // workgroups per CU busy and halve the chain - 591 instead of 713 us per iteration, the SAME iteration counts (the matrices are
-  // strongly diagonally dominant: 3 iterations to 1e-6, 5 to 1e-9 with bands of 4 .. 32 rows; a round-4 A/B script, results in profiles/README.md).  Bands of 4
-  // rows gain nothing more at 2048^2 (the sweeps then move ~6 TB/s) and cost an iteration at 256^2.
-  // Round 5: smaller grids get lower bands by the same argument - a band is one workgroup, and two components x ny / R bands should be
-  // about two workgroups per CU: ny >= 2048: 8 rows, >= 1024: 4, >= 256: 2.  Measured (round 5, solve to 1e-6, same
-  // iteration counts): 1024^2 0.833 -> 0.767 ms, 512^2 0.519 -> 0.429, 256^2 0.440 -> 0.366.
-  // (grids of fewer than 256 rows - the lid-driven cavity - keep 8: nothing there is bound by the bands' parallelism, and at the
-  // reference script's loose 1e-3 the preconditioner decides which iterate inside the tolerance a solve stops at)
-  if (R == 0) R = ny >= 2048 ? 8 : (ny >= 1024 ? 4 : (ny >= 256 ? 2 : 8));
-  if (R > ny + 1) R = ny + 1;
-  g.R = R;
-  for (int c = 0; c < 2; ++c) g.nb[c] = (g.H[c] + R - 1) / R;
-  return g;
-}
-
 template <typename T>
 static size_t bi_workspace_bytes(int nx, int ny, const piso_slab_t* slab = nullptr) {
-  const Geo g = make_geo(nx, ny, 8);
+  const Geo g = make_geo(nx, ny);
   size_t ntot = (size_t)g.n[0] + g.n[1];
   if (slab) { const RowMap M = make_row_map(slab, nx, ny); ntot = (size_t)M.n_u + M.n_v; }      // (local storage: the rank's stored rows)
   size_t b = 0;
@@ -1023,30 +979,303 @@ enum { BD_SIZEOF_T = 0, BD_E, BD_SWEEP_LDS, BD_FACTOR_LDS, BD_R, BD_BANDS_U, BD_
        BD_SLAB, BD_LOOK0, BD_PASSES, BD_HOST_LOOKS, BD_FAILED_MASK, BD_COUNT };
 static thread_local int tl_bi_dispatch[BD_COUNT];
 static thread_local int tl_bi_dispatch_n = 0;
-
-template <typename T, int E>
-static void launch_factor(const BiArgs<T>& a, dim3 gb, hipStream_t s) {
-  tl_bi_dispatch[BD_E] = E;
-  tl_bi_dispatch[BD_FACTOR_LDS] = 0;
-  if constexpr (kSweepLds<T, E> && (size_t)5 * (E * kBlock + E * 8) * sizeof(T) <= (size_t)96 * 1024) {
-    if (opt(OPT_BICG_SWEEP_LDS) != 0) { tl_bi_dispatch[BD_FACTOR_LDS] = 1; bi_factor_lds<T, E><<<gb, kBlock, 0, s>>>(a); return; }
-  }
-  bi_factor<T, E><<<gb, kBlock, 0, s>>>(a);
+// the 13 fields of the plan; passes, host_looks and failed_mask follow where the solve learns them (bi_solve, BiRun::fetch)
+static void record_dispatch(const BiPlan& p, size_t elem, int max_it) {
+  int* d = tl_bi_dispatch;
+  for (int i = 0; i < BD_COUNT; ++i) d[i] = 0;
+  d[BD_SIZEOF_T] = (int)elem; d[BD_E] = p.E;
+  d[BD_SWEEP_LDS] = p.sweep_lds && max_it > 0;              // (what RAN: a solve of no iterations sweeps nothing)
+  d[BD_FACTOR_LDS] = p.factor_lds;
+  d[BD_R] = p.g.R; d[BD_BANDS_U] = p.be[0] - p.bb[0]; d[BD_BANDS_V] = p.be[1] - p.bb[1]; d[BD_BLOCKS] = p.nparts;
+  d[BD_FOLD] = p.fold_ok; d[BD_FUSE_P] = p.fuse_p; d[BD_TRANSPOSE] = p.transpose; d[BD_SLAB] = p.slab; d[BD_LOOK0] = p.look0;
+  tl_bi_dispatch_n = BD_COUNT;
 }
-template <typename T, int E>
-static void launch_sweeps(const BiArgs<T>& aL, const BiArgs<T>& aU, dim3 gb, const T* in, T* out, hipStream_t s) {
-  if constexpr (kSweepLds<T, E>) {
-    if (opt(OPT_BICG_SWEEP_LDS) != 0) {
-      tl_bi_dispatch[BD_SWEEP_LDS] = 1;
-      bi_sweep_lds<T, E, true><<<gb, kBlock, 0, s>>>(aL, in, aL.y);
-      bi_sweep_lds<T, E, false><<<gb, kBlock, 0, s>>>(aU, aU.y, out);
-      return;
+
+// The only host code that names the factorisation and sweep kernels: the plan's E through the ladder, its LDS forms where they exist.
+template <typename T>
+static void launch_factor(const BiPlan& pl, const BiArgs<T>& a, hipStream_t s) {
+  const dim3 gb(pl.grid_b, 2);
+  bi_with_E(pl.E, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    if constexpr (kSweepLds<T, E>) {
+      if (pl.factor_lds) { bi_factor_lds<T, E><<<gb, kBlock, 0, s>>>(a); return; }
+    }
+    bi_factor<T, E><<<gb, kBlock, 0, s>>>(a);
+  });
+}
+template <typename T>
+static void launch_sweeps(const BiPlan& pl, const BiArgs<T>& aL, const BiArgs<T>& aU, const T* in, T* out, hipStream_t s) {
+  const dim3 gb(pl.grid_b, 2);
+  bi_with_E(pl.E, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    if constexpr (kSweepLds<T, E>) {
+      if (pl.sweep_lds) {
+        bi_sweep_lds<T, E, true><<<gb, kBlock, 0, s>>>(aL, in, aL.y);
+        bi_sweep_lds<T, E, false><<<gb, kBlock, 0, s>>>(aU, aU.y, out);
+        return;
+      }
+    }
+    bi_sweep<T, E, true><<<gb, kBlock, 0, s>>>(aL, in, aL.y);
+    bi_sweep<T, E, false><<<gb, kBlock, 0, s>>>(aU, aU.y, out);
+  });
+}
+
+// One solve: the launch sequencing (which buffers and scalar records the NEXT launch sees), the composite steps of an iteration, the
+// set-up launches, a pass and the restart logic around it.  The members that launch kernels are declared in the order a solve first
+// uses their kernels, and both precisions are instantiated explicitly below (members in declaration order): that is the order the
+// kernels stand in the code object.
+template <typename T>
+struct BiRun {
+  const BiPlan& pl;
+  BiArgs<T> a;                       // the arguments every launch starts from (next())
+  hipStream_t stream;
+  PisoComm* pc;
+  T* pbuf0 = nullptr;                // two buffers of partial sums (see BiArgs::parts_in)
+  CompScalars<T>* scbuf0 = nullptr;  // two scalar records (see BiArgs::sc_prev)
+  BiPeer bp;
+  HaloMsg msgs[4] = {};              // {to upper, to lower, from lower, from upper}: edge rows of an SpMV input
+  SideStream* side = nullptr;
+  // Two buffers of partial sums: a launch reads the one the last producer wrote and writes the other; two scalar records: a launch
+  // with folded stages (folded_scalars) reads one and leaves the other as the current one.
+  int cur = 0, pw = 0;
+  BiHost<T> host;                    // the last host look
+  BiRun(const BiPlan& plan, hipStream_t s, PisoComm* comm) : pl(plan), a(), stream(s), pc(comm) {}
+
+  int bind(void* ws, size_t ws_bytes, size_t ntot);
+  int link_slabs();
+  dim3 grid_v() const { return dim3(pl.grid_v, 2); }
+  // arguments of the NEXT launch
+  BiArgs<T> next(int fold, bool produces) {
+    BiArgs<T> b = a;
+    b.parts_in = pbuf0 + (size_t)pw * (2 * 4 * kBiParts);
+    b.parts = pbuf0 + (size_t)(pw ^ 1) * (2 * 4 * kBiParts);
+    b.fold = fold;
+    b.sc_prev = scbuf0 + 2 * cur;
+    if (fold) cur ^= 1;
+    b.sc = scbuf0 + 2 * cur;
+    if (produces) pw ^= 1;
+    return b;
+  }
+  int F(int stage) const { return pl.fold_ok ? stage + 1 : 0; }         // a stage as a launch's `fold` argument (0: stages are launches)
+  BiPeer next_seq() { BiPeer b = bp; if (pl.slab) b.seq = ++pc->seq_ar; return b; }
+  int exchange_on(T* vec, hipStream_t st) {
+    if (pl.rccl) return comm_rccl_exchange_segments(pc, vec, sizeof(T) == 8 ? 1 : 0, msgs, st);
+    peer_exchange_segments<T><<<2, 256, 0, st>>>(bp.pv, vec, msgs[0], msgs[1], msgs[2], msgs[3], ++pc->seq_ex, pc->err);
+    return PISO_OK;
+  }
+  int halo(T* vec) { return pl.slab ? exchange_on(vec, stream) : PISO_OK; }
+  // one stage of the scalar recurrences (peer transport / one GPU: one launch; RCCL: the ranks' sums, an all-reduce, the rest)
+  int scalar(int stage) {
+    const BiArgs<T> sa = next(0, false);
+    if (pl.slab && pl.rccl) {
+      BiPeer b = bp;
+      b.on = 2; bi_scalar<T><<<2, kBlock, 0, stream>>>(sa, stage, b);
+      { const int rc = comm_rccl_allreduce_f64(pc, bp.gsum, 8, stream); if (rc != PISO_OK) return rc; }
+      b.on = 3; bi_scalar<T><<<2, kBlock, 0, stream>>>(sa, stage, b);
+    } else {
+      bi_scalar<T><<<2, kBlock, 0, stream>>>(sa, stage, next_seq());
+    }
+    return PISO_OK;
+  }
+  void spmv_part(int which, int grid, const BiArgs<T>& b, T* in, T* out, int part, int slot0) {
+    if (which == 0) bi_spmv<T, 0><<<dim3(grid, 2), kBlock, 0, stream>>>(b, in, out, part, slot0);
+    else bi_spmv<T, 1><<<dim3(grid, 2), kBlock, 0, stream>>>(b, in, out, part, slot0);
+  }
+  // y = B in with the edge rows of `in` fetched from the neighbours meanwhile (one GPU: one launch)
+  int spmv(int which, T* in, T* out) {
+    const BiArgs<T> b = next(0, true);                        // (slab mode: both launches write the same buffer of partial sums)
+    if (!pl.slab) { spmv_part(which, pl.grid_v, b, in, out, 0, 0); return PISO_OK; }
+    PISO_HIP_CHECK(hipEventRecord(side->ready, stream));                         // `in` is complete on the owned rows
+    PISO_HIP_CHECK(hipStreamWaitEvent(side->stream, side->ready, 0));
+    { const int rc = exchange_on(in, side->stream); if (rc != PISO_OK) return rc; }
+    PISO_HIP_CHECK(hipEventRecord(side->halo, side->stream));
+    spmv_part(which, pl.grid_vs, b, in, out, 1, 0);
+    PISO_HIP_CHECK(hipStreamWaitEvent(stream, side->halo, 0));
+    spmv_part(which, pl.grid_e, b, in, out, 2, pl.gv);
+    return PISO_OK;
+  }
+  int setup(const T* val, const int* rowptr, const int* col, const T* x0);
+  void precond(const T* in, T* out, int fold, int fuse_p) {            // (fold: scalar stages the blocks of the forward sweep apply first)
+    BiArgs<T> aL = next(fold, false);
+    aL.fuse_p = fuse_p;
+    const BiArgs<T> aU = next(0, false);
+    launch_sweeps<T>(pl, aL, aU, in, out, stream);
+  }
+  // the host looks at the current scalar record and the flags
+  int fetch() {
+    tl_bi_dispatch[BD_HOST_LOOKS] += 1;
+    PISO_HIP_CHECK(hipMemcpyAsync(host.sc, scbuf0 + 2 * cur, 2 * sizeof(CompScalars<T>), hipMemcpyDeviceToHost, stream));
+    PISO_HIP_CHECK(hipMemcpyAsync(host.flags, a.flags, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
+    PISO_HIP_CHECK(hipStreamSynchronize(stream));
+    return PISO_OK;
+  }
+  int pass(int max_it, bool& pattern_checked);
+  int solve(float tol, int max_it);
+  int agree();
+};
+
+// the workspace, cut into the arrays of BiArgs (bi_workspace_bytes is the size of it)
+template <typename T>
+int BiRun<T>::bind(void* ws, size_t ws_bytes, size_t ntot) {
+  const Geo& g = a.g;
+  Arena ar(ws, ws_bytes);
+  const auto tk = [&](size_t n) { return ar.take<T>(n); };
+  a.cS = tk(ntot); a.cW = tk(ntot); a.cC = tk(ntot); a.cE = tk(ntot); a.cN = tk(ntot);
+  a.L = reinterpret_cast<Pair<T>*>(tk(2 * ntot)); a.U = reinterpret_cast<Tri<T>*>(tk(3 * ntot));
+  a.r = tk(ntot); a.rh = tk(ntot); a.p = tk(ntot); a.v = tk(ntot); a.t = tk(ntot);
+  a.y = tk(ntot); a.ph = tk(ntot); a.sh = tk(ntot);
+  a.ecol = ar.take<int>((size_t)(g.F[0] + g.F[1]) * kExcSlots);
+  a.eval = ar.take<T>((size_t)(g.F[0] + g.F[1]) * kExcSlots);
+  pbuf0 = ar.take<T>(2 * 2 * 4 * kBiParts);
+  scbuf0 = ar.take<CompScalars<T>>(2 * 2);
+  a.parts = pbuf0; a.parts_in = pbuf0; a.sc = scbuf0; a.sc_prev = scbuf0; a.fold = 0; a.fuse_p = 0;
+  a.flags = ar.take<int>(2);
+  if (!ar.ok()) { set_error_msg("piso_multi_bicgstab_ilu: workspace too small"); return PISO_ERR_INVALID_ARG; }
+  bp.on = 0; bp.seq = 0; bp.err = nullptr; bp.gsum = nullptr;
+  if (pc && pl.rccl) { bp.gsum = ar.take<double>(8); if (!ar.ok()) { set_error_msg("piso_multi_bicgstab_ilu_slab: workspace too small"); return PISO_ERR_INVALID_ARG; } }
+  return PISO_OK;
+}
+
+// a slab call's links to its neighbours: the ring, the four halo messages and - slab mode - the side stream the exchange runs on
+template <typename T>
+int BiRun<T>::link_slabs() {
+  const Geo& g = a.g;
+  const int nyl = pl.nyl, jb = pl.jb, jt = jb + nyl - 1, world = pc->world;
+  bp.pv = make_view(pc, true);       // always a ring: without periodic y the wrap rows travel but no matrix entry reads them
+  bp.err = pc->err; bp.on = pl.slab ? 1 : 0;
+  // Edge rows of an SpMV input; they land at the same global offsets on the receiver.  Downwards go u[jb], v[jb] and v[jb + 1],
+  // upwards u[jt], v[jt] - and, across the periodic seam, the duplicate row v[ny] as well: in A the row v[ny] reads v[1] and
+  // v[0] reads v[ny - 1] (the wrap skips the duplicate face, central_difference_csr_op.cu.cc:259-264), in A^T it is v[1] that
+  // reads v[ny] and v[ny - 1] that reads v[0].
+  const int lo = bp.pv.lower, up = bp.pv.upper;
+  const int jt_lo = lo * nyl + nyl - 1, jb_up = up * nyl;
+  // (where a row starts in the concatenated vectors: the whole grid's offsets, or the stored rows' - rows that follow each other
+  // around the ring - v[ny - 1], v[ny], v[0], v[1] - are neighbours in the stored arrays as well)
+  const auto at = [&](int c, int j) -> int { return a.M.on ? (c ? a.M.n_u : 0) + a.M.frow(c, j * g.W[c]) : g.r0[c] + j * g.W[c]; };
+  msgs[0] = {2, {at(0, jt), at(1, jt), 0}, {g.W[0], (pl.last ? 2 : 1) * g.W[1], 0}};
+  msgs[1] = {2, {at(0, jb), at(1, jb), 0}, {g.W[0], 2 * g.W[1], 0}};
+  msgs[2] = {2, {at(0, jt_lo), at(1, jt_lo), 0}, {g.W[0], (lo == world - 1 ? 2 : 1) * g.W[1], 0}};
+  msgs[3] = {2, {at(0, jb_up), at(1, jb_up), 0}, {g.W[0], 2 * g.W[1], 0}};
+  if (!pl.slab) return PISO_OK;
+  int dev_now = 0;
+  PISO_HIP_CHECK(hipGetDevice(&dev_now));
+  if (dev_now < 0 || dev_now >= kMaxDevices) { set_error_msg("piso_multi_bicgstab_ilu_slab: device ordinal out of range"); return PISO_ERR_INVALID_ARG; }
+  side = &tl_side_dev[dev_now];
+  if (!side->stream) {
+    PISO_HIP_CHECK(hipStreamCreateWithFlags(&side->stream, hipStreamNonBlocking));
+    PISO_HIP_CHECK(hipEventCreateWithFlags(&side->ready, hipEventDisableTiming));
+    PISO_HIP_CHECK(hipEventCreateWithFlags(&side->halo, hipEventDisableTiming));
+  }
+  return PISO_OK;
+}
+
+// scalars, CSR -> stencil form (+ the pattern / NaN flags, agreed on by the ranks), ILU(0)
+template <typename T>
+int BiRun<T>::setup(const T* val, const int* rowptr, const int* col, const T* x0) {
+  bi_init_scalars<T><<<1, 256, 0, stream>>>(a);
+  bi_convert<T><<<grid_v(), kBlock, 0, stream>>>(a, val, rowptr, col, x0, pl.transpose);
+  if (pl.slab && pl.rccl) { const int rc = comm_rccl_allreduce_i32(pc, a.flags, 2, stream); if (rc != PISO_OK) return rc; }   // (sums: non-zero = set)
+  else if (pl.slab) bi_flags_allreduce<T><<<1, 64, 0, stream>>>(a, next_seq());
+  launch_factor<T>(pl, a, stream);
+  PISO_LAUNCH_CHECK();
+  return PISO_OK;
+}
+
+// one pass from the current x: residual, up to max_it iterations in chunks between host looks; leaves the last look in `host`
+template <typename T>
+int BiRun<T>::pass(int max_it, bool& pattern_checked) {
+  const bool fold_ok = pl.fold_ok;
+  // r = b - B x, rh = r, p = v = 0, ||r|| test, first rho / beta
+  { const int rc = halo(a.x); if (rc != PISO_OK) return rc; }
+  bi_residual_init<T><<<grid_v(), kBlock, 0, stream>>>(next(0, true));
+  { const int rc = scalar(ST_INIT); if (rc != PISO_OK) return rc; }
+  PISO_LAUNCH_CHECK();
+  int it = 0, look = pl.look0;
+  bool all_done = false;
+  while (it < max_it && !all_done) {
+    // iterations between host looks: 2, 2, 4, 8, 16, 16, ... - a solve of 3 iterations (the 2048^2 benchmark) still stops at
+    // once, a solve of 100 (lid-driven cavity) synchronises 9 times instead of 50; launches of a converged component return early
+    const int chunk = (max_it - it) < look ? (max_it - it) : look;
+    if (look < 2) look = 2; else if (it >= 4 && look < 16) look *= 2;
+    for (int q = 0; q < chunk; ++q, ++it) {
+      // (folded: the ||r|| test that ended the iteration before - inside a chunk nobody else has applied it yet - then rho / beta)
+      int fold_p = 0;
+      if (it > 0) {
+        if (fold_ok) fold_p = q > 0 ? (F(ST_CHECK_R) | (F(ST_RHO_BETA) << 4)) : F(ST_RHO_BETA);
+        else { const int rc = scalar(ST_RHO_BETA); if (rc != PISO_OK) return rc; }
+      }
+      if (pl.fuse_p) precond(a.p, a.ph, fold_p, 1);
+      else {
+        bi_update_p<T><<<grid_v(), kBlock, 0, stream>>>(next(fold_p, false));
+        precond(a.p, a.ph, 0, 0);
+      }
+      { const int rc = spmv(0, a.ph, a.v); if (rc != PISO_OK) return rc; }
+      if (!fold_ok) { const int rc = scalar(ST_ALPHA); if (rc != PISO_OK) return rc; }
+      bi_update_xr<T, 0><<<grid_v(), kBlock, 0, stream>>>(next(F(ST_ALPHA), true));
+      if (!fold_ok) { const int rc = scalar(ST_CHECK_S); if (rc != PISO_OK) return rc; }
+      precond(a.r, a.sh, F(ST_CHECK_S), 0);
+      { const int rc = spmv(1, a.sh, a.t); if (rc != PISO_OK) return rc; }
+      if (!fold_ok) { const int rc = scalar(ST_OMEGA); if (rc != PISO_OK) return rc; }
+      bi_update_xr<T, 1><<<grid_v(), kBlock, 0, stream>>>(next(F(ST_OMEGA), true));
+      if (!fold_ok || q == chunk - 1) { const int rc = scalar(ST_CHECK_R); if (rc != PISO_OK) return rc; }   // (the host looks at it)
+    }
+    PISO_LAUNCH_CHECK();
+    { const int rc = fetch(); if (rc != PISO_OK) return rc; }
+    if (!pattern_checked) {
+      pattern_checked = true;
+      if (host.flags[0]) {
+        set_error_msg("piso_multi_bicgstab_ilu: CSR input is not a 5-point staggered-grid matrix");
+        return PISO_ERR_UNSUPPORTED_PATTERN;
+      }
+    }
+    all_done = host.sc[0].done && host.sc[1].done;
+  }
+  if (max_it == 0 || !pattern_checked) return fetch();
+  return PISO_OK;
+}
+
+// a pass; a component that ends it above 100 tol (or at NaN) is zeroed and run once more, alone, from x = 0; still failing: zeros
+template <typename T>
+int BiRun<T>::solve(float tol, int max_it) {
+  int failed_mask = 0;      // components that already used their one restart and failed again
+  bool pattern_checked = false;
+  for (int restart = 0; restart < 2; ++restart) {
+    tl_bi_dispatch[BD_PASSES] = restart + 1;
+    { const int rc = pass(max_it, pattern_checked); if (rc != PISO_OK) return rc; }
+    // failure test per component (:392-407): ||r|| > 100 tol or NaN -> x = 0 and one more pass from x = 0
+    int fail_now = 0;
+    for (int c = 0; c < 2; ++c) {
+      const T nrm = host.sc[c].nrm;
+      if (nrm > (T)tol * 100 || nrm != nrm) fail_now |= 1 << c;
+    }
+    if (!fail_now) break;
+    bi_zero_x<T><<<grid_v(), kBlock, 0, stream>>>(next(0, false), fail_now);
+    if (restart == 0) {
+      bi_set_done<T><<<1, 64, 0, stream>>>(next(0, false), !(fail_now & 1), !((fail_now >> 1) & 1));
+    } else {
+      failed_mask = fail_now;
     }
   }
-  tl_bi_dispatch[BD_SWEEP_LDS] = 0;
-  bi_sweep<T, E, true><<<gb, kBlock, 0, s>>>(aL, in, aL.y);
-  bi_sweep<T, E, false><<<gb, kBlock, 0, s>>>(aU, aU.y, out);
+  tl_bi_dispatch[BD_FAILED_MASK] = failed_mask;
+  return PISO_OK;
 }
+
+// peer transport: every rank returns the same status
+template <typename T>
+int BiRun<T>::agree() {
+  int herr = 0;
+  peer_agree_on_error<><<<1, 64, 0, stream>>>(bp.pv, pc->err, ++pc->seq_ar);
+  PISO_HIP_CHECK(hipMemcpyAsync(&herr, pc->err, sizeof(int), hipMemcpyDeviceToHost, stream));
+  PISO_HIP_CHECK(hipStreamSynchronize(stream));
+  if (herr) {
+    PISO_HIP_CHECK(hipMemsetAsync(pc->err, 0, sizeof(int), stream));
+    set_error_msg("piso_multi_bicgstab_ilu_slab: a wait on a peer's mailbox gave up (peer process gone or not running?)");
+    return PISO_ERR_HIP;
+  }
+  return PISO_OK;
+}
+template struct BiRun<float>;
+template struct BiRun<double>;
 
 // pc = NULL: one GPU.  Else: this rank works on the face rows of its y-slab of cell rows.  slab = NULL: val / rowptr / col / rhs / x0
 // are the FULL arrays on every rank (a replicated assembly), x_out is valid on the owned rows only.  slab != NULL (the slab-decomposed
@@ -1071,297 +1300,35 @@ static int bi_solve(const T* val, const int* rowptr, const int* col, const T* rh
     set_error_msg("piso_multi_bicgstab_ilu: workspace too small");
     return PISO_ERR_INVALID_ARG;
   }
+  if (pc && pc->transport == TRANSPORT_PEER && !pc->connected) { set_error_msg("piso_multi_bicgstab_ilu_slab: the peer communicator is not connected"); return PISO_ERR_INVALID_ARG; }
+  const RowMap M = make_row_map(slab_rows, nx, ny, per_x, per_y);
+  const size_t ntot = (size_t)M.n_u + M.n_v;                 // elements of a vector as stored (one GPU: the whole grid's face rows)
+  BiQuery q;
+  q.nx = nx; q.ny = ny; q.band_rows = band_rows; q.elem = sizeof(T); q.transpose = transpose; q.ntot = ntot;
+  q.bicg_fold = opt(OPT_BICG_FOLD); q.bicg_sweep_lds = opt(OPT_BICG_SWEEP_LDS); q.bicg_fuse_p = opt(OPT_BICG_FUSE_P); q.slab_force = opt(OPT_SLAB_FORCE);
+  q.comm = pc != nullptr; q.rccl = pc && pc->transport == TRANSPORT_RCCL;
+  q.world = pc ? pc->world : 1; q.rank = pc ? pc->rank : 0; q.row_cap = pc ? pc->row_cap : 0; q.slab_rows = slab_rows;
+  const BiPlan pl = bi_plan(q);
+  if (pl.status != PISO_OK) { set_error_msg(pl.msg); return pl.status; }     // (nothing is bound, created or launched yet)
+
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  BiArgs<T> a;
-  a.g = make_geo(nx, ny, band_rows);
-  a.M = make_row_map(slab_rows, nx, ny, per_x, per_y);
-  const Geo& g = a.g;
-  const size_t ntot = slab_rows ? (size_t)a.M.n_u + a.M.n_v : (size_t)g.n[0] + g.n[1];
-  Arena ar(ws, ws_bytes);
-  auto tk = [&](size_t n) { return ar.take<T>(n); };
-  a.cS = tk(ntot); a.cW = tk(ntot); a.cC = tk(ntot); a.cE = tk(ntot); a.cN = tk(ntot);
-  a.L = reinterpret_cast<Pair<T>*>(tk(2 * ntot)); a.U = reinterpret_cast<Tri<T>*>(tk(3 * ntot));
-  a.r = tk(ntot); a.rh = tk(ntot); a.p = tk(ntot); a.v = tk(ntot); a.t = tk(ntot);
-  a.y = tk(ntot); a.ph = tk(ntot); a.sh = tk(ntot);
-  a.ecol = ar.take<int>((size_t)(g.F[0] + g.F[1]) * kExcSlots);
-  a.eval = ar.take<T>((size_t)(g.F[0] + g.F[1]) * kExcSlots);
-  T* const pbuf0 = ar.take<T>(2 * 2 * 4 * kBiParts);                      // two buffers of partial sums (see BiArgs::parts_in)
-  CompScalars<T>* const scbuf0 = ar.take<CompScalars<T>>(2 * 2);         // two scalar records (see BiArgs::sc_prev)
-  a.parts = pbuf0; a.parts_in = pbuf0; a.sc = scbuf0; a.sc_prev = scbuf0; a.fold = 0; a.fuse_p = 0;
-  a.flags = ar.take<int>(2);
-  a.rhs = rhs; a.x = x_out; a.tol = tol;
-  if (!ar.ok()) { set_error_msg("piso_multi_bicgstab_ilu: workspace too small"); return PISO_ERR_INVALID_ARG; }
-
-  for (int c = 0; c < 2; ++c) { a.rb[c] = 0; a.re[c] = g.n[c]; a.bb[c] = 0; a.be[c] = g.nb[c]; }
-  BiPeer bp;
-  bp.on = 0; bp.seq = 0; bp.err = nullptr; bp.gsum = nullptr;
-  HaloMsg to_upper = {}, to_lower = {}, from_lower = {}, from_upper = {};
-  const bool slab = pc && (pc->world > 1 || opt(OPT_SLAB_FORCE) > 0);      // (slab_force: test knob - one rank, a ring with itself)
-  const bool rccl = pc && pc->transport == TRANSPORT_RCCL;                   // halo rows by send / recv, sums by all-reduce (slab_comm.h)
-  if (pc) {
-    if (pc->transport == TRANSPORT_PEER && !pc->connected) { set_error_msg("piso_multi_bicgstab_ilu_slab: the peer communicator is not connected"); return PISO_ERR_INVALID_ARG; }
-    const int world = pc->world, rank = pc->rank;
-    // (a product is split into interior rows and kEdgeRows face rows at either end of the slab: thinner slabs would make the two
-    // edge ranges overlap and count their rows twice in the dot products)
-    if (ny % world != 0 || (ny / world) % g.R != 0 || ny / world < 2 * kEdgeRows) {
-      set_error_msg("piso_multi_bicgstab_ilu_slab: the slabs (ny / ranks cell rows) must be whole preconditioner bands of at least 4 rows");
-      return PISO_ERR_INVALID_ARG;
-    }
-    if (!rccl && (size_t)(3 * nx + 1) > pc->row_cap) { set_error_msg("piso_multi_bicgstab_ilu_slab: communicator row_capacity < 3 nx + 1"); return PISO_ERR_INVALID_ARG; }
-    const int nyl = ny / world, jb = rank * nyl, jt = jb + nyl - 1;
-    const bool last = rank == world - 1;
-    if (slab_rows && (slab_rows->row_begin != jb || slab_rows->row_end != jb + nyl || (slab_rows->owns_last_face_row != 0) != last)) {
-      set_error_msg("piso_multi_bicgstab_ilu_slab: the slab does not match the communicator's rank");
-      return PISO_ERR_INVALID_ARG;
-    }
-    a.rb[0] = jb * g.W[0]; a.re[0] = (jb + nyl) * g.W[0];
-    a.rb[1] = jb * g.W[1]; a.re[1] = (jb + nyl + (last ? 1 : 0)) * g.W[1];      // (the duplicate face row v[ny] lives on the last slab)
-    a.bb[0] = a.bb[1] = jb / g.R;
-    a.be[0] = (jb + nyl) / g.R;
-    a.be[1] = last ? g.nb[1] : (jb + nyl) / g.R;
-    bp.pv = make_view(pc, true);       // always a ring: without periodic y the wrap rows travel but no matrix entry reads them
-    bp.err = pc->err; bp.on = slab ? 1 : 0;
-    if (rccl) { bp.gsum = ar.take<double>(8); if (!ar.ok()) { set_error_msg("piso_multi_bicgstab_ilu_slab: workspace too small"); return PISO_ERR_INVALID_ARG; } }
-    // Edge rows of an SpMV input; they land at the same global offsets on the receiver.  Downwards go u[jb], v[jb] and v[jb + 1],
-    // upwards u[jt], v[jt] - and, across the periodic seam, the duplicate row v[ny] as well: in A the row v[ny] reads v[1] and
-    // v[0] reads v[ny - 1] (the wrap skips the duplicate face, central_difference_csr_op.cu.cc:259-264), in A^T it is v[1] that
-    // reads v[ny] and v[ny - 1] that reads v[0].
-    const int lo = bp.pv.lower, up = bp.pv.upper;
-    const int jt_lo = lo * nyl + nyl - 1, jb_up = up * nyl;
-    // (where a row starts in the concatenated vectors: the whole grid's offsets, or the stored rows' - rows that follow each other
-    // around the ring - v[ny - 1], v[ny], v[0], v[1] - are neighbours in the stored arrays as well)
-    auto at = [&](int c, int j) -> int { return a.M.on ? (c ? a.M.n_u : 0) + a.M.frow(c, j * g.W[c]) : g.r0[c] + j * g.W[c]; };
-    to_lower = {2, {at(0, jb), at(1, jb), 0}, {g.W[0], 2 * g.W[1], 0}};
-    to_upper = {2, {at(0, jt), at(1, jt), 0}, {g.W[0], (last ? 2 : 1) * g.W[1], 0}};
-    from_lower = {2, {at(0, jt_lo), at(1, jt_lo), 0}, {g.W[0], (lo == world - 1 ? 2 : 1) * g.W[1], 0}};
-    from_upper = {2, {at(0, jb_up), at(1, jb_up), 0}, {g.W[0], 2 * g.W[1], 0}};
-  }
-  auto next_seq = [&]() -> BiPeer { BiPeer b = bp; if (slab) b.seq = ++pc->seq_ar; return b; };
-  const HaloMsg msgs[4] = {to_upper, to_lower, from_lower, from_upper};
-  constexpr int kDtype = sizeof(T) == 8 ? 1 : 0;
-  auto exchange_on = [&](T* vec, hipStream_t st) -> int {
-    if (rccl) return comm_rccl_exchange_segments(pc, vec, kDtype, msgs, st);
-    peer_exchange_segments<T><<<2, 256, 0, st>>>(bp.pv, vec, to_upper, to_lower, from_lower, from_upper, ++pc->seq_ex, pc->err);
-    return PISO_OK;
-  };
-  auto halo = [&](T* vec) -> int { return slab ? exchange_on(vec, stream) : PISO_OK; };
-  // one stage of the scalar recurrences (peer transport / one GPU: one launch; RCCL: the ranks' sums, an all-reduce, the rest)
-  // Arguments of the NEXT launch.  Two buffers of partial sums: a launch reads the one the last producer wrote and writes the other;
-  // two scalar records: a launch with folded stages (folded_scalars) reads one and leaves the other as the current one.
-  int cur = 0, pw = 0;
-  auto next = [&](int fold, bool produces) -> BiArgs<T> {
-    BiArgs<T> b = a;
-    b.parts_in = pbuf0 + (size_t)pw * (2 * 4 * kBiParts);
-    b.parts = pbuf0 + (size_t)(pw ^ 1) * (2 * 4 * kBiParts);
-    b.fold = fold;
-    b.sc_prev = scbuf0 + 2 * cur;
-    if (fold) cur ^= 1;
-    b.sc = scbuf0 + 2 * cur;
-    if (produces) pw ^= 1;
-    return b;
-  };
-  auto scalar = [&](int stage) -> int {
-    const BiArgs<T> sa = next(0, false);
-    if (slab && rccl) {
-      BiPeer b = bp;
-      b.on = 2; bi_scalar<T><<<2, kBlock, 0, stream>>>(sa, stage, b);
-      { const int rc = comm_rccl_allreduce_f64(pc, bp.gsum, 8, stream); if (rc != PISO_OK) return rc; }
-      b.on = 3; bi_scalar<T><<<2, kBlock, 0, stream>>>(sa, stage, b);
-    } else {
-      bi_scalar<T><<<2, kBlock, 0, stream>>>(sa, stage, next_seq());
-    }
-    return PISO_OK;
-  };
-  int dev_now = 0;
-  if (slab) { PISO_HIP_CHECK(hipGetDevice(&dev_now)); if (dev_now < 0 || dev_now >= kMaxDevices) { set_error_msg("piso_multi_bicgstab_ilu_slab: device ordinal out of range"); return PISO_ERR_INVALID_ARG; } }
-  SideStream& tl_side = tl_side_dev[dev_now];
-  if (slab && !tl_side.stream) {
-    PISO_HIP_CHECK(hipStreamCreateWithFlags(&tl_side.stream, hipStreamNonBlocking));
-    PISO_HIP_CHECK(hipEventCreateWithFlags(&tl_side.ready, hipEventDisableTiming));
-    PISO_HIP_CHECK(hipEventCreateWithFlags(&tl_side.halo, hipEventDisableTiming));
-  }
-
-  const int own0 = a.re[0] - a.rb[0], own1 = a.re[1] - a.rb[1];
-  const int nmax = own0 > own1 ? own0 : own1;
-  int gv = (nmax + kBlock * 4 - 1) / (kBlock * 4);
-  gv = (gv + 7) & ~7;                                       // (a multiple of the XCD count: stencil_rows deals the rows by XCD)
-  if (gv > kBiParts) gv = kBiParts;
-  if (gv < 1) gv = 1;
-  // slab mode: a product is two launches (interior, edge rows) that write the partial slots [0, gv) and [gv, gv + ge); every other
-  // kernel runs gv + ge blocks so that it rewrites ALL slots the scalar kernels add up
-  int ge = 0;
-  if (slab) {
-    ge = (2 * kEdgeRows * g.W[0] + kBlock * 4 - 1) / (kBlock * 4);
-    if (gv + ge > kBiParts) gv = kBiParts - ge;
-  }
-  const dim3 grid_v(gv + ge, 2);
-  a.nparts = gv + ge;
-  const dim3 grid_vs(gv, 2), grid_e(ge > 0 ? ge : 1, 2);
-  // y = B in with the edge rows of `in` fetched from the neighbours meanwhile (one GPU: one launch)
-  auto spmv = [&](int which, T* in, T* out) -> int {
-    const BiArgs<T> a = next(0, true);                        // (slab mode: both launches write the same buffer of partial sums)
-    if (!slab) {
-      if (which == 0) bi_spmv<T, 0><<<grid_v, kBlock, 0, stream>>>(a, in, out, 0, 0);
-      else bi_spmv<T, 1><<<grid_v, kBlock, 0, stream>>>(a, in, out, 0, 0);
-      return PISO_OK;
-    }
-    PISO_HIP_CHECK(hipEventRecord(tl_side.ready, stream));                       // `in` is complete on the owned rows
-    PISO_HIP_CHECK(hipStreamWaitEvent(tl_side.stream, tl_side.ready, 0));
-    { const int rc = exchange_on(in, tl_side.stream); if (rc != PISO_OK) return rc; }
-    PISO_HIP_CHECK(hipEventRecord(tl_side.halo, tl_side.stream));
-    if (which == 0) bi_spmv<T, 0><<<grid_vs, kBlock, 0, stream>>>(a, in, out, 1, 0);
-    else bi_spmv<T, 1><<<grid_vs, kBlock, 0, stream>>>(a, in, out, 1, 0);
-    PISO_HIP_CHECK(hipStreamWaitEvent(stream, tl_side.halo, 0));
-    if (which == 0) bi_spmv<T, 0><<<grid_e, kBlock, 0, stream>>>(a, in, out, 2, gv);
-    else bi_spmv<T, 1><<<grid_e, kBlock, 0, stream>>>(a, in, out, 2, gv);
-    return PISO_OK;
-  };
-  const int nb0 = a.be[0] - a.bb[0], nb1 = a.be[1] - a.bb[1];
-  const int nbmax = nb0 > nb1 ? nb0 : nb1;
-  const dim3 grid_b(nbmax, 2);
-  const int Wmax = nx + 1;
-  const int need = (Wmax + kBlock - 1) / kBlock;
-  if (need > 32) { set_error_msg("piso_multi_bicgstab_ilu: nx > 8191 not supported"); return PISO_ERR_INVALID_ARG; }
-
-  const int look0 = ntot < 32768 ? 1 : 2;                    // first host look (tiny systems - the lid-driven cavity converges in one iteration: a second one is 13 launches for nothing)
-  {
-    int* d = tl_bi_dispatch;
-    for (int i = 0; i < BD_COUNT; ++i) d[i] = 0;
-    d[BD_SIZEOF_T] = (int)sizeof(T); d[BD_R] = g.R; d[BD_BANDS_U] = nb0; d[BD_BANDS_V] = nb1; d[BD_BLOCKS] = gv + ge;
-    d[BD_TRANSPOSE] = transpose & 3; d[BD_SLAB] = slab ? 1 : 0; d[BD_LOOK0] = look0;
-    tl_bi_dispatch_n = BD_COUNT;                             // (E and the LDS forms: launch_factor / launch_sweeps; the rest as the solve goes)
-  }
-  bi_init_scalars<T><<<1, 256, 0, stream>>>(a);
-  bi_convert<T><<<grid_v, kBlock, 0, stream>>>(a, val, rowptr, col, x0, transpose & 3);
-  if (slab && rccl) { const int rc = comm_rccl_allreduce_i32(pc, a.flags, 2, stream); if (rc != PISO_OK) return rc; }   // (sums: non-zero = set)
-  else if (slab) bi_flags_allreduce<T><<<1, 64, 0, stream>>>(a, next_seq());
-  if (need <= 1) launch_factor<T, 1>(a, grid_b, stream);
-  else if (need <= 2) launch_factor<T, 2>(a, grid_b, stream);
-  else if (need <= 3) launch_factor<T, 3>(a, grid_b, stream);             // (W = nx + 1 with nx a power of two: 2^k / 256 + 1)
-  else if (need <= 4) launch_factor<T, 4>(a, grid_b, stream);
-  else if (need <= 5) launch_factor<T, 5>(a, grid_b, stream);
-  else if (need <= 8) launch_factor<T, 8>(a, grid_b, stream);
-  else if (need <= 9) launch_factor<T, 9>(a, grid_b, stream);
-  else if (need <= 16) launch_factor<T, 16>(a, grid_b, stream);
-  else launch_factor<T, 32>(a, grid_b, stream);
-  PISO_LAUNCH_CHECK();
-
-  auto precond = [&](const T* in, T* out, int fold, int fuse_p) {       // (fold: scalar stages the blocks of the forward sweep apply first)
-    BiArgs<T> aL = next(fold, false);
-    aL.fuse_p = fuse_p;
-    const BiArgs<T> aU = next(0, false);
-    if (need <= 1) launch_sweeps<T, 1>(aL, aU, grid_b, in, out, stream);
-    else if (need <= 2) launch_sweeps<T, 2>(aL, aU, grid_b, in, out, stream);
-    else if (need <= 3) launch_sweeps<T, 3>(aL, aU, grid_b, in, out, stream);
-    else if (need <= 4) launch_sweeps<T, 4>(aL, aU, grid_b, in, out, stream);
-    else if (need <= 5) launch_sweeps<T, 5>(aL, aU, grid_b, in, out, stream);
-    else if (need <= 8) launch_sweeps<T, 8>(aL, aU, grid_b, in, out, stream);
-    else if (need <= 9) launch_sweeps<T, 9>(aL, aU, grid_b, in, out, stream);
-    else if (need <= 16) launch_sweeps<T, 16>(aL, aU, grid_b, in, out, stream);
-    else launch_sweeps<T, 32>(aL, aU, grid_b, in, out, stream);
-  };
-  // Scalar stages folded into their consumers (folded_scalars) on one GPU: 14 -> 9 launches per iteration.  Every block of a vector
-  // kernel re-reads the partial records in passing (<= 16 KB, L2-resident); at 2048^2 the five launches saved are worth 2.5 % of the
-  // iteration (606 -> 590 us, round 5), more on smaller grids.  Option bicg_fold: 0 never.
-  const bool fold_ok = !slab && opt(OPT_BICG_FOLD) != 0;
-  auto F = [&](int stage) -> int { return fold_ok ? stage + 1 : 0; };
-  // p = r + beta (p - omega v) inside the forward sweep of p_hat (BiArgs::fuse_p): 9 -> 8 launches per iteration.  Option bicg_fuse_p 0: never.
-  const int fuse_p = opt(OPT_BICG_FUSE_P) != 0;
-  tl_bi_dispatch[BD_FOLD] = fold_ok ? 1 : 0;
-  tl_bi_dispatch[BD_FUSE_P] = fuse_p;
-
-  BiHost<T> host;
-  auto fetch = [&]() -> int {
-    tl_bi_dispatch[BD_HOST_LOOKS] += 1;
-    PISO_HIP_CHECK(hipMemcpyAsync(host.sc, scbuf0 + 2 * cur, 2 * sizeof(CompScalars<T>), hipMemcpyDeviceToHost, stream));
-    PISO_HIP_CHECK(hipMemcpyAsync(host.flags, a.flags, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
-    PISO_HIP_CHECK(hipStreamSynchronize(stream));
-    return PISO_OK;
-  };
-
-  int failed_mask = 0;      // components that already used their one restart and failed again
-  bool pattern_checked = false;
-  for (int restart = 0; restart < 2; ++restart) {
-    tl_bi_dispatch[BD_PASSES] = restart + 1;
-    // r = b - B x, rh = r, p = v = 0, ||r|| test, first rho / beta
-    { const int rc = halo(a.x); if (rc != PISO_OK) return rc; }
-    bi_residual_init<T><<<grid_v, kBlock, 0, stream>>>(next(0, true));
-    { const int rc = scalar(ST_INIT); if (rc != PISO_OK) return rc; }
-    PISO_LAUNCH_CHECK();
-    int it = 0, look = look0;
-    bool all_done = false;
-    while (it < max_it && !all_done) {
-      // iterations between host looks: 2, 2, 4, 8, 16, 16, ... - a solve of 3 iterations (the 2048^2 benchmark) still stops at
-      // once, a solve of 100 (lid-driven cavity) synchronises 9 times instead of 50; launches of a converged component return early
-      const int chunk = (max_it - it) < look ? (max_it - it) : look;
-      if (look < 2) look = 2; else if (it >= 4 && look < 16) look *= 2;
-      for (int q = 0; q < chunk; ++q, ++it) {
-        // (folded: the ||r|| test that ended the iteration before - inside a chunk nobody else has applied it yet - then rho / beta)
-        int fold_p = 0;
-        if (it > 0) {
-          if (fold_ok) fold_p = q > 0 ? (F(ST_CHECK_R) | (F(ST_RHO_BETA) << 4)) : F(ST_RHO_BETA);
-          else { const int rc = scalar(ST_RHO_BETA); if (rc != PISO_OK) return rc; }
-        }
-        if (fuse_p) precond(a.p, a.ph, fold_p, 1);
-        else {
-          bi_update_p<T><<<grid_v, kBlock, 0, stream>>>(next(fold_p, false));
-          precond(a.p, a.ph, 0, 0);
-        }
-        { const int rc = spmv(0, a.ph, a.v); if (rc != PISO_OK) return rc; }
-        if (!fold_ok) { const int rc = scalar(ST_ALPHA); if (rc != PISO_OK) return rc; }
-        bi_update_xr<T, 0><<<grid_v, kBlock, 0, stream>>>(next(F(ST_ALPHA), true));
-        if (!fold_ok) { const int rc = scalar(ST_CHECK_S); if (rc != PISO_OK) return rc; }
-        precond(a.r, a.sh, F(ST_CHECK_S), 0);
-        { const int rc = spmv(1, a.sh, a.t); if (rc != PISO_OK) return rc; }
-        if (!fold_ok) { const int rc = scalar(ST_OMEGA); if (rc != PISO_OK) return rc; }
-        bi_update_xr<T, 1><<<grid_v, kBlock, 0, stream>>>(next(F(ST_OMEGA), true));
-        if (!fold_ok || q == chunk - 1) { const int rc = scalar(ST_CHECK_R); if (rc != PISO_OK) return rc; }   // (the host looks at it)
-      }
-      PISO_LAUNCH_CHECK();
-      { const int rc = fetch(); if (rc != PISO_OK) return rc; }
-      if (!pattern_checked) {
-        pattern_checked = true;
-        if (host.flags[0]) {
-          set_error_msg("piso_multi_bicgstab_ilu: CSR input is not a 5-point staggered-grid matrix");
-          return PISO_ERR_UNSUPPORTED_PATTERN;
-        }
-      }
-      all_done = host.sc[0].done && host.sc[1].done;
-    }
-    if (max_it == 0 || !pattern_checked) { const int rc = fetch(); if (rc != PISO_OK) return rc; }
-    // failure test per component (:392-407): ||r|| > 100 tol or NaN -> x = 0 and one more pass from x = 0
-    int fail_now = 0;
-    for (int c = 0; c < 2; ++c) {
-      const T nrm = host.sc[c].nrm;
-      if (nrm > (T)tol * 100 || nrm != nrm) fail_now |= 1 << c;
-    }
-    if (!fail_now) break;
-    bi_zero_x<T><<<grid_v, kBlock, 0, stream>>>(next(0, false), fail_now);
-    if (restart == 0) {
-      bi_set_done<T><<<1, 64, 0, stream>>>(next(0, false), !(fail_now & 1), !((fail_now >> 1) & 1));
-    } else {
-      failed_mask = fail_now;
-    }
-  }
-  tl_bi_dispatch[BD_FAILED_MASK] = failed_mask;
-  if (slab && !rccl) {
-    int herr = 0;
-    peer_agree_on_error<><<<1, 64, 0, stream>>>(bp.pv, pc->err, ++pc->seq_ar);      // every rank returns the same status
-    PISO_HIP_CHECK(hipMemcpyAsync(&herr, pc->err, sizeof(int), hipMemcpyDeviceToHost, stream));
-    PISO_HIP_CHECK(hipStreamSynchronize(stream));
-    if (herr) {
-      PISO_HIP_CHECK(hipMemsetAsync(pc->err, 0, sizeof(int), stream));
-      set_error_msg("piso_multi_bicgstab_ilu_slab: a wait on a peer's mailbox gave up (peer process gone or not running?)");
-      return PISO_ERR_HIP;
-    }
-  }
+  BiRun<T> run(pl, stream, pc);
+  BiArgs<T>& a = run.a;
+  a.g = pl.g; a.M = M; a.rhs = rhs; a.x = x_out; a.tol = tol; a.nparts = pl.nparts;
+  for (int c = 0; c < 2; ++c) { a.rb[c] = pl.rb[c]; a.re[c] = pl.re[c]; a.bb[c] = pl.bb[c]; a.be[c] = pl.be[c]; }
+  { const int rc = run.bind(ws, ws_bytes, ntot); if (rc != PISO_OK) return rc; }
+  if (pc) { const int rc = run.link_slabs(); if (rc != PISO_OK) return rc; }
+  record_dispatch(pl, sizeof(T), max_it);
+  { const int rc = run.setup(val, rowptr, col, x0); if (rc != PISO_OK) return rc; }
+  { const int rc = run.solve(tol, max_it); if (rc != PISO_OK) return rc; }
+  if (pl.slab && !pl.rccl) { const int rc = run.agree(); if (rc != PISO_OK) return rc; }
   PISO_HIP_CHECK(hipStreamSynchronize(stream));
-  if (host.flags[1] && warning) {
+  if (run.host.flags[1] && warning) {
     const uint8_t one = 1;
     PISO_HIP_CHECK(hipMemcpyAsync(warning, &one, 1, hipMemcpyHostToDevice, stream));
     PISO_HIP_CHECK(hipStreamSynchronize(stream));
   }
-  if (iterations_out) { iterations_out[0] = host.sc[0].it_count; iterations_out[1] = host.sc[1].it_count; }
+  if (iterations_out) { iterations_out[0] = run.host.sc[0].it_count; iterations_out[1] = run.host.sc[1].it_count; }
   return PISO_OK;
 }
 
@@ -1483,7 +1450,7 @@ static int csr_matvec_impl(const float* csr_val, const int* csr_rowptr, const in
     set_error_msg("piso_csr_matvec_f32: invalid argument");
     return PISO_ERR_INVALID_ARG;
   }
-  const Geo g = make_geo(nx, ny, 8);
+  const Geo g = make_geo(nx, ny);
   const RowMap M = make_row_map(slab, nx, ny, periodic_x ? 1 : 0, periodic_y ? 1 : 0);
   const FaceWin fw = face_window(M);                       // component-local row ranges (whole components on one GPU)
   const int lo0 = fw.u_lo, hi0 = fw.u_lo + fw.cu, lo1 = fw.v_lo - g.n[0], hi1 = lo1 + fw.cv;

@@ -1,6 +1,6 @@
 """Which kernel instances does an ILU(0)-BiCGStab solve run, and is every instance, band geometry and edge the driver can pick right?
 
-One call of piso_multi_bicgstab_ilu_* picks (csrc/bicgstab.hip: bi_solve, make_geo, launch_factor, launch_sweeps)
+One call of piso_multi_bicgstab_ilu_* picks (csrc/bicgstab_dispatch.h: bi_plan, the one place the driver bi_solve of csrc/bicgstab.hip decides in)
   E       row elements per thread of the factorisation and the sweeps, from need = ceil((nx + 1) / 256): 1, 2, 3, 4, 5, 8, 9, 16, 32
   LDS     bi_sweep_lds / bi_factor_lds instead of bi_sweep / bi_factor where they exist (float E = 5, 8, 9, 16; double E = 5, 8, 9) and option
           bicg_sweep_lds is not 0
@@ -44,7 +44,7 @@ f32, f64 = np.float32, np.float64
 CASES = ("periodic", "xper_ywall", "cavity", "spatial_ml")
 REGIME = {"easy": dict(cfl=0.5, viscosity=1e-2), "mid": dict(cfl=2.0, viscosity=0.1), "hard": dict(cfl=6.0, viscosity=0.5)}
 E_LADDER = (1, 2, 3, 4, 5, 8, 9, 16, 32)
-# (sizeof T, E) that have bi_sweep_lds / bi_factor_lds instances: kSweepLds - four (factor: five) staged rows of E * 256 + E * 8 elements in 96 KB
+# (sizeof T, E) that have bi_sweep_lds / bi_factor_lds instances: bi_lds_instance - four (factor: five) staged rows of E * 256 + E * 8 elements in 96 KB
 LDS_FORMS = {(4, 5), (4, 8), (4, 9), (4, 16), (8, 5), (8, 8), (8, 9)}
 K_DEFAULT = (1, 2, 3, 5, 7)           # 7: past the first doubling of the look cadence (looks after 2, 4, 6 / 1, 3, 5, 7 iterations)
 
@@ -192,7 +192,7 @@ def done_at(h, tol):
 
 
 def expected_looks(look0, max_it, passes):
-    """Host fetches of the scalar record, restated from bi_solve: passes = per pass the iteration at which each component was done (None:
+    """Host fetches of the scalar record, restated from the driver (csrc/bicgstab.hip BiRun::pass): passes = per pass the iteration at which each component was done (None:
     never).  A chunk of `look` iterations, then a fetch; look: look0, then 2, and doubling up to 16 from iteration 4 on."""
     looks = 0
     for done in passes:
@@ -476,7 +476,7 @@ def test_csr_matvec_over_the_table_shapes(rid, transpose):
 
 # ------------------------------------------------------------------------------------------------------------------ without a card
 def restated_record(r):
-    """The dispatch rules of bi_solve / make_geo in plain Python, from the row's grid and knobs alone."""
+    """The dispatch rules of bi_plan (csrc/bicgstab_dispatch.h) in plain Python, from the row's grid and knobs alone."""
     ny, nx, band = r["ny"], r["nx"], r["band"]
     need = -(-(nx + 1) // 256)
     E = min(e for e in E_LADDER if e >= need)
