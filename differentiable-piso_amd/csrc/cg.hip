@@ -1,7 +1,7 @@
 // Host driver of the single-GPU pressure CG (kernels: cg_kernels.h).  See cg_kernels.h for the design.
 #include <atomic>
 #include "cg_kernels.h"
-#include "cg_dispatch.h"
+#include "cg_driver.h"
 #include "cg_tiny.h"
 #include "options.h"
 #include <cstdio>
@@ -83,18 +83,37 @@ static bool padded_dims(int nx, int ny, int per_x, int per_y, int elem, int* nxp
   return true;
 }
 
+// The workspace of a solve on n cells (of the padded grid, if `padded`), in this order.  cg_workspace_bytes counts it.
+template <typename T>
+struct CgCarve { T *cC, *oT; float* oF; int* flags; T *b_pad, *x_pad; unsigned* persist_ws; };
+template <typename T>
+static CgCarve<T> cg_carve(Arena& ar, size_t n, bool padded, CgArgs<T>& a) {
+  CgCarve<T> c;
+  c.cC = ar.take<T>(n);
+  c.oT = ar.take<T>(4 * n);
+  c.oF = ar.take<float>(4 * n);
+  c.flags = ar.take<int>(4);
+  c.b_pad = padded ? ar.take<T>(n) : nullptr;
+  c.x_pad = padded ? ar.take<T>(n) : nullptr;
+  a.r = ar.take<T>(n); a.z = ar.take<T>(n); a.p[0] = ar.take<T>(n); a.p[1] = ar.take<T>(n);
+  a.zp[0] = ar.take<T>(n); a.zp[1] = ar.take<T>(n);
+  a.partsA = ar.take<T>(3 * kMaxPartials); a.partsB = ar.take<T>(3 * kMaxPartials); a.partsS = ar.take<T>(kMaxPartials);
+  a.scal = ar.take<T>(SC_COUNT);
+  a.state = ar.take<CgState>(2);
+  c.persist_ws = ar.take<unsigned>(kPersistWsWordsAll);
+  return c;
+}
+
+// (an upper bound: the periodicity is not known here, and periodic grids are never padded.  A grid that may be padded has always been
+// advertised as the plain carve on THREE times its padded cells - more than its two padded copies of b and x take - and stays so.)
 template <typename T>
 static size_t cg_workspace_bytes(int nx_in, int ny_in) {
   int nx = nx_in, ny = ny_in;
-  const bool padded = padded_dims(nx_in, ny_in, 0, 0, (int)sizeof(T), &nx, &ny);   // (an upper bound: periodic grids are never padded)
-  const size_t n = (size_t)nx * ny + (padded ? 2 * (size_t)nx * ny : 0);             // + padded copies of b and x
-  size_t b = 0;
-  b += 11 * align_up(n * sizeof(T), 256);                // diag + 4 off-diagonal arrays (T) + r, z, p0, p1 + the two z' perimeter buffers
-  b += align_up(4 * n * sizeof(float), 256) + 256;        // float copy of the off-diagonals + flag
-  b += 3 * align_up(3 * kMaxPartials * sizeof(T), 256);
-  b += align_up(SC_COUNT * sizeof(T), 256) + align_up(2 * sizeof(CgState), 256) + 512;
-  b += align_up(kPersistWsWordsAll * sizeof(unsigned), 256);  // exchange records of the persistent kernel
-  return b + 4096;
+  const bool padded = padded_dims(nx_in, ny_in, 0, 0, (int)sizeof(T), &nx, &ny);
+  Arena ar = counting_arena();
+  CgArgs<T> a;
+  cg_carve<T>(ar, (padded ? 3 : 1) * (size_t)nx * ny, false, a);
+  return counted_bytes(ar);
 }
 
 // The calling thread's dispatch record (fields: include/piso_hip.h).  One workgroup (cg_tiny.h): path 0 / 1, no tiling, no plan;
@@ -214,160 +233,140 @@ static int poll_batch(size_t n) {
   return batch < 10 ? 10 : (batch > 200 ? 200 : batch);
 }
 
-// returns PISO_OK, an error, or kPersistRetry: a persistent segment failed (an exchange gave up: some workgroups were not resident -
-// another kernel or process holds CUs; or the true-residual check) and its state is unusable -> the caller runs the whole solve again
-// with allow_persist = false: the two-kernel path needs no co-residency
+// The one-GPU link of the iteration (cg_driver.h: cg_iterate): single launches, no halo rows.  Its own: the events around sampled
+// NORMAL K1 / K2 launches, the host's looks (one batch behind on the two-kernel path; after a persistent segment, deferred while the
+// segments are short), the XCD map, the per-phase timing, the true-residual check, the dispatch record.
 template <typename T, typename CT, int V, bool RECON>
-static int cg_run(CgArgs<T> a, unsigned* persist_ws, bool symmetric, float accuracy, int max_iterations, int rank_deficient, int reset, int fixed,
-                  int* iterations_out, float* kernel_ms_out, hipStream_t stream, bool allow_persist) {
-  const size_t n = (size_t)a.nx * a.ny;
-  const CgTiling tile = cg_tile(a, V, opt(OPT_CG_RPW), opt(OPT_CG_MAXBLOCKS));                   // tuning knobs
-  const int g1 = tile.g1, g2 = tile.g2, gflat = tile.gflat;
-  a.accuracy = fixed ? -1.0f : accuracy;                 // fixed-work mode: the test can never succeed
-
-  { const int rc = ensure_poll(); if (rc != PISO_OK) return rc; }
-  const bool prof = (kernel_ms_out != nullptr) || g_prof.enabled;
-  EventPool& ep = tl_events;
-  if (prof) { const int rc = ensure_events(ep); if (rc != PISO_OK) return rc; }
-  ep.used[0] = ep.used[1] = 0;
-  const int prof_stride = g_prof.stride > 0 ? g_prof.stride : 8;
-
-  cg_init<T><<<gflat, kBlock, 0, stream>>>(a, rank_deficient);
-  PISO_LAUNCH_CHECK();
-
-  const int batch = poll_batch(n);
-  int sv = 0, polls = 0, stop_it = -1;
-  const int total = fixed ? fixed : max_iterations;
-  bool finished = false;
-  bool pending = false;                                  // x still lacks alpha_k p_k of the last executed iteration
-  int k_last = -1;
-  // ---- persistent segments: the plan, confirmed by the occupancy of the instance it names (cg_dispatch.h)
-  PersistPlan plan = persist_plan(PersistQuery{a.nx, a.ny, V, a.per_y, a.nx_true != 0, sizeof(T), sizeof(CT), RECON, symmetric, false, tl_poll.cus,
-                                               opt(OPT_CG_PERSIST), opt(OPT_CG_PERSIST_R), opt(OPT_CG_PERSIST_HALF), opt(OPT_CG_PERSIST_NQ),
-                                               opt(OPT_CG_XCD_LOCAL), g_xcd_local_failed, allow_persist});
+struct GpuLink {
+  CgArgs<T> a;
+  hipStream_t stream;
+  bool fixed, prof;
+  CgTiling tile;
+  PersistPlan plan;                                      // confirmed by the occupancy of the instance it names (cg_dispatch.h)
   PersistCtl pc;
-  { const int rc = persist_prepare<T, CT, RECON, false>(plan, tl_poll.cus, pc, persist_ws, stream); if (rc != PISO_OK) return rc; }
   PersistTiming timing;
-  if (plan.R && kPersistDiag && opt_on(OPT_CG_PERSIST_TIMING)) {
-    PISO_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&timing.ticks), 12 * plan.launch_grid * sizeof(unsigned long long)));
-    PISO_HIP_CHECK(hipMemsetAsync(timing.ticks, 0, 12 * plan.launch_grid * sizeof(unsigned long long), stream));
-    pc.timing = timing.ticks;
-  }
-  record_dispatch(plan.R ? 3 : 2, sizeof(T), sizeof(CT), 0, V, RECON, symmetric, &tile, &plan, !allow_persist);
-  const int seg_len = persist_segment_len(n, opt(OPT_CG_SEGMENT));
-  hipEvent_t* seg_ev = tl_poll.seg_ev;
-  if (plan.R && prof && !seg_ev[0]) { PISO_HIP_CHECK(hipEventCreate(&seg_ev[0])); PISO_HIP_CHECK(hipEventCreate(&seg_ev[1])); }
+  int seg_len, batch, prof_stride, polls = 0, unsynced = 0;
+  bool sample = false;                                   // events around this iteration's K1 / K2: sampled NORMAL iterations only
   SegmentTimes seg;
-  int segments_run = 0, unsynced = 0;
-  for (int k = 0; k < total && !finished; ++k) {
-    const bool is_reset = !fixed && ((k + 1) % reset == 0);
-    if (plan.R && k > 0 && !is_reset) {
-      // run NORMAL iterations [k, ke) in one launch: up to the next reset iteration / the end / one segment length
-      int ke = total;
-      if (!fixed) { const int next_reset = ((k + 1 + reset - 1) / reset) * reset - 1; if (next_reset < ke) ke = next_reset; }
-      if (ke > k + seg_len) ke = k + seg_len;
-      if (ke > k) {
-        if (prof) PISO_HIP_CHECK(hipEventRecord(seg_ev[0], stream));
-        { const int rc = persist_launch<T, CT, RECON, false>(plan, a, pc, g_persist_launches.fetch_add(1, std::memory_order_relaxed), k, ke, sv, pending, NoSlab{}, stream);
-          if (rc != PISO_OK) return rc; }
-        if (prof) PISO_HIP_CHECK(hipEventRecord(seg_ev[1], stream));
-        // Short segments (frequent residual resets: the reference's default residual_reset = 10 leaves 9 iterations between two
-        // resets) are not worth a host round trip each: the host looks again after ~250 iterations.  Everything queued behind a
-        // converged or failed segment returns at once (every kernel checks the state record first), the error flag is sticky.
-        const bool defer = !prof && ke - k <= 32 && unsynced + (ke - k) <= 256 && ke < total;
-        unsynced = defer ? unsynced + (ke - k) : 0;
-        if (!defer) {
-          PISO_HIP_CHECK(hipMemcpyAsync(&tl_poll.pinned[0], &a.state[0], sizeof(CgState), hipMemcpyDeviceToHost, stream));
-          int herr = 0;
-          PISO_HIP_CHECK(hipMemcpyAsync(&herr, pc.err, sizeof(int), hipMemcpyDeviceToHost, stream));
-          PISO_HIP_CHECK(hipStreamSynchronize(stream));
-          if (herr) {                                      // a grid-wide exchange gave up
-            ++g_persist_fallbacks;
-            if (plan.xcd_local) g_xcd_local_failed = true;
-            return kPersistRetry;
-          }
-          if (prof) {
-            // (a solve that converges inside the launch leaves it there: the iterations it RAN count, not the segment's length)
-            const int ran = tl_poll.pinned[0].done ? (tl_poll.pinned[0].iterations - k > 0 ? tl_poll.pinned[0].iterations - k : 0) : ke - k;
-            float t = 0; PISO_HIP_CHECK(hipEventElapsedTime(&t, seg_ev[0], seg_ev[1])); seg.ms += t; seg.iters += ran < ke - k ? ran : ke - k; ++seg.launches;
-          }
-          if (tl_poll.pinned[0].done) { finished = true; stop_it = tl_poll.pinned[0].iterations; }
-        }
-        ++segments_run;
-        k_last = ke - 1;
-        pending = false;                                   // the segment applies every x += alpha p itself
-        k = ke - 1;                                        // the loop increment moves to ke
-        continue;
-      }
-    }
-    const bool sample = prof && (k % prof_stride == prof_stride - 1) && ep.used[0] < EventPool::kMax && !is_reset && k > 0;
-    if (is_reset) {
-      if (pending) { cg_flush_x<T><<<gflat, kBlock, 0, stream>>>(a, k - 1, sv); pending = false; }
-      cg_k1<T, CT, V, RECON><<<g1, kBlock, 0, stream>>>(a, k, MODE_RESET, sv, k > 0 ? 1 : 0, 0);
-      ++sv;
-      cg_reset_residual<T><<<gflat, kBlock, 0, stream>>>(a, sv);
-      cg_k1<T, CT, V, RECON><<<g1, kBlock, 0, stream>>>(a, k, MODE_INIT, sv, 0, 0);
-    } else if (k == 0) {
-      cg_k1<T, CT, V, RECON><<<g1, kBlock, 0, stream>>>(a, k, MODE_INIT, sv, 0, 0);
-    } else {
-      if (sample) PISO_HIP_CHECK(hipEventRecord(ep.start[0][ep.used[0]], stream));
-      cg_k1<T, CT, V, RECON><<<g1, kBlock, 0, stream>>>(a, k, MODE_NORMAL, sv, 1, pending ? 1 : 0);
-      if (sample) PISO_HIP_CHECK(hipEventRecord(ep.stop[0][ep.used[0]++], stream));
-      ++sv;
-    }
-    if (sample) PISO_HIP_CHECK(hipEventRecord(ep.start[1][ep.used[1]], stream));
-    cg_k2<T, V><<<g2, kBlock, 0, stream>>>(a, k, sv);
-    if (sample) PISO_HIP_CHECK(hipEventRecord(ep.stop[1][ep.used[1]++], stream));
+  EventPool& ep = tl_events;
+
+  // everything before the first iteration: tiling, cg_init, the plan of the persistent part, the dispatch record
+  int start(unsigned* persist_ws, bool symmetric, int rank_deficient, bool allow_persist) {
+    const size_t n = (size_t)a.nx * a.ny;
+    tile = cg_tile(a, V, opt(OPT_CG_RPW), opt(OPT_CG_MAXBLOCKS));                   // tuning knobs
+    PISO_TRY(ensure_poll());
+    if (prof) PISO_TRY(ensure_events(ep));
+    ep.used[0] = ep.used[1] = 0;
+    prof_stride = g_prof.stride > 0 ? g_prof.stride : 8;
+    cg_init<T><<<tile.gflat, kBlock, 0, stream>>>(a, rank_deficient);
     PISO_LAUNCH_CHECK();
-    pending = true;
-    k_last = k;
-    if (!fixed && ((k + 1) % batch == 0) && k + 1 < total) {
-      const int slot = polls & 1;
-      PISO_HIP_CHECK(hipMemcpyAsync(&tl_poll.pinned[slot], &a.state[sv & 1], sizeof(CgState), hipMemcpyDeviceToHost, stream));
-      PISO_HIP_CHECK(hipEventRecord(tl_poll.ev[slot], stream));
-      if (polls > 0) {                                   // look at the PREVIOUS poll while this batch is already queued
-        const int r = inspect_poll((polls - 1) & 1, &stop_it);
-        if (r < 0) return PISO_ERR_HIP;
-        if (r > 0) finished = true;
-      }
-      ++polls;
+    batch = poll_batch(n);
+    plan = persist_plan(PersistQuery{a.nx, a.ny, V, a.per_y, a.nx_true != 0, sizeof(T), sizeof(CT), RECON, symmetric, false, tl_poll.cus,
+                                     opt(OPT_CG_PERSIST), opt(OPT_CG_PERSIST_R), opt(OPT_CG_PERSIST_HALF), opt(OPT_CG_PERSIST_NQ),
+                                     opt(OPT_CG_XCD_LOCAL), g_xcd_local_failed, allow_persist});
+    PISO_TRY((persist_prepare<T, CT, RECON, false>(plan, tl_poll.cus, pc, persist_ws, stream)));
+    if (plan.R && kPersistDiag && opt_on(OPT_CG_PERSIST_TIMING)) {
+      PISO_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&timing.ticks), 12 * plan.launch_grid * sizeof(unsigned long long)));
+      PISO_HIP_CHECK(hipMemsetAsync(timing.ticks, 0, 12 * plan.launch_grid * sizeof(unsigned long long), stream));
+      pc.timing = timing.ticks;
     }
+    record_dispatch(plan.R ? 3 : 2, sizeof(T), sizeof(CT), 0, V, RECON, symmetric, &tile, &plan, !allow_persist);
+    seg_len = persist_segment_len(n, opt(OPT_CG_SEGMENT));
+    hipEvent_t* seg_ev = tl_poll.seg_ev;
+    if (plan.R && prof && !seg_ev[0]) { PISO_HIP_CHECK(hipEventCreate(&seg_ev[0])); PISO_HIP_CHECK(hipEventCreate(&seg_ev[1])); }
+    return PISO_OK;
   }
-  // the direction of the last executed iteration (a converged solve was already flushed by the K1 that detected it)
-  if (pending && k_last >= 0) cg_flush_x<T><<<gflat, kBlock, 0, stream>>>(a, k_last, sv);
-  // Final look.  (A success of the test that belongs to the very last iteration is not evaluated: the reference would
-  // report iterations == total for it, which is what an unfinished loop reports as well.)
-  if (!fixed && !finished) {
-    const int slot = polls & 1;
-    PISO_HIP_CHECK(hipMemcpyAsync(&tl_poll.pinned[slot], &a.state[sv & 1], sizeof(CgState), hipMemcpyDeviceToHost, stream));
-    PISO_HIP_CHECK(hipEventRecord(tl_poll.ev[slot], stream));
-    const int r = inspect_poll(slot, &stop_it);
-    if (r < 0) return PISO_ERR_HIP;
-    if (r > 0) finished = true;
-  }
-  PISO_HIP_CHECK(hipStreamSynchronize(stream));
-  if (opt(OPT_CG_XCD_MAP) == 1) {
-    tl_xcd_map_n = 0;
-    if (segments_run > 0 && !plan.xcd_local && plan.grid <= kPersistMaxGrid) {
-      PISO_HIP_CHECK(hipMemcpy(tl_xcd_map, pc.xcd + kPersistXcdTable, (size_t)plan.grid * sizeof(int), hipMemcpyDeviceToHost));
-      tl_xcd_map_n = plan.grid;
-    }
-  }
-  if (segments_run > 0) {                                  // (segments whose host look was deferred: did one of them give up?)
+
+  bool persistent() const { return plan.R != 0; }
+  int segment(int k, int ke, CgLoop& st) {
+    hipEvent_t* seg_ev = tl_poll.seg_ev;
+    if (prof) PISO_HIP_CHECK(hipEventRecord(seg_ev[0], stream));
+    PISO_TRY((persist_launch<T, CT, RECON, false>(plan, a, pc, g_persist_launches.fetch_add(1, std::memory_order_relaxed), k, ke, st.sv, st.pending, NoSlab{}, stream)));
+    if (prof) PISO_HIP_CHECK(hipEventRecord(seg_ev[1], stream));
+    // Short segments (frequent residual resets: the reference's default residual_reset = 10 leaves 9 iterations between two
+    // resets) are not worth a host round trip each: the host looks again after ~250 iterations.  Everything queued behind a
+    // converged or failed segment returns at once (every kernel checks the state record first), the error flag is sticky.
+    const bool defer = !prof && ke - k <= 32 && unsynced + (ke - k) <= 256 && ke < st.total;
+    unsynced = defer ? unsynced + (ke - k) : 0;
+    if (defer) return PISO_OK;
+    PISO_HIP_CHECK(hipMemcpyAsync(&tl_poll.pinned[0], &a.state[0], sizeof(CgState), hipMemcpyDeviceToHost, stream));
     int herr = 0;
-    PISO_HIP_CHECK(hipMemcpy(&herr, pc.err, sizeof(int), hipMemcpyDeviceToHost));
-    if (herr) { ++g_persist_fallbacks; return kPersistRetry; }
+    PISO_HIP_CHECK(hipMemcpyAsync(&herr, pc.err, sizeof(int), hipMemcpyDeviceToHost, stream));
+    PISO_HIP_CHECK(hipStreamSynchronize(stream));
+    if (herr) {                                          // a grid-wide exchange gave up
+      ++g_persist_fallbacks;
+      if (plan.xcd_local) g_xcd_local_failed = true;
+      return kPersistRetry;
+    }
+    const CgState& hst = tl_poll.pinned[0];
+    if (prof) {
+      // (a solve that converges inside the launch leaves it there: the iterations it RAN count, not the segment's length)
+      const int ran = hst.done ? (hst.iterations - k > 0 ? hst.iterations - k : 0) : ke - k;
+      float t = 0; PISO_HIP_CHECK(hipEventElapsedTime(&t, seg_ev[0], seg_ev[1])); seg.ms += t; seg.iters += ran < ke - k ? ran : ke - k; ++seg.launches;
+    }
+    if (hst.done) { st.finished = true; st.stop_it = hst.iterations; }
+    return PISO_OK;
   }
-  if (segments_run > 0 && sizeof(T) == 8 && !fixed && opt(OPT_CG_VERIFY) != 0) {
-    bool failed = false;
-    { const int rc = verify_residual<T, CT>(a, pc, stream, &failed); if (rc != PISO_OK) return rc; }
-    if (failed) { ++g_verify_failures; ++g_persist_fallbacks; return kPersistRetry; }
+
+  int k1(int k, int mode, int sv, int chk, int pend) {
+    sample = prof && mode == MODE_NORMAL && (k % prof_stride == prof_stride - 1) && ep.used[0] < EventPool::kMax;
+    if (sample) PISO_HIP_CHECK(hipEventRecord(ep.start[0][ep.used[0]], stream));
+    cg_k1<T, CT, V, RECON><<<tile.g1, kBlock, 0, stream>>>(a, k, mode, sv, chk, pend);
+    if (sample) PISO_HIP_CHECK(hipEventRecord(ep.stop[0][ep.used[0]++], stream));
+    return PISO_OK;
   }
-  if (timing.ticks) { const int rc = print_persist_timing(timing.ticks, plan.grid, k_last); if (rc != PISO_OK) return rc; }
-  if (iterations_out) *iterations_out = finished ? stop_it : total;
-  tl_dispatch[DI_SEGMENTS] = segments_run;
-  return prof ? read_profile(ep, seg, kernel_ms_out) : PISO_OK;
-}
+  int k2(int k, int sv) {
+    if (sample) PISO_HIP_CHECK(hipEventRecord(ep.start[1][ep.used[1]], stream));
+    cg_k2<T, V><<<tile.g2, kBlock, 0, stream>>>(a, k, sv);
+    if (sample) PISO_HIP_CHECK(hipEventRecord(ep.stop[1][ep.used[1]++], stream));
+    return PISO_OK;
+  }
+  int flush(int k, int sv) { cg_flush_x<T><<<tile.gflat, kBlock, 0, stream>>>(a, k, sv); return PISO_OK; }
+  int reset_residual(int sv) { cg_reset_residual<T><<<tile.gflat, kBlock, 0, stream>>>(a, sv); return PISO_OK; }
+  int halo(int) { return PISO_OK; }
+
+  // queues a copy of the state record and looks at the PREVIOUS copy while this batch is already queued (now: waits for this one)
+  int poll(CgLoop& st, bool now) {
+    const int slot = polls & 1;
+    PISO_HIP_CHECK(hipMemcpyAsync(&tl_poll.pinned[slot], &a.state[st.sv & 1], sizeof(CgState), hipMemcpyDeviceToHost, stream));
+    PISO_HIP_CHECK(hipEventRecord(tl_poll.ev[slot], stream));
+    if (now || polls > 0) {
+      const int r = inspect_poll(now ? slot : (polls - 1) & 1, &st.stop_it);
+      if (r < 0) return PISO_ERR_HIP;
+      if (r > 0) st.finished = true;
+    }
+    ++polls;
+    return PISO_OK;
+  }
+  int look(int k, CgLoop& st) { return (!fixed && (k + 1) % batch == 0 && k + 1 < st.total) ? poll(st, false) : PISO_OK; }
+
+  int finish(CgLoop& st) {
+    // Final look.  (A success of the test that belongs to the very last iteration is not evaluated: the reference would
+    // report iterations == total for it, which is what an unfinished loop reports as well.)
+    if (!fixed && !st.finished) PISO_TRY(poll(st, true));
+    PISO_HIP_CHECK(hipStreamSynchronize(stream));
+    if (opt(OPT_CG_XCD_MAP) == 1) {
+      tl_xcd_map_n = 0;
+      if (st.segments_run > 0 && !plan.xcd_local && plan.grid <= kPersistMaxGrid) {
+        PISO_HIP_CHECK(hipMemcpy(tl_xcd_map, pc.xcd + kPersistXcdTable, (size_t)plan.grid * sizeof(int), hipMemcpyDeviceToHost));
+        tl_xcd_map_n = plan.grid;
+      }
+    }
+    if (st.segments_run > 0) {                           // (segments whose host look was deferred: did one of them give up?)
+      int herr = 0;
+      PISO_HIP_CHECK(hipMemcpy(&herr, pc.err, sizeof(int), hipMemcpyDeviceToHost));
+      if (herr) { ++g_persist_fallbacks; return kPersistRetry; }
+    }
+    if (st.segments_run > 0 && sizeof(T) == 8 && !fixed && opt(OPT_CG_VERIFY) != 0) {
+      bool failed = false;
+      PISO_TRY((verify_residual<T, CT>(a, pc, stream, &failed)));
+      if (failed) { ++g_verify_failures; ++g_persist_fallbacks; return kPersistRetry; }
+    }
+    if (timing.ticks) PISO_TRY(print_persist_timing(timing.ticks, plan.grid, st.k_last));
+    tl_dispatch[DI_SEGMENTS] = st.segments_run;
+    return PISO_OK;
+  }
+};
 
 // rows of nx elements between arrays of different leading dimensions (padded-grid mode: b in, x out)
 template <typename T>
@@ -438,74 +437,52 @@ static int cg_solve(int nx, int ny, int per_x, int per_y, const T* L, const T* b
   const size_t n = (size_t)nxp * nyp;
   Arena ar(ws, ws_bytes);
   CgArgs<T> a;
-  T* cC = ar.take<T>(n);
-  T* oT = ar.take<T>(4 * n);
-  float* oF = ar.take<float>(4 * n);
-  int* flags = ar.take<int>(4);
-  a.cC = cC;
-  a.b = b; a.x = x_out;
-  T *b_pad = nullptr, *x_pad = nullptr;
-  if (padded) { b_pad = ar.take<T>(n); x_pad = ar.take<T>(n); a.b = b_pad; a.x = x_pad; }
-  a.r = ar.take<T>(n); a.z = ar.take<T>(n); a.p[0] = ar.take<T>(n); a.p[1] = ar.take<T>(n);
-  a.zp[0] = ar.take<T>(n); a.zp[1] = ar.take<T>(n);
-  a.partsA = ar.take<T>(3 * kMaxPartials); a.partsB = ar.take<T>(3 * kMaxPartials); a.partsS = ar.take<T>(kMaxPartials);
-  a.scal = ar.take<T>(SC_COUNT);
-  a.state = ar.take<CgState>(2);
-  unsigned* persist_ws = ar.take<unsigned>(kPersistWsWordsAll);
+  const CgCarve<T> c = cg_carve<T>(ar, n, padded, a);
+  a.cC = c.cC;
+  a.b = padded ? c.b_pad : b; a.x = padded ? c.x_pad : x_out;
   a.nx = nxp; a.ny = nyp; a.per_x = per_x; a.per_y = per_y;
   a.nx_true = padded ? nx : 0; a.ny_true = padded ? ny : 0; a.ncells = padded ? (double)n_true : 0.0;
-  a.ntx = a.nty = a.rows_per_wave = 0; a.nA = a.nB = 0; a.accuracy = accuracy;
+  a.ntx = a.nty = a.rows_per_wave = 0; a.nA = a.nB = 0;
+  a.accuracy = fixed ? -1.0f : accuracy;                   // fixed-work mode: the test can never succeed
   a.gA = nullptr; a.gB = nullptr;
   a.nt = 0;
   if (opt(OPT_CG_NT) > 0) a.nt = opt(OPT_CG_NT);
   if (!ar.ok()) { set_error_msg("piso_cg_solve: workspace too small"); return PISO_ERR_INVALID_ARG; }
 
-  PISO_HIP_CHECK(hipMemsetAsync(flags, 0, 4 * sizeof(int), stream));
+  PISO_HIP_CHECK(hipMemsetAsync(c.flags, 0, 4 * sizeof(int), stream));
   cg_zero_partials<T><<<(3 * kMaxPartials + 255) / 256, 256, 0, stream>>>(a.partsA, a.partsB, a.partsS);
   const int gs = grid_for((long long)n_true, kBlock * 4);
   if (padded) {                                             // zero coefficients and a zero right-hand side keep the padding at zero
-    PISO_HIP_CHECK(hipMemsetAsync(cC, 0, n * sizeof(T), stream));
-    PISO_HIP_CHECK(hipMemsetAsync(oT, 0, 4 * n * sizeof(T), stream));
-    PISO_HIP_CHECK(hipMemsetAsync(oF, 0, 4 * n * sizeof(float), stream));
-    PISO_HIP_CHECK(hipMemsetAsync(b_pad, 0, n * sizeof(T), stream));
-    cg_copy_rows<T><<<gs, kBlock, 0, stream>>>(b, b_pad, nx, ny, nx, nxp);
+    PISO_HIP_CHECK(hipMemsetAsync(c.cC, 0, n * sizeof(T), stream));
+    PISO_HIP_CHECK(hipMemsetAsync(c.oT, 0, 4 * n * sizeof(T), stream));
+    PISO_HIP_CHECK(hipMemsetAsync(c.oF, 0, 4 * n * sizeof(float), stream));
+    PISO_HIP_CHECK(hipMemsetAsync(c.b_pad, 0, n * sizeof(T), stream));
+    cg_copy_rows<T><<<gs, kBlock, 0, stream>>>(b, c.b_pad, nx, ny, nx, nxp);
   }
-  cg_setup_coeffs<T><<<gs, kBlock, 0, stream>>>(L, cC, oT, oF, a.partsS, flags, n_true, nx, ny, per_x, per_y, padded ? nxp : 0, padded ? n : 0);
+  cg_setup_coeffs<T><<<gs, kBlock, 0, stream>>>(L, c.cC, c.oT, c.oF, a.partsS, c.flags, n_true, nx, ny, per_x, per_y, padded ? nxp : 0, padded ? n : 0);
   PISO_LAUNCH_CHECK();
-  // The off-diagonals of the PISO pressure matrix are float32 face coefficients (laplace_op.cu.cc:140-177): stored as
-  // float they are exact and K1 reads 24 instead of 40 coefficient bytes per cell.  Any other input keeps them in T.
   int hflags[3] = {1, 1, 1};
-  {
-    PISO_HIP_CHECK(hipMemcpyAsync(hflags, flags, 3 * sizeof(int), hipMemcpyDeviceToHost, stream));
-    PISO_HIP_CHECK(hipStreamSynchronize(stream));
-  }
-  if (opt_on(OPT_CG_NO_COMPACT)) hflags[0] = hflags[1] = 1;         // tuning / test knob: plain T coefficients
-  if (opt_on(OPT_CG_NO_RECON)) hflags[1] = 1;
-  if (opt_on(OPT_CG_NO_SYM)) hflags[2] = 1;
-  const bool symmetric = !hflags[2];
-  constexpr int VMID = 16 / sizeof(T);
+  PISO_HIP_CHECK(hipMemcpyAsync(hflags, c.flags, 3 * sizeof(int), hipMemcpyDeviceToHost, stream));
+  PISO_HIP_CHECK(hipStreamSynchronize(stream));
+  const CgCoefs coefs = cg_coefs(hflags[0], hflags[1], hflags[2], opt_on(OPT_CG_NO_COMPACT), opt_on(OPT_CG_NO_RECON), opt_on(OPT_CG_NO_SYM));
+  // (compact with fp32 state: trivially exact - the same path, so that the diagonal can be rebuilt there too)
+  if (coefs.compact) { a.oS = c.oF; a.oW = c.oF + n; a.oE = c.oF + 2 * n; a.oN = c.oF + 3 * n; }
+  else { a.oS = c.oT; a.oW = c.oT + n; a.oE = c.oT + 2 * n; a.oN = c.oT + 3 * n; }
   const bool aligned = ((reinterpret_cast<uintptr_t>(a.b) | reinterpret_cast<uintptr_t>(a.x)) & 15) == 0;
-  const bool vec = aligned && (nxp % VMID == 0);
-  int rc = kPersistRetry;
-  // (second attempt: a persistent segment failed - the whole solve again on the two-kernel iteration)
-#define PISO_CG_RUN(CT, V, RECON)                                              \
-  for (int attempt = 0; attempt < 2 && rc == kPersistRetry; ++attempt)         \
-    rc = cg_run<T, CT, V, RECON>(a, persist_ws, symmetric, accuracy, max_iterations, rank_deficient, reset, fixed, iterations_out, kernel_ms_out, stream, attempt == 0)
-  if (!hflags[0]) {                                         // (fp32 state: trivially exact - the same path, so that the diagonal can be rebuilt there too)
-    a.oS = oF; a.oW = oF + n; a.oE = oF + 2 * n; a.oN = oF + 3 * n;
-    if (!hflags[1]) { if (vec) PISO_CG_RUN(float, VMID, true); else PISO_CG_RUN(float, 1, true); }
-    else if (vec) PISO_CG_RUN(float, VMID, false);
-    else PISO_CG_RUN(float, 1, false);
-  } else {
-    a.oS = oT; a.oW = oT + n; a.oE = oT + 2 * n; a.oN = oT + 3 * n;
-    if (vec) PISO_CG_RUN(T, VMID, false);
-    else PISO_CG_RUN(T, 1, false);
-  }
-#undef PISO_CG_RUN
-  if (rc == kPersistRetry) { set_error_msg("piso_cg_solve: persistent segment failed twice"); return PISO_ERR_HIP; }
+  const bool vec = aligned && (nxp % (16 / (int)sizeof(T)) == 0);
+  const bool prof = (kernel_ms_out != nullptr) || g_prof.enabled;
+  const int rc = cg_retry_without_segments("piso_cg_solve", [&](bool allow_persist) {
+    return cg_with_instance<T>(coefs, vec, [&](auto inst) {
+      using I = decltype(inst);
+      GpuLink<T, typename I::CT, I::V, I::RECON> link{a, stream, fixed != 0, prof};
+      PISO_TRY(link.start(c.persist_ws, coefs.symmetric, rank_deficient, allow_persist));
+      PISO_TRY(cg_iterate(link, fixed ? fixed : max_iterations, reset, fixed != 0, iterations_out));
+      return prof ? read_profile(link.ep, link.seg, kernel_ms_out) : PISO_OK;
+    });
+  });
   if (rc != PISO_OK) return rc;
-  if (padded) {                                             // (cg_run has synchronised the stream: x_pad is final)
-    cg_copy_rows<T><<<gs, kBlock, 0, stream>>>(x_pad, x_out, nx, ny, nxp, nx);
+  if (padded) {                                             // (the solve has synchronised the stream: x_pad is final)
+    cg_copy_rows<T><<<gs, kBlock, 0, stream>>>(c.x_pad, x_out, nx, ny, nxp, nx);
     PISO_LAUNCH_CHECK();
     PISO_HIP_CHECK(hipStreamSynchronize(stream));
   }

@@ -24,7 +24,7 @@
 
 #include <vector>
 
-#include "cg_dispatch.h"
+#include "cg_driver.h"
 #include "cg_kernels.h"
 #include "options.h"
 #include "peer.h"
@@ -77,15 +77,15 @@ static int load_rccl() {
   } while (0)
 
 // ------------------------------------------------------------------------------------------------ per-rank context
-template <typename T>
+// (fp64 only: the C ABI has no other slab solve, the mailbox rows hold 8-byte elements)
 struct SlabRank {
-  CgArgs<T> a;          // r, p[], x point at row 0 of buffers that own one halo row below (row -1) and above (row ny)
-  T *rbase, *pbase[2], *xbase;
-  T* g;                 // [12]: gA[0..2], pad, gB[4..6], pad, gS[8..10] (sum |diag|, #not-f32, #not-recon)
-  T* oT; float* oF; T* cC;
+  CgArgs<double> a;     // r, p[], x point at row 0 of buffers that own one halo row below (row -1) and above (row ny)
+  double *rbase, *pbase[2], *xbase;
+  double* g;            // [12]: gA[0..2], pad, gB[4..6], pad, gS[8..10] (sum |diag|, #not-f32, #not-recon)
+  double* oT; float* oF; double* cC;
   int* flags;
-  const T* L;
-  T* x_out;             // owned rows of the caller's output
+  const double* L;
+  double* x_out;        // owned rows of the caller's output
   int rank;             // position in the slab ring
   unsigned* persist_ws; // exchange records + error flag of the persistent kernel
 };
@@ -210,7 +210,6 @@ int comm_rccl_allreduce_i32(PisoComm* pc, int* buf, int count, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------ communication
-template <typename T>
 struct Comm {
   int world;              // slabs in the ring
   bool periodic_y;
@@ -219,45 +218,34 @@ struct Comm {
   bool peer() const { return rccl && rccl->transport == TRANSPORT_PEER; }
 
   // sum `count` values at offset `off` of every rank's g buffer
-  int allreduce(std::vector<SlabRank<T>>& R, int off, int count, hipStream_t s) {
+  int allreduce(std::vector<SlabRank>& R, int off, int count, hipStream_t s) {
     if (peer()) {
-      if constexpr (sizeof(T) == 8) {
-        if (world == 1) return PISO_OK;
-        peer_allreduce<<<1, 64, 0, s>>>(make_view(rccl, periodic_y), reinterpret_cast<double*>(R[0].g) + off, count, ++rccl->seq_ar, rccl->err);
-      } else {
-        set_error_msg("peer transport: fp64 only"); return PISO_ERR_INVALID_ARG;
-      }
+      if (world == 1) return PISO_OK;
+      peer_allreduce<<<1, 64, 0, s>>>(make_view(rccl, periodic_y), R[0].g + off, count, ++rccl->seq_ar, rccl->err);
     } else if (rccl) {
       if (world == 1) return PISO_OK;
-      PISO_NCCL_CHECK(g_rccl.AllReduce(R[0].g + off, R[0].g + off, count, sizeof(T) == 8 ? ncclDouble : ncclFloat, ncclSum,
-                                       rccl->comm, s));
+      PISO_NCCL_CHECK(g_rccl.AllReduce(R[0].g + off, R[0].g + off, count, ncclDouble, ncclSum, rccl->comm, s));
     } else {
-      loop_allreduce<T><<<1, 64, 0, s>>>(R[0].g + off, world, g_stride, count);
+      loop_allreduce<double><<<1, 64, 0, s>>>(R[0].g + off, world, g_stride, count);
     }
     return PISO_OK;
   }
-  // fill the halo rows (row -1 and row ny) of `which` (0: r, 1: x) from the neighbours' edge rows
-  int exchange(std::vector<SlabRank<T>>& R, int which, hipStream_t s) {
+  // fill the halo rows (row -1 and row ny) of `which` (HALO_R, HALO_X) from the neighbours' edge rows
+  int exchange(std::vector<SlabRank>& R, int which, hipStream_t s) {
     const int nx = R[0].a.nx;
-    auto base0 = [&](SlabRank<T>& k) { return which == 0 ? k.a.r : k.a.x; };   // row 0
+    auto base0 = [&](SlabRank& k) { return which == HALO_R ? k.a.r : k.a.x; };   // row 0
     if (peer()) {
-      if constexpr (sizeof(T) == 8) {
-        SlabRank<T>& me = R[0];
-        double* row0 = reinterpret_cast<double*>(base0(me));
-        const int ny = me.a.ny;
-        if (nx > (int)rccl->row_cap) { set_error_msg("peer transport: row longer than the mailbox rows"); return PISO_ERR_INVALID_ARG; }
-        peer_exchange_rows<<<2, kBlock, 0, s>>>(make_view(rccl, periodic_y), row0, row0 + (size_t)(ny - 1) * nx, row0 - nx,
-                                                row0 + (size_t)ny * nx, nx, ++rccl->seq_ex, rccl->err);
-      } else {
-        set_error_msg("peer transport: fp64 only"); return PISO_ERR_INVALID_ARG;
-      }
+      double* row0 = base0(R[0]);
+      const int ny = R[0].a.ny;
+      if (nx > (int)rccl->row_cap) { set_error_msg("peer transport: row longer than the mailbox rows"); return PISO_ERR_INVALID_ARG; }
+      peer_exchange_rows<<<2, kBlock, 0, s>>>(make_view(rccl, periodic_y), row0, row0 + (size_t)(ny - 1) * nx, row0 - nx,
+                                              row0 + (size_t)ny * nx, nx, ++rccl->seq_ex, rccl->err);
     } else if (rccl) {
-      SlabRank<T>& me = R[0];
-      const int ny = me.a.ny, rank = rccl->rank;
+      const int ny = R[0].a.ny, rank = rccl->rank;
       const int lo = (rank > 0) ? rank - 1 : (periodic_y ? world - 1 : -1);
       const int hi = (rank < world - 1) ? rank + 1 : (periodic_y ? 0 : -1);
-      T* row0 = base0(me);
-      const ncclDataType_t dt = sizeof(T) == 8 ? ncclDouble : ncclFloat;
+      double* row0 = base0(R[0]);
+      constexpr ncclDataType_t dt = ncclDouble;
       // Sends and receives between one pair of ranks are matched in issue order, and with 1 or 2 ranks the lower and the
       // upper neighbour are the same peer: every rank issues the UPWARD transfer first, then the DOWNWARD one.
       PISO_NCCL_CHECK(g_rccl.GroupStart());
@@ -268,13 +256,12 @@ struct Comm {
       PISO_NCCL_CHECK(g_rccl.GroupEnd());
     } else {
       for (int r = 0; r < world; ++r) {
-        SlabRank<T>& me = R[r];
-        const int ny = me.a.ny;
+        const int ny = R[r].a.ny;
         const int lo = (r > 0) ? r - 1 : (periodic_y ? world - 1 : -1);
         const int hi = (r < world - 1) ? r + 1 : (periodic_y ? 0 : -1);
-        T* row0 = base0(me);
-        if (lo >= 0) slab_copy_rows<T><<<4, 256, 0, s>>>(base0(R[lo]) + (size_t)(R[lo].a.ny - 1) * nx, row0 - nx, nx);
-        if (hi >= 0) slab_copy_rows<T><<<4, 256, 0, s>>>(base0(R[hi]), row0 + (size_t)ny * nx, nx);
+        double* row0 = base0(R[r]);
+        if (lo >= 0) slab_copy_rows<double><<<4, 256, 0, s>>>(base0(R[lo]) + (size_t)(R[lo].a.ny - 1) * nx, row0 - nx, nx);
+        if (hi >= 0) slab_copy_rows<double><<<4, 256, 0, s>>>(base0(R[hi]), row0 + (size_t)ny * nx, nx);
       }
     }
     return PISO_OK;
@@ -282,166 +269,144 @@ struct Comm {
 };
 
 // ------------------------------------------------------------------------------------------------ driver
-template <typename T>
+// One rank's share of the workspace: n owned cells, nh cells with the two halo rows - in this order.  slab_rank_bytes counts it.
+static void slab_carve(Arena& ar, size_t n, size_t nh, SlabRank& k) {
+  k.cC = ar.take<double>(n); k.oT = ar.take<double>(4 * n); k.oF = ar.take<float>(4 * n);
+  k.flags = ar.take<int>(4);
+  k.rbase = ar.take<double>(nh); k.pbase[0] = ar.take<double>(nh); k.pbase[1] = ar.take<double>(nh); k.xbase = ar.take<double>(nh);
+  CgArgs<double>& a = k.a;
+  a.z = ar.take<double>(n);
+  a.zp[0] = ar.take<double>(n); a.zp[1] = ar.take<double>(n);   // z' perimeters of the persistent kernel (agent-scope accesses only)
+  k.persist_ws = ar.take<unsigned>(kPersistWsWordsAll);
+  a.partsA = ar.take<double>(3 * kMaxPartials); a.partsB = ar.take<double>(3 * kMaxPartials); a.partsS = ar.take<double>(kMaxPartials);
+  a.scal = ar.take<double>(SC_COUNT);
+  a.state = ar.take<CgState>(2);
+}
 static size_t slab_rank_bytes(int nx, int nyl) {
-  const size_t n = (size_t)nx * nyl, nh = (size_t)nx * (nyl + 2);
-  size_t b = 0;
-  b += align_up(n * sizeof(T), 256) * (1 + 4 + 1);          // cC, oT(4), z
-  b += align_up(4 * n * sizeof(float), 256);                 // oF
-  b += align_up(nh * sizeof(T), 256) * 4;                    // r, p0, p1, x with halos
-  b += align_up(n * sizeof(T), 256) * 2;                     // z' perimeter buffers of the persistent kernel
-  b += 3 * align_up(3 * kMaxPartials * sizeof(T), 256);
-  b += 4 * 256 + align_up(16 * sizeof(T), 256);
-  b += align_up(kPersistWsWordsAll * sizeof(unsigned), 256);
-  return b + 4096;
+  Arena ar = counting_arena();
+  SlabRank k;
+  slab_carve(ar, (size_t)nx * nyl, (size_t)nx * (nyl + 2), k);
+  return counted_bytes(ar);
 }
 
 struct SlabPinned { CgState st; int err; int pad[3]; double errsum; };
 static thread_local SlabPinned* tl_slab_pinned = nullptr;
 
-// returns PISO_OK, an error, or kPersistRetry: a persistent segment failed on some rank -> the caller re-initialises the solve and
-// calls again with allow_persist = false
-template <typename T, typename CT, int V, bool RECON>
-static int slab_iterate(std::vector<SlabRank<T>>& R, Comm<T>& comm, float accuracy, int max_iterations, int reset,
-                        int* iterations_out, hipStream_t stream, bool symmetric, bool allow_persist, double global_cells,
-                        unsigned* persist_ws) {
-  const int nloc = (int)R.size();
-  std::vector<int> g1(nloc), g2(nloc), gflat(nloc);
-  for (int q = 0; q < nloc; ++q) {
-    CgArgs<T>& a = R[q].a;
-    const CgTiling tile = cg_tile(a, V, 0, 0);               // (options cg_rpw / cg_maxblocks are the one-GPU driver's)
-    g1[q] = tile.g1; g2[q] = tile.g2; gflat[q] = tile.gflat;
-    a.accuracy = accuracy;
-    a.gA = R[q].g; a.gB = R[q].g + 4;
-  }
-  if (!tl_slab_pinned) PISO_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&tl_slab_pinned), sizeof(SlabPinned), hipHostMallocDefault));
-
-  // ---- persistent segments (peer transport, one rank per process): the NORMAL iterations of the slab run inside
-  // cg_persist1<..., SLAB>; every rank takes the same decision (same shape, same options, failures are all-reduced).  The plan is the
-  // one-GPU driver's (cg_dispatch.h) with full workgroups: a slab has never honoured cg_persist_half / cg_persist_nq / cg_xcd_local
+// The slab link of the iteration (cg_driver.h: cg_iterate): per-local-rank launches, partial sums collapsed and all-reduced, halo rows
+// of r / x exchanged.  Every rank queues the same collectives in the same order: whatever decides about one - a segment's failure, the
+// verification's verdict, (in slab_solve) the coefficient flags - is read from all-reduced values, never from this rank's alone.
+template <typename CT, int V, bool RECON>
+struct SlabLink {
+  std::vector<SlabRank>& R;
+  Comm& comm;
+  hipStream_t stream;
+  std::vector<int> g1, g2, gflat;
   PersistPlan plan;
-  int cus = 0;
-  if (allow_persist && comm.peer() && nloc == 1 && R[0].a.nx <= (int)comm.rccl->row_cap) {
-    int dev = 0;
-    PISO_HIP_CHECK(hipGetDevice(&dev));
-    PISO_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    plan = persist_plan(PersistQuery{R[0].a.nx, R[0].a.ny, V, R[0].a.per_y, false, sizeof(T), sizeof(CT), RECON, symmetric, true, cus,
-                                     opt(OPT_CG_PERSIST), opt(OPT_CG_PERSIST_R), 0, 0, 0, false, true});
-  }
   PersistCtl pc;
-  { const int rc = persist_prepare<T, CT, RECON, true>(plan, cus, pc, persist_ws, stream); if (rc != PISO_OK) return rc; }
   SlabCtl sl;
-  if (plan.R) {
-    sl.pv = make_view(comm.rccl, comm.periodic_y);
-    sl.ncells = global_cells;
-    sl.rows_own = sl.pv.mbox[sl.pv.rank] + PeerLayout::kRows;
-    sl.rows_lo = sl.pv.mbox[sl.pv.lower >= 0 ? sl.pv.lower : sl.pv.rank] + PeerLayout::kRows;
-    sl.rows_hi = sl.pv.mbox[sl.pv.upper >= 0 ? sl.pv.upper : sl.pv.rank] + PeerLayout::kRows;
-    sl.hop_ticks = opt(OPT_SLAB_HOP_TICKS) > 0 ? (unsigned)opt(OPT_SLAB_HOP_TICKS) : 0u;
-  }
-  const int seg_len = persist_segment_len((size_t)R[0].a.nx * R[0].a.ny, opt(OPT_CG_SEGMENT));   // (per GPU)
+  int seg_len;
 
-  auto k1 = [&](int k, int mode, int sv, int chk, int pend) -> int {
-    for (int q = 0; q < nloc; ++q) cg_k1<T, CT, V, RECON><<<g1[q], kBlock, 0, stream>>>(R[q].a, k, mode, sv, chk, pend);
-    for (int q = 0; q < nloc; ++q) slab_collapse<T><<<1, kBlock, 0, stream>>>(R[q].a.partsA, g1[q], 3, R[q].g);
+  int start(float accuracy, bool symmetric, bool allow_persist, double global_cells) {
+    const int nloc = (int)R.size();
+    g1.resize(nloc); g2.resize(nloc); gflat.resize(nloc);
+    for (int q = 0; q < nloc; ++q) {
+      CgArgs<double>& a = R[q].a;
+      const CgTiling tile = cg_tile(a, V, 0, 0);               // (options cg_rpw / cg_maxblocks are the one-GPU driver's)
+      g1[q] = tile.g1; g2[q] = tile.g2; gflat[q] = tile.gflat;
+      a.accuracy = accuracy;
+      a.gA = R[q].g; a.gB = R[q].g + 4;
+    }
+    if (!tl_slab_pinned) PISO_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&tl_slab_pinned), sizeof(SlabPinned), hipHostMallocDefault));
+    // ---- persistent segments (peer transport, one rank per process): the NORMAL iterations of the slab run inside
+    // cg_persist1<..., SLAB>; every rank takes the same decision (same shape, same options, failures are all-reduced).  The plan is the
+    // one-GPU driver's (cg_dispatch.h) with full workgroups: a slab has never honoured cg_persist_half / cg_persist_nq / cg_xcd_local
+    int cus = 0;
+    if (allow_persist && comm.peer() && nloc == 1 && R[0].a.nx <= (int)comm.rccl->row_cap) {
+      int dev = 0;
+      PISO_HIP_CHECK(hipGetDevice(&dev));
+      PISO_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+      plan = persist_plan(PersistQuery{R[0].a.nx, R[0].a.ny, V, R[0].a.per_y, false, sizeof(double), sizeof(CT), RECON, symmetric, true, cus,
+                                       opt(OPT_CG_PERSIST), opt(OPT_CG_PERSIST_R), 0, 0, 0, false, true});
+    }
+    PISO_TRY((persist_prepare<double, CT, RECON, true>(plan, cus, pc, R[0].persist_ws, stream)));
+    if (plan.R) {
+      sl.pv = make_view(comm.rccl, comm.periodic_y);
+      sl.ncells = global_cells;
+      sl.rows_own = sl.pv.mbox[sl.pv.rank] + PeerLayout::kRows;
+      sl.rows_lo = sl.pv.mbox[sl.pv.lower >= 0 ? sl.pv.lower : sl.pv.rank] + PeerLayout::kRows;
+      sl.rows_hi = sl.pv.mbox[sl.pv.upper >= 0 ? sl.pv.upper : sl.pv.rank] + PeerLayout::kRows;
+      sl.hop_ticks = opt(OPT_SLAB_HOP_TICKS) > 0 ? (unsigned)opt(OPT_SLAB_HOP_TICKS) : 0u;
+    }
+    seg_len = persist_segment_len((size_t)R[0].a.nx * R[0].a.ny, opt(OPT_CG_SEGMENT));   // (per GPU)
+    return PISO_OK;
+  }
+
+  bool persistent() const { return plan.R != 0; }
+  int segment(int k, int ke, CgLoop& st) {
+    PisoComm* c = comm.rccl;
+    // tags: a 16-bit launch counter (the same on every rank) above a 16-bit exchange counter.  When the counter wraps, the
+    // records of 65536 launches ago could pass for new ones: everybody waits for everybody, then clears its own.
+    if ((c->launches & 0xffffu) == 0 && c->launches > 0) {
+      PISO_TRY(comm.allreduce(R, 12, 1, stream));
+      PISO_HIP_CHECK(hipMemsetAsync(c->mbox[c->rank] + PeerLayout::kXcdRecs, 0, PeerLayout::kXcdRecBytes, stream));
+      PISO_TRY(comm.allreduce(R, 12, 1, stream));
+    }
+    PISO_TRY((persist_launch<double, CT, RECON, true>(plan, R[0].a, pc, c->launches++, k, ke, st.sv, st.pending, sl, stream)));
+    // did the segment fail anywhere?  (g[12] = my error flag, summed over the ranks)
+    slab_err_to_sum<double><<<1, 64, 0, stream>>>(pc.err, c->err, R[0].g + 12);
+    PISO_TRY(comm.allreduce(R, 12, 1, stream));
+    PISO_HIP_CHECK(hipMemcpyAsync(&tl_slab_pinned->errsum, R[0].g + 12, sizeof(double), hipMemcpyDeviceToHost, stream));
+    PISO_HIP_CHECK(hipMemcpyAsync(&tl_slab_pinned->st, &R[0].a.state[0], sizeof(CgState), hipMemcpyDeviceToHost, stream));
+    PISO_HIP_CHECK(hipStreamSynchronize(stream));
+    if (tl_slab_pinned->errsum != 0) {
+      ++c->persist_fallbacks;
+      PISO_HIP_CHECK(hipMemsetAsync(c->err, 0, sizeof(int), stream));
+      return kPersistRetry;
+    }
+    c->persist_iterations += ke - k;
+    if (tl_slab_pinned->st.done) { st.finished = true; st.stop_it = tl_slab_pinned->st.iterations; }
+    return PISO_OK;
+  }
+
+  int k1(int k, int mode, int sv, int chk, int pend) {
+    for (size_t q = 0; q < R.size(); ++q) cg_k1<double, CT, V, RECON><<<g1[q], kBlock, 0, stream>>>(R[q].a, k, mode, sv, chk, pend);
+    for (size_t q = 0; q < R.size(); ++q) slab_collapse<double><<<1, kBlock, 0, stream>>>(R[q].a.partsA, g1[q], 3, R[q].g);
     return comm.allreduce(R, 0, 3, stream);
-  };
-  auto k2 = [&](int k, int sv) -> int {
-    for (int q = 0; q < nloc; ++q) cg_k2<T, V><<<g2[q], kBlock, 0, stream>>>(R[q].a, k, sv);
-    for (int q = 0; q < nloc; ++q) slab_collapse<T><<<1, kBlock, 0, stream>>>(R[q].a.partsB, g2[q], 3, R[q].g + 4);
-    int rc = comm.allreduce(R, 4, 3, stream);
-    if (rc != PISO_OK) return rc;
-    return comm.exchange(R, 0, stream);                  // halo rows of the new residual
-  };
-
-  int sv = 0, stop_it = -1, k_last = -1, segments_run = 0;
-  bool pending = false, finished = false;
-  const int batch = 25;
-  for (int k = 0; k < max_iterations && !finished; ++k) {
-    const bool is_reset = ((k + 1) % reset == 0);
-    int rc = PISO_OK;
-    if (plan.R && k > 0 && !is_reset) {
-      // NORMAL iterations [k, ke) in one launch: up to the next reset iteration / the end / one segment length
-      int ke = max_iterations;
-      { const int next_reset = ((k + 1 + reset - 1) / reset) * reset - 1; if (next_reset < ke) ke = next_reset; }
-      if (ke > k + seg_len) ke = k + seg_len;
-      if (ke > k) {
-        PisoComm* c = comm.rccl;
-        // tags: a 16-bit launch counter (the same on every rank) above a 16-bit exchange counter.  When the counter wraps, the
-        // records of 65536 launches ago could pass for new ones: everybody waits for everybody, then clears its own.
-        if ((c->launches & 0xffffu) == 0 && c->launches > 0) {
-          rc = comm.allreduce(R, 12, 1, stream);
-          if (rc == PISO_OK) PISO_HIP_CHECK(hipMemsetAsync(c->mbox[c->rank] + PeerLayout::kXcdRecs, 0, PeerLayout::kXcdRecBytes, stream));
-          if (rc == PISO_OK) rc = comm.allreduce(R, 12, 1, stream);
-          if (rc != PISO_OK) return rc;
-        }
-        rc = persist_launch<T, CT, RECON, true>(plan, R[0].a, pc, c->launches++, k, ke, sv, pending, sl, stream);
-        if (rc != PISO_OK) return rc;
-        // did the segment fail anywhere?  (g[12] = my error flag, summed over the ranks)
-        slab_err_to_sum<T><<<1, 64, 0, stream>>>(pc.err, c->err, R[0].g + 12);
-        rc = comm.allreduce(R, 12, 1, stream);
-        if (rc != PISO_OK) return rc;
-        if constexpr (sizeof(T) == 8) PISO_HIP_CHECK(hipMemcpyAsync(&tl_slab_pinned->errsum, R[0].g + 12, sizeof(double), hipMemcpyDeviceToHost, stream));
-        PISO_HIP_CHECK(hipMemcpyAsync(&tl_slab_pinned->st, &R[0].a.state[0], sizeof(CgState), hipMemcpyDeviceToHost, stream));
-        PISO_HIP_CHECK(hipStreamSynchronize(stream));
-        if (tl_slab_pinned->errsum != 0) {
-          ++c->persist_fallbacks;
-          PISO_HIP_CHECK(hipMemsetAsync(c->err, 0, sizeof(int), stream));
-          return kPersistRetry;
-        }
-        c->persist_iterations += ke - k;
-        ++segments_run;
-        if (tl_slab_pinned->st.done) { finished = true; stop_it = tl_slab_pinned->st.iterations; }
-        k_last = ke - 1;
-        pending = false;                                   // the segment applies every x += alpha p itself
-        k = ke - 1;
-        continue;
-      }
-    }
-    if (is_reset) {
-      if (pending) { for (int q = 0; q < nloc; ++q) cg_flush_x<T><<<gflat[q], kBlock, 0, stream>>>(R[q].a, k - 1, sv); pending = false; }
-      rc = comm.exchange(R, 1, stream);                  // halo rows of x for L x
-      if (rc == PISO_OK) rc = k1(k, MODE_RESET, sv, k > 0 ? 1 : 0, 0);
-      ++sv;
-      for (int q = 0; q < nloc; ++q) cg_reset_residual<T><<<gflat[q], kBlock, 0, stream>>>(R[q].a, sv);
-      if (rc == PISO_OK) rc = comm.exchange(R, 0, stream);
-      if (rc == PISO_OK) rc = k1(k, MODE_INIT, sv, 0, 0);
-    } else if (k == 0) {
-      rc = k1(k, MODE_INIT, sv, 0, 0);
-    } else {
-      rc = k1(k, MODE_NORMAL, sv, 1, pending ? 1 : 0);
-      ++sv;
-    }
-    if (rc == PISO_OK) rc = k2(k, sv);
-    if (rc != PISO_OK) return rc;
-    PISO_LAUNCH_CHECK();
-    pending = true;
-    k_last = k;
-    if ((k + 1) % batch == 0 || k + 1 == max_iterations) {
-      PISO_HIP_CHECK(hipMemcpyAsync(&tl_slab_pinned->st, &R[0].a.state[sv & 1], sizeof(CgState), hipMemcpyDeviceToHost, stream));
-      PISO_HIP_CHECK(hipStreamSynchronize(stream));
-      if (tl_slab_pinned->st.done) { finished = true; stop_it = tl_slab_pinned->st.iterations; }
-    }
   }
-  if (pending && k_last >= 0)
-    for (int q = 0; q < nloc; ++q) cg_flush_x<T><<<gflat[q], kBlock, 0, stream>>>(R[q].a, k_last, sv);
-  // ---- run-time verification of a solve that used the persistent slab kernel (as cg.hip does on one GPU; here it also covers
-  // what crossed xGMI): r must still be b - A^ x for the x this rank returns.  Needs the neighbours' edge rows of x and the
-  // global sum(x); the verdicts of all ranks are summed, so all ranks accept or all restart on the two-kernel iteration.
-  if constexpr (sizeof(T) == 8) {
-    if (segments_run > 0 && opt(OPT_CG_VERIFY) != 0) {
-      CgArgs<T>& a0 = R[0].a;
+  int k2(int k, int sv) {
+    for (size_t q = 0; q < R.size(); ++q) cg_k2<double, V><<<g2[q], kBlock, 0, stream>>>(R[q].a, k, sv);
+    for (size_t q = 0; q < R.size(); ++q) slab_collapse<double><<<1, kBlock, 0, stream>>>(R[q].a.partsB, g2[q], 3, R[q].g + 4);
+    return comm.allreduce(R, 4, 3, stream);
+  }
+  int flush(int k, int sv) { for (size_t q = 0; q < R.size(); ++q) cg_flush_x<double><<<gflat[q], kBlock, 0, stream>>>(R[q].a, k, sv); return PISO_OK; }
+  int reset_residual(int sv) { for (size_t q = 0; q < R.size(); ++q) cg_reset_residual<double><<<gflat[q], kBlock, 0, stream>>>(R[q].a, sv); return PISO_OK; }
+  int halo(int which) { return comm.exchange(R, which, stream); }
+
+  // every 25 iterations and after the last, synchronously (every rank reads the same all-reduced test)
+  int look(int k, CgLoop& st) {
+    if ((k + 1) % 25 != 0 && k + 1 != st.total) return PISO_OK;
+    PISO_HIP_CHECK(hipMemcpyAsync(&tl_slab_pinned->st, &R[0].a.state[st.sv & 1], sizeof(CgState), hipMemcpyDeviceToHost, stream));
+    PISO_HIP_CHECK(hipStreamSynchronize(stream));
+    if (tl_slab_pinned->st.done) { st.finished = true; st.stop_it = tl_slab_pinned->st.iterations; }
+    return PISO_OK;
+  }
+
+  int finish(CgLoop& st) {
+    // ---- run-time verification of a solve that used the persistent slab kernel (as cg.hip does on one GPU; here it also covers
+    // what crossed xGMI): r must still be b - A^ x for the x this rank returns.  Needs the neighbours' edge rows of x and the
+    // global sum(x); the verdicts of all ranks are summed, so all ranks accept or all restart on the two-kernel iteration.
+    if (st.segments_run > 0 && opt(OPT_CG_VERIFY) != 0) {
+      CgArgs<double>& a0 = R[0].a;
       unsigned* out2 = reinterpret_cast<unsigned*>(pc.err) + 4;
       PISO_HIP_CHECK(hipMemsetAsync(out2, 0, 2 * sizeof(unsigned), stream));
-      int rc = comm.exchange(R, 1, stream);
+      PISO_TRY(halo(HALO_X));
       const int gvf = grid_for((long long)a0.nx * a0.ny, kBlock * 4, 1024);
-      cg_verify_sum_x<T><<<gvf, kBlock, 0, stream>>>(a0, a0.partsA);
-      slab_collapse<T><<<1, kBlock, 0, stream>>>(a0.partsA, gvf, 1, R[0].g + 12);
-      if (rc == PISO_OK) rc = comm.allreduce(R, 12, 1, stream);
-      cg_verify_gap<T, CT><<<gvf, kBlock, 0, stream>>>(a0, a0.partsA, 0, out2, R[0].g + 12);
-      slab_gap_to_sum<T><<<1, 64, 0, stream>>>(out2, R[0].g + 13, opt(OPT_CG_VERIFY) == 2 ? 1 : 0);
-      if (rc == PISO_OK) rc = comm.allreduce(R, 13, 1, stream);
-      if (rc != PISO_OK) return rc;
+      cg_verify_sum_x<double><<<gvf, kBlock, 0, stream>>>(a0, a0.partsA);
+      slab_collapse<double><<<1, kBlock, 0, stream>>>(a0.partsA, gvf, 1, R[0].g + 12);
+      PISO_TRY(comm.allreduce(R, 12, 1, stream));
+      cg_verify_gap<double, CT><<<gvf, kBlock, 0, stream>>>(a0, a0.partsA, 0, out2, R[0].g + 12);
+      slab_gap_to_sum<double><<<1, 64, 0, stream>>>(out2, R[0].g + 13, opt(OPT_CG_VERIFY) == 2 ? 1 : 0);
+      PISO_TRY(comm.allreduce(R, 13, 1, stream));
       PISO_LAUNCH_CHECK();
       PISO_HIP_CHECK(hipMemcpyAsync(&tl_slab_pinned->errsum, R[0].g + 13, sizeof(double), hipMemcpyDeviceToHost, stream));
       PISO_HIP_CHECK(hipStreamSynchronize(stream));
@@ -452,112 +417,91 @@ static int slab_iterate(std::vector<SlabRank<T>>& R, Comm<T>& comm, float accura
         return kPersistRetry;
       }
     }
+    for (size_t q = 0; q < R.size(); ++q)
+      slab_copy_rows<double><<<gflat[q], kBlock, 0, stream>>>(R[q].a.x, R[q].x_out, (size_t)R[q].a.nx * R[q].a.ny);
+    PISO_LAUNCH_CHECK();
+    if (comm.peer()) {
+      if (comm.world > 1)       // every rank returns the same status (a wait may have given up on one rank only)
+        peer_agree_on_error<><<<1, 64, 0, stream>>>(make_view(comm.rccl, comm.periodic_y), comm.rccl->err, ++comm.rccl->seq_ar);
+      PISO_HIP_CHECK(hipMemcpyAsync(&tl_slab_pinned->err, comm.rccl->err, sizeof(int), hipMemcpyDeviceToHost, stream));
+    }
+    PISO_HIP_CHECK(hipStreamSynchronize(stream));
+    if (comm.peer() && tl_slab_pinned->err) {
+      PISO_HIP_CHECK(hipMemsetAsync(comm.rccl->err, 0, sizeof(int), stream));
+      set_error_msg("slab CG: a wait on a peer's mailbox gave up (peer process gone or not running?)");
+      return PISO_ERR_HIP;
+    }
+    return PISO_OK;
   }
-  for (int q = 0; q < nloc; ++q)
-    slab_copy_rows<T><<<gflat[q], kBlock, 0, stream>>>(R[q].a.x, R[q].x_out, (size_t)R[q].a.nx * R[q].a.ny);
-  PISO_LAUNCH_CHECK();
-  if (comm.peer()) {
-    if (comm.world > 1)       // every rank returns the same status (a wait may have given up on one rank only)
-      peer_agree_on_error<><<<1, 64, 0, stream>>>(make_view(comm.rccl, comm.periodic_y), comm.rccl->err, ++comm.rccl->seq_ar);
-    PISO_HIP_CHECK(hipMemcpyAsync(&tl_slab_pinned->err, comm.rccl->err, sizeof(int), hipMemcpyDeviceToHost, stream));
-  }
-  PISO_HIP_CHECK(hipStreamSynchronize(stream));
-  if (comm.peer() && tl_slab_pinned->err) {
-    PISO_HIP_CHECK(hipMemsetAsync(comm.rccl->err, 0, sizeof(int), stream));
-    set_error_msg("slab CG: a wait on a peer's mailbox gave up (peer process gone or not running?)");
-    return PISO_ERR_HIP;
-  }
-  if (iterations_out) *iterations_out = finished ? stop_it : max_iterations;
-  return PISO_OK;
-}
+};
 
 // Set up the ranks found in `R` (L, b, x_out, rank already filled in) inside `ws`, then iterate.
-template <typename T>
-static int slab_solve(std::vector<SlabRank<T>>& R, Comm<T>& comm, int nx, int nyl, int per_x, const T* const* b,
+static int slab_solve(std::vector<SlabRank>& R, Comm& comm, int nx, int nyl, int per_x, const double* const* b,
                       double global_cells, float accuracy, int max_iterations, int rank_deficient, int reset,
-                      int* iterations_out, char* ws, size_t ws_per_rank, hipStream_t stream) {
+                      int* iterations_out, char* ws, hipStream_t stream) {
   const int nloc = (int)R.size();
-  const size_t n = (size_t)nx * nyl, nh = (size_t)nx * (nyl + 2);
+  const size_t n = (size_t)nx * nyl, nh = (size_t)nx * (nyl + 2), ws_per_rank = slab_rank_bytes(nx, nyl);
   // the g buffers of all local ranks are contiguous (loopback all-reduce walks them with a fixed stride)
-  T* gall = reinterpret_cast<T*>(ws);
-  const size_t gbytes = align_up((size_t)nloc * 16 * sizeof(T), 256);
+  double* gall = reinterpret_cast<double*>(ws);
+  const size_t gbytes = align_up((size_t)nloc * 16 * sizeof(double), 256);
   comm.g_stride = 16;
   PISO_HIP_CHECK(hipMemsetAsync(gall, 0, gbytes, stream));
+  const int gflat = grid_for((long long)n, kBlock * 4);
+  // r, p, x with their halo rows and the partial sums: before the first attempt and again before the second
+  const auto zero_state = [&](SlabRank& k) -> int {
+    PISO_HIP_CHECK(hipMemsetAsync(k.rbase, 0, nh * sizeof(double), stream));
+    PISO_HIP_CHECK(hipMemsetAsync(k.pbase[0], 0, nh * sizeof(double), stream));
+    PISO_HIP_CHECK(hipMemsetAsync(k.pbase[1], 0, nh * sizeof(double), stream));
+    PISO_HIP_CHECK(hipMemsetAsync(k.xbase, 0, nh * sizeof(double), stream));
+    cg_zero_partials<double><<<(3 * kMaxPartials + 255) / 256, 256, 0, stream>>>(k.a.partsA, k.a.partsB, k.a.partsS);
+    return PISO_OK;
+  };
   for (int q = 0; q < nloc; ++q) {
-    SlabRank<T>& k = R[q];
+    SlabRank& k = R[q];
     Arena ar(ws + gbytes + (size_t)q * ws_per_rank, ws_per_rank);
     k.g = gall + (size_t)q * 16;
-    k.cC = ar.take<T>(n); k.oT = ar.take<T>(4 * n); k.oF = ar.take<float>(4 * n);
-    k.flags = ar.take<int>(4);
-    k.rbase = ar.take<T>(nh); k.pbase[0] = ar.take<T>(nh); k.pbase[1] = ar.take<T>(nh); k.xbase = ar.take<T>(nh);
-    CgArgs<T>& a = k.a;
-    a.z = ar.take<T>(n);
-    a.zp[0] = ar.take<T>(n); a.zp[1] = ar.take<T>(n);   // z' perimeters of the persistent kernel (agent-scope accesses only)
-    k.persist_ws = ar.take<unsigned>(kPersistWsWordsAll);
-    a.partsA = ar.take<T>(3 * kMaxPartials); a.partsB = ar.take<T>(3 * kMaxPartials); a.partsS = ar.take<T>(kMaxPartials);
-    a.scal = ar.take<T>(SC_COUNT);
-    a.state = ar.take<CgState>(2);
+    slab_carve(ar, n, nh, k);
     if (!ar.ok()) { set_error_msg("piso_cg_solve_slab: workspace too small"); return PISO_ERR_INVALID_ARG; }
+    CgArgs<double>& a = k.a;
     a.cC = k.cC; a.b = b[q];
     a.r = k.rbase + nx; a.p[0] = k.pbase[0] + nx; a.p[1] = k.pbase[1] + nx; a.x = k.xbase + nx;
     a.nx = nx; a.ny = nyl; a.per_x = per_x; a.per_y = 2;
     a.gA = nullptr; a.gB = nullptr; a.nt = 0;
     a.nx_true = 0; a.ny_true = 0; a.ncells = 0.0;
     PISO_HIP_CHECK(hipMemsetAsync(k.flags, 0, 4 * sizeof(int), stream));
-    PISO_HIP_CHECK(hipMemsetAsync(k.rbase, 0, nh * sizeof(T), stream));
-    PISO_HIP_CHECK(hipMemsetAsync(k.pbase[0], 0, nh * sizeof(T), stream));
-    PISO_HIP_CHECK(hipMemsetAsync(k.pbase[1], 0, nh * sizeof(T), stream));
-    PISO_HIP_CHECK(hipMemsetAsync(k.xbase, 0, nh * sizeof(T), stream));
-    cg_zero_partials<T><<<(3 * kMaxPartials + 255) / 256, 256, 0, stream>>>(a.partsA, a.partsB, a.partsS);
-    const int gs = grid_for((long long)n, kBlock * 4);
+    PISO_TRY(zero_state(k));
     // symmetry is checked inside the slab (per_y = 2: the N entries of its last row pair with S entries on the neighbour - the
     // persistent kernel reads them from the N array, so nothing is assumed about that pair)
-    cg_setup_coeffs<T><<<gs, kBlock, 0, stream>>>(k.L, k.cC, k.oT, k.oF, a.partsS, k.flags, n, nx, nyl, per_x, 2);
-    slab_collapse<T><<<1, kBlock, 0, stream>>>(a.partsS, gs, 1, k.g + 8);
-    slab_flags_to_sums<T><<<1, 64, 0, stream>>>(k.flags, k.g + 8);
+    cg_setup_coeffs<double><<<gflat, kBlock, 0, stream>>>(k.L, k.cC, k.oT, k.oF, a.partsS, k.flags, n, nx, nyl, per_x, 2);
+    slab_collapse<double><<<1, kBlock, 0, stream>>>(a.partsS, gflat, 1, k.g + 8);
+    slab_flags_to_sums<double><<<1, 64, 0, stream>>>(k.flags, k.g + 8);
   }
   PISO_LAUNCH_CHECK();
-  { const int rc = comm.allreduce(R, 8, 4, stream); if (rc != PISO_OK) return rc; }
-  T hg[4];
-  PISO_HIP_CHECK(hipMemcpyAsync(hg, R[0].g + 8, 4 * sizeof(T), hipMemcpyDeviceToHost, stream));
+  PISO_TRY(comm.allreduce(R, 8, 4, stream));               // every rank reads the same flags: the same instance, the same collectives
+  double hg[4];
+  PISO_HIP_CHECK(hipMemcpyAsync(hg, R[0].g + 8, 4 * sizeof(double), hipMemcpyDeviceToHost, stream));
   PISO_HIP_CHECK(hipStreamSynchronize(stream));
-  const bool f32ok = sizeof(T) == 8 && hg[1] == 0 && !opt_on(OPT_CG_NO_COMPACT);
-  const bool recon = f32ok && hg[2] == 0 && !opt_on(OPT_CG_NO_RECON);
-  const bool symmetric = hg[3] == 0 && !opt_on(OPT_CG_NO_SYM);
-  constexpr int VMID = 16 / sizeof(T);
-  const bool vec = (nx % VMID == 0);
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    // (second attempt: a persistent segment failed on some rank - every rank restarts the solve on the two-kernel iteration)
+  const CgCoefs coefs = cg_coefs(hg[1], hg[2], hg[3], opt_on(OPT_CG_NO_COMPACT), opt_on(OPT_CG_NO_RECON), opt_on(OPT_CG_NO_SYM));
+  // (second attempt: a persistent segment failed on some rank - every rank restarts the solve on the two-kernel iteration)
+  return cg_retry_without_segments("slab CG", [&](bool allow_persist) {
     for (int q = 0; q < nloc; ++q) {
-      SlabRank<T>& k = R[q];
-      const int gflat = grid_for((long long)n, kBlock * 4);
-      if (attempt > 0) {
-        PISO_HIP_CHECK(hipMemsetAsync(k.rbase, 0, nh * sizeof(T), stream));
-        PISO_HIP_CHECK(hipMemsetAsync(k.pbase[0], 0, nh * sizeof(T), stream));
-        PISO_HIP_CHECK(hipMemsetAsync(k.pbase[1], 0, nh * sizeof(T), stream));
-        PISO_HIP_CHECK(hipMemsetAsync(k.xbase, 0, nh * sizeof(T), stream));
-        cg_zero_partials<T><<<(3 * kMaxPartials + 255) / 256, 256, 0, stream>>>(k.a.partsA, k.a.partsB, k.a.partsS);
+      SlabRank& k = R[q];
+      if (!allow_persist) {
+        PISO_TRY(zero_state(k));
         k.a.gA = nullptr; k.a.gB = nullptr;
       }
-      cg_init<T><<<gflat, kBlock, 0, stream>>>(k.a, rank_deficient, k.g + 8, global_cells);
-      if (f32ok) { k.a.oS = k.oF; k.a.oW = k.oF + n; k.a.oE = k.oF + 2 * n; k.a.oN = k.oF + 3 * n; }
+      cg_init<double><<<gflat, kBlock, 0, stream>>>(k.a, rank_deficient, k.g + 8, global_cells);
+      if (coefs.compact) { k.a.oS = k.oF; k.a.oW = k.oF + n; k.a.oE = k.oF + 2 * n; k.a.oN = k.oF + 3 * n; }
       else { k.a.oS = k.oT; k.a.oW = k.oT + n; k.a.oE = k.oT + 2 * n; k.a.oN = k.oT + 3 * n; }
     }
-    { const int rc = comm.exchange(R, 0, stream); if (rc != PISO_OK) return rc; }     // halo rows of r0 = b
-    int rc = PISO_OK;
-#define PISO_SLAB_RUN(CT, V, RC) \
-    rc = slab_iterate<T, CT, V, RC>(R, comm, accuracy, max_iterations, reset, iterations_out, stream, symmetric, attempt == 0, global_cells, R[0].persist_ws)
-    if (f32ok && recon && vec) PISO_SLAB_RUN(float, VMID, true);
-    else if (f32ok && recon) PISO_SLAB_RUN(float, 1, true);
-    else if (f32ok && vec) PISO_SLAB_RUN(float, VMID, false);
-    else if (f32ok) PISO_SLAB_RUN(float, 1, false);
-    else if (vec) PISO_SLAB_RUN(T, VMID, false);
-    else PISO_SLAB_RUN(T, 1, false);
-#undef PISO_SLAB_RUN
-    if (rc != kPersistRetry) return rc;
-  }
-  set_error_msg("slab CG: persistent segment failed twice");
-  return PISO_ERR_HIP;
+    PISO_TRY(comm.exchange(R, HALO_R, stream));            // halo rows of r0 = b
+    return cg_with_instance<double>(coefs, nx % (16 / (int)sizeof(double)) == 0, [&](auto inst) {
+      using I = decltype(inst);
+      SlabLink<typename I::CT, I::V, I::RECON> link{R, comm, stream};
+      PISO_TRY(link.start(accuracy, coefs.symmetric, allow_persist, global_cells));
+      return cg_iterate(link, max_iterations, reset, false, iterations_out);
+    });
+  });
 }
 
 }  // namespace piso
@@ -823,7 +767,7 @@ int piso_comm_check(void* comm, piso_stream_t stream_) {
 }
 
 size_t piso_cg_slab_workspace_bytes(int nx, int ny_local, int local_ranks) {
-  return (size_t)local_ranks * slab_rank_bytes<double>(nx, ny_local) + align_up((size_t)local_ranks * 16 * sizeof(double), 256) + 4096;
+  return (size_t)local_ranks * slab_rank_bytes(nx, ny_local) + align_up((size_t)local_ranks * 16 * sizeof(double), 256) + 4096;
 }
 
 int piso_cg_solve_slab_f64(void* comm, int nx, int ny_local, int periodic_x, int periodic_y, const double* laplace_local,
@@ -839,14 +783,13 @@ int piso_cg_solve_slab_f64(void* comm, int nx, int ny_local, int periodic_x, int
   PisoComm* pc = static_cast<PisoComm*>(comm);
   if (pc->transport == TRANSPORT_PEER && !pc->connected) { set_error_msg("piso_cg_solve_slab_f64: peer communicator not connected"); return PISO_ERR_INVALID_ARG; }
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  std::vector<SlabRank<double>> R(1);
+  std::vector<SlabRank> R(1);
   R[0].L = laplace_local; R[0].x_out = x_out_local; R[0].rank = pc->rank;
-  Comm<double> cm;
+  Comm cm;
   cm.world = pc->world; cm.periodic_y = periodic_y != 0; cm.rccl = pc; cm.g_stride = 16;
   const double* b[1] = {divergence_local};
-  const int rc = slab_solve<double>(R, cm, nx, ny_local, periodic_x, b, (double)nx * ny_local * pc->world, accuracy, max_iterations,
-                                    rank_deficient, residual_reset, iterations_out, static_cast<char*>(workspace),
-                                    slab_rank_bytes<double>(nx, ny_local), stream);
+  const int rc = slab_solve(R, cm, nx, ny_local, periodic_x, b, (double)nx * ny_local * pc->world, accuracy, max_iterations,
+                            rank_deficient, residual_reset, iterations_out, static_cast<char*>(workspace), stream);
   if (rc != PISO_OK) return rc;
   if (x_out_global) {                                       // every rank receives the whole field (replicated PISO step)
     if (pc->world == 1) {
@@ -874,17 +817,17 @@ int piso_cg_solve_slab_emulated_f64(int slabs, int nx, int ny, int periodic_x, i
   const int nyl = ny / slabs;
   if (workspace_bytes < piso_cg_slab_workspace_bytes(nx, nyl, slabs)) { set_error_msg("piso_cg_solve_slab_emulated_f64: workspace too small"); return PISO_ERR_INVALID_ARG; }
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  std::vector<SlabRank<double>> R(slabs);
+  std::vector<SlabRank> R(slabs);
   std::vector<const double*> b(slabs);
   for (int r = 0; r < slabs; ++r) {
     const size_t off = (size_t)r * nyl * nx;
     R[r].L = laplace + off * 5; R[r].x_out = x_out + off; R[r].rank = r;
     b[r] = divergence + off;
   }
-  Comm<double> cm;
+  Comm cm;
   cm.world = slabs; cm.periodic_y = periodic_y != 0; cm.rccl = nullptr; cm.g_stride = 16;
-  return slab_solve<double>(R, cm, nx, nyl, periodic_x, b.data(), (double)nx * ny, accuracy, max_iterations, rank_deficient,
-                            residual_reset, iterations_out, static_cast<char*>(workspace), slab_rank_bytes<double>(nx, nyl), stream);
+  return slab_solve(R, cm, nx, nyl, periodic_x, b.data(), (double)nx * ny, accuracy, max_iterations, rank_deficient,
+                    residual_reset, iterations_out, static_cast<char*>(workspace), stream);
 }
 
 }  // extern "C"

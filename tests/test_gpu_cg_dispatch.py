@@ -2,7 +2,7 @@
 
 One call of piso_cg_solve_* ends in one of about thirty kernel instances, chosen from the grid, the DATA (are the off-diagonals exact
 floats, can the diagonal be rebuilt, is the matrix symmetric bit for bit) and the POINTERS (16-byte alignment of b and x) - cg.hip:
-cg_solve / cg_run over cg_dispatch.h: persist_plan.  Every row of ROWS below pins one instance class: the solve goes through the C ABI, the dispatch record
+cg_solve / GpuLink over cg_driver.h: cg_coefs, cg_with_instance and cg_dispatch.h: persist_plan.  Every row of ROWS below pins one instance class: the solve goes through the C ABI, the dispatch record
 (piso_cg_last_dispatch) must EQUAL the row's expectation - written from the dispatch code, not read back from the card - and the result
 is compared with the C oracle (never with another GPU path alone).  Run with `-m gpu` on an MI355X (256 CUs, 8 XCDs: the expected
 persistent shapes assume them).
