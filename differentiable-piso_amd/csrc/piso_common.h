@@ -252,9 +252,11 @@ inline RowMap make_row_map(const piso_slab_t* slab, int nx, int ny, int per_x = 
   }
   return m;
 }
+// (owns_last_face_row with row_end < ny is refused: the launch would write face row v[row_end], which the slab above owns.  row_end == ny
+// WITHOUT it is legal: nobody writes v[ny] then - include/piso_hip.h)
 inline bool slab_ok(const piso_slab_t* s, int ny) {
   return !s || (s->ny_global == ny && s->row_begin >= 0 && s->row_end > s->row_begin && s->row_end <= ny && s->row_end - s->row_begin >= 4 &&
-                (s->row_end - s->row_begin) + 6 <= ny);
+                (s->row_end - s->row_begin) + 6 <= ny && (!s->owns_last_face_row || s->row_end == ny));
 }
 inline FaceWin face_window(const RowMap& m) {
   const int nx = m.nx, ny = m.ny, n_u = (nx + 1) * ny;

@@ -48,14 +48,20 @@ typedef void* piso_stream_t;
  *                          row_end - row_begin + 6 of them; flat face vectors: the stored u rows followed by the stored v rows
  *                          (v-first vectors: v then u)
  *   padded cell masks      rows [row_begin, row_begin + (row_end - row_begin) + 3) of the [ny + 2] padded rows (no ring)
- *   padded velocities      padded u rows [row_begin, row_end + 2), then padded v rows [row_begin, row_end + 3)
+ *   padded velocities      padded u rows [row_begin, row_end + 2), then padded v rows [row_begin, row_end + 3): the STORAGE.
+ *                          piso_pad_velocity_slab fills padded u rows [row_begin, row_end + 1 + owns_last_face_row) and padded v rows
+ *                          [row_begin, row_end + 2 + owns_last_face_row) - all the assembly of the owned face rows reads - and leaves the
+ *                          remaining stored row of each component (every slab but the last has one) untouched
  *   CSR                    the rows of the stored face rows (u rows, then v rows) in stored order; row pointers
  *                          [stored u rows (nx + 1) + 1][stored v rows nx + 1] are offsets into the stored value / column arrays of
  *                          each component; column indices keep the whole grid's numbering (component-local row numbers)
  *   pressure matrix, CG    the owned rows only ([row_end - row_begin][nx][5]; what piso_cg_solve_slab_* takes)
  * A launch writes the OWNED rows (cells / u rows [row_begin, row_end), v rows [row_begin, row_end + owns_last_face_row)) and reads
  * the stored rows around them, which the caller fills with piso_comm_exchange (element segments of the stored arrays).
- * Constraints: 4 <= row_end - row_begin <= ny_global - 6. */
+ * Constraints: 0 <= row_begin, row_end <= ny_global, 4 <= row_end - row_begin <= ny_global - 6, and owns_last_face_row only with
+ * row_end == ny_global (a slab below the last one would write v[row_end], which its upper neighbour owns); anything else:
+ * PISO_ERR_INVALID_ARG.  row_end == ny_global WITHOUT owns_last_face_row is accepted: that launch leaves v[ny] to its caller (no
+ * entry point then writes it; the stored arrays are the same either way). */
 typedef struct piso_slab {
   int ny_global;              /* cell rows of the whole grid (must equal the entry point's ny) */
   int row_begin, row_end;     /* owned cell rows */
