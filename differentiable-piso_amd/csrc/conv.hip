@@ -15,20 +15,27 @@
 //   conv_wgrad     dW[ky][kx][ci][co] = sum over pixels in[pixel + (ky, kx) - pad][ci] * g[pixel][co]: M = ci,
 //                  N = co, K = pixels; every workgroup reduces a band of rows into its own partial, a second kernel adds the
 //                  partials in a fixed order (deterministic, no atomics)
+//
+// Which instance a call runs, with what launch shape, and what it refuses: conv_dispatch.h (conv_plan, the instance table).  Here: the kernels, and
+// conv_launch - the only host code that names one.
 #include "piso_common.h"
 #include "options.h"
+#include "conv_dispatch.h"
 
 namespace piso {
+
+static_assert(kConvBlock == kBlock, "conv_dispatch.h plans workgroups of kBlock threads");
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr float kLeakySlope = 0.2f;
 
-struct ConvGeom {
-  int H, W;          // input rows / columns
-  int Ho, Wo;        // output rows / columns
-  int pad;           // zero padding on every side
-  int cin, cout;     // true channel counts of `in` / `out` (the weight tensor is [KS][KS][CINP][COUTP], zero padded)
-};
+template <int A, int B>
+__device__ __forceinline__ void zero_tiles(f32x4 (&acc)[A][B]) {
+#pragma unroll
+  for (int a = 0; a < A; ++a)
+#pragma unroll
+    for (int b = 0; b < B; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+}
 
 // KS: kernel size; CINP: input channels rounded up to 4 (<= 4 channels) or to 16; NT: output-channel tiles of 16 (COUTP = 16 NT).
 // CINP >= 16: the K dimension of a block of 16 channels is PERMUTED so that every operand is one 16-byte load: K-step j of the
@@ -47,10 +54,7 @@ __global__ __launch_bounds__(kBlock) void conv_forward_kernel(ConvGeom g, const 
   const int y = tile / tiles_x, x0 = (tile - y * tiles_x) * 16 * MT;
   const int ai = lane & 15, ak = lane >> 4;                 // A: pixel in tile, channel group;  B: channel group = ak, co = ai
   f32x4 acc[MT][NT];
-#pragma unroll
-  for (int m = 0; m < MT; ++m)
-#pragma unroll
-    for (int n = 0; n < NT; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  zero_tiles(acc);
   if constexpr (CINP >= 16) {
     // Software pipeline over the K-blocks (tap row, block of 16 channels, tap column): the operands of block s + 1 are loaded while
     // the 16 MT NT / 4 MFMAs of block s run - issued and consumed in the same block the loop ran at the latency of one L2 round
@@ -164,10 +168,7 @@ __global__ __launch_bounds__(kBlock) void conv_forward_lds_kernel(ConvGeom g, co
   const int y = active ? tile / tiles_x : 0, x0 = active ? (tile - y * tiles_x) * 16 * MT : 0;
   const int ai = lane & 15, ak = lane >> 4;
   f32x4 acc[MT][NT];
-#pragma unroll
-  for (int m = 0; m < MT; ++m)
-#pragma unroll
-    for (int n = 0; n < NT; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  zero_tiles(acc);
   // every wave walks ALL tap rows (the weights of a stage are the same for every output row); a tap row outside the image - zero
   // padding above / below - contributes nothing: its pixels are staged as zeros (wave-uniform: no loads are issued)
   constexpr int nstages = KS * CB;
@@ -252,10 +253,7 @@ __global__ __launch_bounds__(kBlock) void conv_wgrad_kernel(ConvGeom g, const fl
   const int item0 = (blockIdx.y * 4 + wave) * IPW;
   if (item0 >= ITEMS) return;
   f32x4 acc[IPW][NT];
-#pragma unroll
-  for (int t = 0; t < IPW; ++t)
-#pragma unroll
-    for (int n = 0; n < NT; ++n) acc[t][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  zero_tiles(acc);
   int ky[IPW], kx[IPW], ci[IPW];
 #pragma unroll
   for (int t = 0; t < IPW; ++t) {
@@ -336,10 +334,7 @@ __global__ __launch_bounds__(kBlock) void conv_wgrad_lds_kernel(ConvGeom g, cons
   const int item0 = (blockIdx.y * 4 + wave) * IPW;
   if (threadIdx.x < 2) Is[threadIdx.x][IV] = (f32x4){0.f, 0.f, 0.f, 0.f};
   f32x4 acc[IPW][NT];
-#pragma unroll
-  for (int t = 0; t < IPW; ++t)
-#pragma unroll
-    for (int n = 0; n < NT; ++n) acc[t][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  zero_tiles(acc);
   int aoff[IPW];                                            // float offset of (ky, kx, ci tile) inside a staged `in` chunk, + my ci
 #pragma unroll
   for (int t = 0; t < IPW; ++t) {
@@ -440,10 +435,7 @@ __global__ __launch_bounds__(kBlock) void conv_wgrad64_kernel(ConvGeom g, const 
   if (tap >= TAPS) return;
   const int ky = tap / KS, kx = tap - ky * KS;
   f32x4 acc[4][4];
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  zero_tiles(acc);
   const int y_begin = blockIdx.x * rows_per_block, y_end = min(y_begin + rows_per_block, g.Ho);
   for (int y = y_begin; y < y_end; ++y) {
     const int yy = y + ky - g.pad;
@@ -493,10 +485,7 @@ __global__ __launch_bounds__(64 * KS) void conv_wgrad64_lds_kernel(ConvGeom g, c
   if (threadIdx.x < 2) Is[threadIdx.x][PA * 16] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const int tap = ky * KS + kx;
   f32x4 acc[4][4];
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  zero_tiles(acc);
   const int y_begin = blockIdx.x * rows_per_block, y_end = min(y_begin + rows_per_block, g.Ho);
   const int chunks_x = (g.Wo + CH - 1) / CH;
   f32x4 rg[NLB], ri[NLA];
@@ -605,88 +594,61 @@ __global__ __launch_bounds__(kBlock) void conv_wgrad_reduce4_kernel(const float*
   __syncthreads();
   if (wave == 0 && k4 < n4) *reinterpret_cast<f32x4*>(dw + (size_t)k4 * 4) = ((sm[threadIdx.x] + sm[64 + threadIdx.x]) + sm[128 + threadIdx.x]) + sm[192 + threadIdx.x];
 }
-// (returns the reducer that ran, as piso_conv_last_dispatch reports it: 4 the 4-wide one, 1 the scalar one)
-static int launch_wgrad_reduce(const float* part, float* dw, int nblocks, int taps, int cinp16, int coutp, int cin, int cout, hipStream_t stream) {
-  const int n = taps * cin * cout;
-  if (cout % 4 == 0 && coutp % 4 == 0) {
-    conv_wgrad_reduce4_kernel<<<(n / 4 + 63) / 64, kBlock, 0, stream>>>(part, dw, nblocks, taps, cinp16, coutp, cin, cout);
-    return 4;
-  }
-  conv_wgrad_reduce_kernel<<<(n + 63) / 64, kBlock, 0, stream>>>(part, dw, nblocks, taps, cinp16, coutp, cin, cout);
-  return 1;
-}
 
-// row bands = partial sums per weight: what the second stage has to add (and re-read).  256: one output row per band at config 4's
-// size - with bands of two rows the 9 x 126 waves of the 64 -> 64 layer left SIMDs with two waves next to SIMDs with one
-constexpr int kWgradMaxBlocks = 256;
-
-// which kernel instance the calling thread's last convolution ran (piso_conv_last_dispatch; fields: include/piso_hip.h)
-enum { CD_ENTRY = 0, CD_KS, CD_C, CD_NT, CD_IPW, CD_FAMILY, CD_LEAKY, CD_GRID_X, CD_GRID_Y, CD_BLOCK, CD_ROWS_PER_BLOCK, CD_NBLOCKS, CD_REDUCER,
-       CD_HO, CD_WO, CD_COUNT };
-enum { CF_FWD_DIRECT = 0, CF_FWD_LDS, CF_WG_GENERIC, CF_WG_GENERIC_LDS, CF_WG_PACK4, CF_WG_64, CF_WG_64_LDS };
-static thread_local int tl_conv_dispatch[CD_COUNT];
+// which kernel instance the calling thread's last convolution ran (piso_conv_last_dispatch; fields: include/piso_hip.h): the plan that was launched
+static thread_local int tl_conv_dispatch[kConvRecordFields];
 static thread_local int tl_conv_dispatch_n = 0;
-static void record_forward(const ConvGeom& g, int ks, int cinp, int nt, int family, int leaky, int grid) {
-  const int r[CD_COUNT] = {1, ks, cinp, nt, 0, family, leaky != 0, grid, 1, kBlock, 0, 0, 0, g.Ho, g.Wo};
-  for (int i = 0; i < CD_COUNT; ++i) tl_conv_dispatch[i] = r[i];
-  tl_conv_dispatch_n = CD_COUNT;
-}
-static void record_wgrad(const ConvGeom& g, int ks, int mti, int nt, int ipw, int family, int grid_y, int block, int rows_per_block, int nblocks,
-                         int reducer) {
-  const int r[CD_COUNT] = {2, ks, mti, nt, ipw, family, 0, nblocks, grid_y, block, rows_per_block, nblocks, reducer, g.Ho, g.Wo};
-  for (int i = 0; i < CD_COUNT; ++i) tl_conv_dispatch[i] = r[i];
-  tl_conv_dispatch_n = CD_COUNT;
-}
+static void record(const ConvPlan& p) { conv_record(p, tl_conv_dispatch); tl_conv_dispatch_n = kConvRecordFields; }
 
-template <int KS, int CINP, int NT>
-static int launch_forward(const ConvGeom& g, const float* in, const float* w, float* out, int leaky, hipStream_t stream) {
-  if constexpr (CINP >= 16 && KS >= 3) {
-    if (opt(OPT_CONV_LDS) != 0) {                            // operands staged through LDS (option conv_lds 0: the direct kernel)
-      const int tiles2 = ((g.Wo + 63) / 64) * g.Ho, grid2 = (tiles2 + kBlock / 64 - 1) / (kBlock / 64);
-      if (leaky) conv_forward_lds_kernel<KS, CINP, NT, true><<<grid2, kBlock, 0, stream>>>(g, in, w, out);
-      else conv_forward_lds_kernel<KS, CINP, NT, false><<<grid2, kBlock, 0, stream>>>(g, in, w, out);
-      PISO_LAUNCH_CHECK();
-      record_forward(g, KS, CINP, NT, CF_FWD_LDS, leaky, grid2);
-      return PISO_OK;
-    }
+// The only host code that names a convolution kernel: the instance is the plan's (KS, C, NT, family), every launch dimension the plan's.
+// b: w_laid_out (forward) / grad_out (weight gradient); out: `out` / dw
+static int conv_launch(const ConvPlan& p, const float* in, const float* b, float* out, float* part, hipStream_t stream) {
+  const ConvGeom& g = p.g;
+  const dim3 grid(p.grid_x, p.grid_y);
+  const int block = p.block, rows = p.rows_per_block;
+  if (p.entry == CE_FORWARD) {
+    conv_with_shape<kConvFwd>(p.KS, p.C, p.NT, [&](auto i) {
+      constexpr ConvShape s = kConvFwd[decltype(i)::value];
+      if constexpr (conv_fwd_has_lds(s.KS, s.C)) {
+        if (p.family == CF_FWD_LDS) {
+          if (p.leaky) conv_forward_lds_kernel<s.KS, s.C, s.NT, true><<<grid, block, 0, stream>>>(g, in, b, out);
+          else conv_forward_lds_kernel<s.KS, s.C, s.NT, false><<<grid, block, 0, stream>>>(g, in, b, out);
+          return;
+        }
+      }
+      if (p.leaky) conv_forward_kernel<s.KS, s.C, s.NT, true><<<grid, block, 0, stream>>>(g, in, b, out);
+      else conv_forward_kernel<s.KS, s.C, s.NT, false><<<grid, block, 0, stream>>>(g, in, b, out);
+    });
+    PISO_LAUNCH_CHECK();
+    return PISO_OK;
   }
-  const int tiles = ((g.Wo + 63) / 64) * g.Ho;
-  const int grid = (tiles + kBlock / 64 - 1) / (kBlock / 64);
-  if (leaky) conv_forward_kernel<KS, CINP, NT, true><<<grid, kBlock, 0, stream>>>(g, in, w, out);
-  else conv_forward_kernel<KS, CINP, NT, false><<<grid, kBlock, 0, stream>>>(g, in, w, out);
+  constexpr ConvShape p4 = kConvWgPack4;
+  if (p.family == CF_WG_64_LDS) conv_wgrad64_lds_kernel<kConvWg64.KS><<<grid, block, 0, stream>>>(g, in, b, part, rows);
+  else if (p.family == CF_WG_64) conv_wgrad64_kernel<kConvWg64.KS><<<grid, block, 0, stream>>>(g, in, b, part, rows);
+  else if (p.family == CF_WG_PACK4) conv_wgrad_kernel<p4.KS, p4.C, p4.NT, p4.IPW, true><<<grid, block, 0, stream>>>(g, in, b, part, rows);
+  else
+    conv_with_shape<kConvWg>(p.KS, p.C, p.NT, [&](auto i) {
+      constexpr ConvShape s = kConvWg[decltype(i)::value];
+      if (p.family == CF_WG_GENERIC_LDS) conv_wgrad_lds_kernel<s.KS, s.C, s.NT, s.IPW><<<grid, block, 0, stream>>>(g, in, b, part, rows);
+      else conv_wgrad_kernel<s.KS, s.C, s.NT, s.IPW><<<grid, block, 0, stream>>>(g, in, b, part, rows);
+    });
   PISO_LAUNCH_CHECK();
-  record_forward(g, KS, CINP, NT, CF_FWD_DIRECT, leaky, grid);
+  const int taps = p.KS * p.KS, cinp16 = 16 * p.C, coutp = 16 * p.NT;
+  if (p.reducer == 4) conv_wgrad_reduce4_kernel<<<p.reduce_grid, kBlock, 0, stream>>>(part, out, p.nblocks, taps, cinp16, coutp, g.cin, g.cout);
+  else conv_wgrad_reduce_kernel<<<p.reduce_grid, kBlock, 0, stream>>>(part, out, p.nblocks, taps, cinp16, coutp, g.cin, g.cout);
+  PISO_LAUNCH_CHECK();
   return PISO_OK;
 }
 
-template <int KS, int MTI, int NT, int IPW, bool PACK4 = false>
-static int launch_wgrad(const ConvGeom& g, const float* in, const float* gout, float* part, float* dw, hipStream_t stream) {
-  const int rows_per_block = (g.Ho + kWgradMaxBlocks - 1) / kWgradMaxBlocks;
-  const int nblocks = (g.Ho + rows_per_block - 1) / rows_per_block;
-  constexpr int items = PACK4 ? KS * ((KS + 3) / 4) : KS * KS * MTI;
-  constexpr int groups = (items + 4 * IPW - 1) / (4 * IPW);
-  bool staged = false;
-  if constexpr (!PACK4) {
-    if (opt(OPT_CONV_LDS) != 0 && g.cin % 4 == 0 && g.cout % 4 == 0) {
-      conv_wgrad_lds_kernel<KS, MTI, NT, IPW><<<dim3(nblocks, groups), kBlock, 0, stream>>>(g, in, gout, part, rows_per_block);
-      staged = true;
-    }
-  }
-  if (!staged) conv_wgrad_kernel<KS, MTI, NT, IPW, PACK4><<<dim3(nblocks, groups), kBlock, 0, stream>>>(g, in, gout, part, rows_per_block);
-  PISO_LAUNCH_CHECK();
-  const int reducer = launch_wgrad_reduce(part, dw, nblocks, KS * KS, 16 * MTI, 16 * NT, g.cin, g.cout, stream);
-  PISO_LAUNCH_CHECK();
-  record_wgrad(g, KS, MTI, NT, IPW, PACK4 ? CF_WG_PACK4 : staged ? CF_WG_GENERIC_LDS : CF_WG_GENERIC, groups, kBlock, rows_per_block, nblocks, reducer);
-  return PISO_OK;
+// one call: plan it, refuse it or launch it, record what ran (a refused or failed call leaves the record untouched)
+static int conv_run(const ConvQuery& q, const float* in, const float* b, float* out, void* workspace, piso_stream_t stream) {
+  const ConvPlan p = conv_plan(q);
+  if (p.status != PISO_OK) { set_error_msg(p.msg); return p.status; }
+  const int st = conv_launch(p, in, b, out, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
+  if (st == PISO_OK) record(p);
+  return st;
 }
 
-static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
-}  // namespace piso
-
-using namespace piso;
-
-namespace piso {
 // g' = g * leaky'(pre-activation) from the layer's saved OUTPUT (a leaky ReLU with a positive slope keeps the sign): the gradient of
 // the pre-activation that both the input gradient and the weight gradient consume.  One pass (torch: a multiply and a where).
 __global__ __launch_bounds__(kBlock) void leaky_backward_kernel(const float* __restrict__ g, const float* __restrict__ out, float* __restrict__ gp, size_t n4) {
@@ -702,7 +664,11 @@ __global__ __launch_bounds__(kBlock) void leaky_backward_tail_kernel(const float
   const size_t i = begin + (size_t)blockIdx.x * kBlock + threadIdx.x;
   if (i < n) gp[i] = out[i] > 0.f ? g[i] : kLeakySlope * g[i];
 }
+
+static inline bool misaligned16(const void* a, const void* b) { return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) != 0; }
 }  // namespace piso
+
+using namespace piso;
 
 extern "C" {
 int piso_conv_last_dispatch(int* out, int capacity) {
@@ -723,87 +689,26 @@ int piso_leaky_relu_backward(const float* grad_out, const float* out, float* gra
   return PISO_OK;
 }
 
-static inline int padded_cin(int cin) { return cin <= 4 ? 4 : round_up(cin, 16); }
-static inline bool misaligned16(const void* a, const void* b) { return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) != 0; }
-
 // Weight layout expected by piso_conv2d_forward (zero filled beyond the true channel counts), COUTP = round_up(cout, 16):
 //   cin <= 4 : [ks][ks][4][COUTP]                                 (HWIO, channels padded to 4)
 //   cin  > 4 : [ks][ks][CINP / 16][4][COUTP][4], CINP = round_up(cin, 16): element [tap][blk][q][co][j] = W[tap][16 blk + 4 q + j][co]
-size_t piso_conv2d_weight_elems(int ks, int cin, int cout) { return (size_t)ks * ks * padded_cin(cin) * round_up(cout, 16); }
+size_t piso_conv2d_weight_elems(int ks, int cin, int cout) { return conv_weight_elems(ks, cin, cout); }
 
-size_t piso_conv2d_wgrad_workspace_bytes(int ks, int cin, int cout) {
-  return (size_t)kWgradMaxBlocks * ks * ks * round_up(cin, 16) * round_up(cout, 16) * sizeof(float);
-}
+size_t piso_conv2d_wgrad_workspace_bytes(int ks, int cin, int cout) { return conv_wgrad_workspace_bytes(ks, cin, cout); }
 
 int piso_conv2d_forward(const float* in, const float* w_laid_out, float* out, int H, int W, int cin, int cout, int ks, int pad, int leaky_out,
-                        piso_stream_t stream_) {
+                        piso_stream_t stream) {
   const piso::OptScope knobs;                              // (the call works on a snapshot of the knobs, options.h)
-  ConvGeom g;
-  g.H = H; g.W = W; g.pad = pad; g.cin = cin; g.cout = cout;
-  g.Ho = H + 2 * pad - ks + 1; g.Wo = W + 2 * pad - ks + 1;
-  if (!in || !w_laid_out || !out || g.Ho < 1 || g.Wo < 1 || cin < 1 || cout < 1 || cout > 64 || cin > 64 || (cin > 4 && cin % 16 != 0)) {
-    set_error_msg("piso_conv2d_forward: invalid argument (channels: 1..4 or a multiple of 16 up to 64 in, 1..64 out; kernel size 1 | 3 | 5 | 7)");
-    return PISO_ERR_INVALID_ARG;
-  }
-  if (cin > 4 && misaligned16(in, w_laid_out)) {           // (16 channels and more: every operand is a 16-byte load)
-    set_error_msg("piso_conv2d_forward: invalid argument (with more than 4 input channels `in` and `w_laid_out` must be 16-byte aligned)");
-    return PISO_ERR_INVALID_ARG;
-  }
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const int cinp = padded_cin(cin), nt = round_up(cout, 16) / 16;
-#define PISO_CONV_FWD(KS, CINP, NT) \
-  if (ks == KS && cinp == CINP && nt == NT) return launch_forward<KS, CINP, NT>(g, in, w_laid_out, out, leaky_out, stream)
-  // the layers of the closure and of its input-gradient pass (channel roles swapped)
-  PISO_CONV_FWD(7, 4, 1);  PISO_CONV_FWD(7, 16, 1);
-  PISO_CONV_FWD(5, 16, 1); PISO_CONV_FWD(5, 16, 2); PISO_CONV_FWD(5, 32, 1);
-  PISO_CONV_FWD(3, 32, 4); PISO_CONV_FWD(3, 64, 2); PISO_CONV_FWD(3, 64, 4);
-  PISO_CONV_FWD(1, 64, 4); PISO_CONV_FWD(1, 64, 1); PISO_CONV_FWD(1, 4, 4);
-#undef PISO_CONV_FWD
-  set_error_msg("piso_conv2d_forward: this (kernel size, channels) combination is not instantiated");
-  return PISO_ERR_INVALID_ARG;
+  const ConvQuery q{CE_FORWARD, H, W, cin, cout, ks, pad, leaky_out, opt(OPT_CONV_LDS), !in || !w_laid_out || !out, misaligned16(in, w_laid_out), false, 0};
+  return conv_run(q, in, w_laid_out, out, nullptr, stream);
 }
 
 int piso_conv2d_wgrad(const float* in, const float* grad_out, float* dw, int H, int W, int cin, int cout, int ks, int pad, void* workspace,
-                      size_t workspace_bytes, piso_stream_t stream_) {
+                      size_t workspace_bytes, piso_stream_t stream) {
   const piso::OptScope knobs;                              // (the call works on a snapshot of the knobs, options.h)
-  ConvGeom g;
-  g.H = H; g.W = W; g.pad = pad; g.cin = cin; g.cout = cout;
-  g.Ho = H + 2 * pad - ks + 1; g.Wo = W + 2 * pad - ks + 1;
-  if (!in || !grad_out || !dw || !workspace || g.Ho < 1 || g.Wo < 1 || cin < 1 || cout < 1 || cout > 64 || cin > 64 ||
-      workspace_bytes < piso_conv2d_wgrad_workspace_bytes(ks, cin, cout)) {
-    set_error_msg("piso_conv2d_wgrad: invalid argument");
-    return PISO_ERR_INVALID_ARG;
-  }
-  // (cout % 4 == 0: the 4-wide reducer reads the partials and writes dw with 16-byte accesses; cin % 4 == 0 as well: the staged kernels
-  // and the 64 -> 64 kernels load `in` and `grad_out` that way)
-  if ((cout % 4 == 0 && misaligned16(dw, workspace)) || (cin % 4 == 0 && cout % 4 == 0 && misaligned16(in, grad_out))) {
-    set_error_msg("piso_conv2d_wgrad: invalid argument (cout % 4 == 0: `dw` and `workspace` must be 16-byte aligned; cin % 4 == 0 as well: `in` and `grad_out` too)");
-    return PISO_ERR_INVALID_ARG;
-  }
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  float* part = static_cast<float*>(workspace);
-  const int mti = round_up(cin, 16) / 16, nt = round_up(cout, 16) / 16;
-#define PISO_CONV_WG(KS, MTI, NT, IPW) \
-  if (ks == KS && mti == MTI && nt == NT) return launch_wgrad<KS, MTI, NT, IPW>(g, in, grad_out, part, dw, stream)
-  if (cin == 64 && cout == 64 && ks == 3) {      // (measured: 304 us against 329 us for the generic kernel at 250 x 876; the 1 x 1
-    // layer has a single tap, i.e. one busy wave per workgroup here, and stays on the generic kernel: 130 us against 219 us)
-    const int rows_per_block = (g.Ho + kWgradMaxBlocks - 1) / kWgradMaxBlocks, nblocks = (g.Ho + rows_per_block - 1) / rows_per_block;
-    const bool staged = opt(OPT_CONV_LDS) != 0;
-    if (staged) conv_wgrad64_lds_kernel<3><<<dim3(nblocks, 3), 192, 0, stream>>>(g, in, grad_out, part, rows_per_block);
-    else conv_wgrad64_kernel<3><<<dim3(nblocks, 3), 192, 0, stream>>>(g, in, grad_out, part, rows_per_block);
-    PISO_LAUNCH_CHECK();
-    const int reducer = launch_wgrad_reduce(part, dw, nblocks, ks * ks, 64, 64, 64, 64, stream);
-    PISO_LAUNCH_CHECK();
-    record_wgrad(g, 3, 4, 4, 1, staged ? CF_WG_64_LDS : CF_WG_64, 3, 192, rows_per_block, nblocks, reducer);
-    return PISO_OK;
-  }
-  // (items per wave: enough waves to fill the chip, few enough registers for the 4 x 4-pixel prefetch)
-  if (ks == 7 && cin <= 4 && nt == 1) return launch_wgrad<7, 1, 1, 1, true>(g, in, grad_out, part, dw, stream);
-  PISO_CONV_WG(7, 1, 1, 3); PISO_CONV_WG(5, 1, 1, 2); PISO_CONV_WG(5, 1, 2, 2); PISO_CONV_WG(3, 2, 4, 1); PISO_CONV_WG(3, 4, 4, 1);
-  PISO_CONV_WG(1, 4, 4, 1); PISO_CONV_WG(1, 4, 1, 1);
-#undef PISO_CONV_WG
-  set_error_msg("piso_conv2d_wgrad: this (kernel size, channels) combination is not instantiated");
-  return PISO_ERR_INVALID_ARG;
+  const ConvQuery q{CE_WGRAD, H, W, cin, cout, ks, pad, 0, opt(OPT_CONV_LDS), !in || !grad_out || !dw || !workspace, misaligned16(in, grad_out),
+                    misaligned16(dw, workspace), workspace_bytes};
+  return conv_run(q, in, grad_out, dw, workspace, stream);
 }
 
 }  // extern "C"

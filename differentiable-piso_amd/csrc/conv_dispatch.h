@@ -1,0 +1,144 @@
+// Host side of the closure convolutions' kernel choice (conv.hip): the geometry a kernel is handed, WHICH instances exist (kConvFwd, kConvWg,
+// the PACK4 and 64 -> 64 rows, conv_fwd_has_lds: the one statement of it - the planner asks at run time, conv_launch at compile time) and the
+// plan of a call (conv_plan: pure, no HIP calls - every refusal of both entry points, the family, every launch dimension, the bands, the
+// reducer, i.e. the whole dispatch record).  Plain C++: a host compiler can include this file and walk every plan without a card.
+#pragma once
+#include <stddef.h>
+
+#include <type_traits>
+#include <utility>
+
+#include "../../include/piso_hip.h"
+
+namespace piso {
+
+constexpr int kConvBlock = 256;   // threads of a workgroup (piso_common.h: kBlock; conv.hip holds the two equal)
+
+struct ConvGeom {
+  int H, W;          // input rows / columns
+  int Ho, Wo;        // output rows / columns
+  int pad;           // zero padding on every side
+  int cin, cout;     // true channel counts of `in` / `out` (the weight tensor is [KS][KS][CINP][COUTP], zero padded)
+};
+inline ConvGeom conv_geom(int H, int W, int cin, int cout, int ks, int pad) {
+  return ConvGeom{H, W, H + 2 * pad - ks + 1, W + 2 * pad - ks + 1, pad, cin, cout};
+}
+
+constexpr int round_up(int v, int m) { return (v + m - 1) / m * m; }
+constexpr int ceil_div(int v, int m) { return (v + m - 1) / m; }
+constexpr int padded_cin(int cin) { return cin <= 4 ? 4 : round_up(cin, 16); }
+// row bands = partial sums per weight: what the second stage has to add (and re-read).  256: one output row per band at config 4's
+// size - with bands of two rows the 9 x 126 waves of the 64 -> 64 layer left SIMDs with two waves next to SIMDs with one
+constexpr int kWgradMaxBlocks = 256;
+inline size_t conv_weight_elems(int ks, int cin, int cout) { return (size_t)ks * ks * padded_cin(cin) * round_up(cout, 16); }
+inline size_t conv_wgrad_workspace_bytes(int ks, int cin, int cout) {
+  return (size_t)kWgradMaxBlocks * ks * ks * round_up(cin, 16) * round_up(cout, 16) * sizeof(float);
+}
+
+// ---- the instances.  A shape is the record's (KS, C, NT, IPW): C = CINP forward (input channels rounded up to 4 or to 16), MTI = CINP16 / 16
+// for the weight gradient; NT output-channel tiles of 16; IPW items per wave (weight gradient: enough waves to fill the chip, few enough
+// registers for the 4 x 4-pixel prefetch).  Forward: the layers of the closure and of its input-gradient pass (channel roles swapped).
+struct ConvShape { int KS, C, NT, IPW; };
+inline constexpr ConvShape kConvFwd[] = {{7, 4, 1, 0},  {7, 16, 1, 0}, {5, 16, 1, 0}, {5, 16, 2, 0}, {5, 32, 1, 0}, {3, 32, 4, 0},
+                                  {3, 64, 2, 0}, {3, 64, 4, 0}, {1, 64, 4, 0}, {1, 64, 1, 0}, {1, 4, 4, 0}};
+inline constexpr ConvShape kConvWg[] = {{7, 1, 1, 3}, {5, 1, 1, 2}, {5, 1, 2, 2}, {3, 2, 4, 1}, {3, 4, 4, 1}, {1, 4, 4, 1}, {1, 4, 1, 1}};
+inline constexpr ConvShape kConvWgPack4 = {7, 1, 1, 1};   // conv_wgrad_kernel<.., PACK4>: the first layer
+inline constexpr ConvShape kConvWg64 = {3, 4, 4, 1};      // conv_wgrad64[_lds]_kernel<KS>: workgroups of KS waves, one per tap column; grid y = KS tap rows
+// conv_with_shape<table>(ks, c, nt, f) calls f(std::integral_constant<size_t, i>) for THE row i of the table with these (KS, C, NT); false - and no call -
+// if there is none
+template <const auto& T, typename F, size_t... I>
+inline bool conv_with_shape_(int ks, int c, int nt, F&& f, std::index_sequence<I...>) {
+  return (... || (T[I].KS == ks && T[I].C == c && T[I].NT == nt && (f(std::integral_constant<size_t, I>{}), true)));
+}
+template <const auto& T, typename F>
+inline bool conv_with_shape(int ks, int c, int nt, F&& f) {
+  return conv_with_shape_<T>(ks, c, nt, f, std::make_index_sequence<sizeof(T) / sizeof(T[0])>{});
+}
+// forward: a form with the operands staged through LDS exists (tap columns share the staged pixels; channels in blocks of 16)
+constexpr bool conv_fwd_has_lds(int ks, int cinp) { return cinp >= 16 && ks >= 3; }
+// forward, CINP >= 16: every operand is a 16-byte load (both forms)
+constexpr bool conv_fwd_loads16(int cinp) { return cinp >= 16; }
+// (measured: 304 us against 329 us for the generic kernel at 250 x 876; the 1 x 1 layer has a single tap, i.e. one busy wave per workgroup
+// there, and stays on the generic kernel: 130 us against 219 us)
+constexpr bool conv_wg_is_64(int ks, int cin, int cout) { return ks == kConvWg64.KS && cin == 64 && cout == 64; }
+constexpr bool conv_wg_is_pack4(int ks, int cin, int nt) { return ks == kConvWgPack4.KS && cin <= 4 && nt == kConvWgPack4.NT; }
+// weight gradient: the channel counts whose 16-byte forms exist - the staged generic kernel, both 64 -> 64 kernels load `in` and `grad_out`
+// that way.  Option conv_lds decides whether a staged form RUNS, never what a call must satisfy: the alignment rule asks this, not the family
+constexpr bool conv_wg_loads16(int cin, int cout) { return cin % 4 == 0 && cout % 4 == 0; }
+// ... and the 4-wide reducer reads the partials and writes dw with 16-byte accesses
+constexpr int conv_wg_reducer(int cout) { return cout % 4 == 0 ? 4 : 1; }
+
+// ---- the plan: everything an entry point decides before it launches
+enum { CE_FORWARD = 1, CE_WGRAD = 2 };
+enum { CF_FWD_DIRECT = 0, CF_FWD_LDS, CF_WG_GENERIC, CF_WG_GENERIC_LDS, CF_WG_PACK4, CF_WG_64, CF_WG_64_LDS };
+struct ConvQuery {
+  int entry;                         // CE_FORWARD (piso_conv2d_forward) | CE_WGRAD (piso_conv2d_wgrad)
+  int H, W, cin, cout, ks, pad;
+  int leaky;                         // forward: leaky_out as passed
+  int conv_lds;                      // option value (-1: not set)
+  bool null_ptr;                     // one of the entry's pointers is NULL
+  bool operands_off16, result_off16; // not 16-byte aligned: `in` or the second operand (w_laid_out / grad_out); wgrad: dw or workspace
+  size_t workspace_bytes;            // wgrad
+};
+constexpr int kConvRecordFields = 15;
+struct ConvPlan {
+  int status = PISO_OK;              // != PISO_OK: the call is refused with `msg`, nothing else of the plan is to be used
+  const char* msg = nullptr;
+  ConvGeom g;
+  // the dispatch record (include/piso_hip.h: piso_conv_last_dispatch; with g.Ho, g.Wo) = the launch of the main kernel: grid (grid_x, grid_y), block
+  int entry, KS, C, NT, IPW, family, leaky, grid_x, grid_y, block, rows_per_block, nblocks, reducer;
+  int reduce_grid;                   // gridDim.x of the reducer
+};
+inline void conv_record(const ConvPlan& p, int (&r)[kConvRecordFields]) {
+  const int v[kConvRecordFields] = {p.entry, p.KS, p.C, p.NT, p.IPW, p.family, p.leaky, p.grid_x, p.grid_y, p.block, p.rows_per_block, p.nblocks, p.reducer,
+                                    p.g.Ho, p.g.Wo};
+  for (int i = 0; i < kConvRecordFields; ++i) r[i] = v[i];
+}
+
+inline ConvPlan conv_plan(const ConvQuery& q) {
+  ConvPlan p{};
+  const auto refuse = [&p](const char* msg) { p.status = PISO_ERR_INVALID_ARG; p.msg = msg; return p; };
+  p.g = conv_geom(q.H, q.W, q.cin, q.cout, q.ks, q.pad);
+  const ConvGeom& g = p.g;
+  const int cin = q.cin, cout = q.cout, ks = q.ks;
+  const bool sizes_ok = g.Ho >= 1 && g.Wo >= 1 && cin >= 1 && cout >= 1 && cout <= 64 && cin <= 64;
+  const bool lds = q.conv_lds != 0;                          // (option conv_lds 0: the direct kernels)
+  p.entry = q.entry; p.KS = ks; p.NT = round_up(cout, 16) / 16; p.grid_y = 1; p.block = kConvBlock;
+  if (q.entry == CE_FORWARD) {
+    if (q.null_ptr || !sizes_ok || (cin > 4 && cin % 16 != 0))
+      return refuse("piso_conv2d_forward: invalid argument (channels: 1..4 or a multiple of 16 up to 64 in, 1..64 out; kernel size 1 | 3 | 5 | 7)");
+    p.C = padded_cin(cin);
+    if (conv_fwd_loads16(p.C) && q.operands_off16)
+      return refuse("piso_conv2d_forward: invalid argument (with more than 4 input channels `in` and `w_laid_out` must be 16-byte aligned)");
+    if (!conv_with_shape<kConvFwd>(ks, p.C, p.NT, [](auto) {})) return refuse("piso_conv2d_forward: this (kernel size, channels) combination is not instantiated");
+    p.family = lds && conv_fwd_has_lds(ks, p.C) ? CF_FWD_LDS : CF_FWD_DIRECT;
+    p.leaky = q.leaky != 0;
+    p.grid_x = ceil_div(ceil_div(g.Wo, 64) * g.Ho, kConvBlock / 64);       // a wave owns a tile of 64 pixels of one output row
+    return p;
+  }
+  if (q.null_ptr || !sizes_ok || q.workspace_bytes < conv_wgrad_workspace_bytes(ks, cin, cout)) return refuse("piso_conv2d_wgrad: invalid argument");
+  p.C = round_up(cin, 16) / 16;
+  p.reducer = conv_wg_reducer(cout);
+  if ((p.reducer == 4 && q.result_off16) || (conv_wg_loads16(cin, cout) && q.operands_off16))
+    return refuse("piso_conv2d_wgrad: invalid argument (cout % 4 == 0: `dw` and `workspace` must be 16-byte aligned; cin % 4 == 0 as well: `in` and `grad_out` too)");
+  // grid y: the work items of a band - (tap, 16-channel tile of ci); PACK4: (ky, group of 4 kx) - over workgroups of four waves x IPW items
+  if (conv_wg_is_64(ks, cin, cout)) {
+    p.IPW = kConvWg64.IPW; p.family = lds ? CF_WG_64_LDS : CF_WG_64;
+    p.grid_y = ks; p.block = 64 * ks;
+  } else if (conv_wg_is_pack4(ks, cin, p.NT)) {
+    p.IPW = kConvWgPack4.IPW; p.family = CF_WG_PACK4;
+    p.grid_y = ceil_div(ks * ceil_div(ks, 4), 4 * p.IPW);
+  } else if (conv_with_shape<kConvWg>(ks, p.C, p.NT, [&p](auto i) { p.IPW = kConvWg[i].IPW; })) {
+    p.family = lds && conv_wg_loads16(cin, cout) ? CF_WG_GENERIC_LDS : CF_WG_GENERIC;
+    p.grid_y = ceil_div(ks * ks * p.C, 4 * p.IPW);
+  } else {
+    return refuse("piso_conv2d_wgrad: this (kernel size, channels) combination is not instantiated");
+  }
+  p.rows_per_block = ceil_div(g.Ho, kWgradMaxBlocks);
+  p.grid_x = p.nblocks = ceil_div(g.Ho, p.rows_per_block);
+  const int n = ks * ks * cin * cout;                        // the reducers: 64 weights (scalar) or 64 x 4 (4-wide) per workgroup
+  p.reduce_grid = p.reducer == 4 ? ceil_div(n / 4, 64) : ceil_div(n, 64);
+  return p;
+}
+
+}  // namespace piso

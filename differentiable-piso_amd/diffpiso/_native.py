@@ -237,6 +237,15 @@ def cg_last_xcd_map():
     return tuple(buf[i] for i in range(min(n, 256)))
 
 
+def _last_dispatch(fn, name, fields):
+    """The record a piso_*_last_dispatch function of the library keeps for the calling thread, as a dict over `fields`; {} if it has none."""
+    buf = (C.c_int * 32)()
+    n = fn(buf, 32)
+    if n != 0 and n != len(fields):
+        raise PisoNativeError("%s returned %d fields, this binding knows %d" % (name, n, len(fields)))
+    return {k: buf[i] for i, k in enumerate(fields[:n])}
+
+
 DISPATCH_FIELDS = ("path", "sizeof_T", "sizeof_CT", "V", "RECON", "symmetric", "rows_per_wave", "k1_grid", "k1_tiles", "R", "NQ", "waves",
                    "launch_grid", "padded", "xcd_local", "fell_back", "tiny_per_x", "k2_grid", "segments")
 
@@ -244,11 +253,7 @@ DISPATCH_FIELDS = ("path", "sizeof_T", "sizeof_CT", "V", "RECON", "symmetric", "
 def cg_last_dispatch():
     """Which kernel instance this thread's last pressure CG solve was dispatched to (include/piso_hip.h: piso_cg_last_dispatch),
     as a dict; {} if the thread has not solved."""
-    buf = (C.c_int * 32)()
-    n = lib.piso_cg_last_dispatch(buf, 32)
-    if n != 0 and n != len(DISPATCH_FIELDS):
-        raise PisoNativeError("piso_cg_last_dispatch returned %d fields, this binding knows %d" % (n, len(DISPATCH_FIELDS)))
-    return {k: buf[i] for i, k in enumerate(DISPATCH_FIELDS[:n])}
+    return _last_dispatch(lib.piso_cg_last_dispatch, "piso_cg_last_dispatch", DISPATCH_FIELDS)
 
 
 BICGSTAB_DISPATCH_FIELDS = ("sizeof_T", "E", "sweep_lds", "factor_lds", "R", "bands_u", "bands_v", "blocks", "fold", "fuse_p", "transpose_flags",
@@ -258,11 +263,7 @@ BICGSTAB_DISPATCH_FIELDS = ("sizeof_T", "E", "sweep_lds", "factor_lds", "R", "ba
 def bicgstab_last_dispatch():
     """Which kernel instances this thread's last ILU(0)-BiCGStab solve ran (include/piso_hip.h: piso_bicgstab_last_dispatch), as a dict;
     {} if the thread has not solved or its last call was refused."""
-    buf = (C.c_int * 32)()
-    n = lib.piso_bicgstab_last_dispatch(buf, 32)
-    if n != 0 and n != len(BICGSTAB_DISPATCH_FIELDS):
-        raise PisoNativeError("piso_bicgstab_last_dispatch returned %d fields, this binding knows %d" % (n, len(BICGSTAB_DISPATCH_FIELDS)))
-    return {k: buf[i] for i, k in enumerate(BICGSTAB_DISPATCH_FIELDS[:n])}
+    return _last_dispatch(lib.piso_bicgstab_last_dispatch, "piso_bicgstab_last_dispatch", BICGSTAB_DISPATCH_FIELDS)
 
 
 CONV_DISPATCH_FIELDS = ("entry", "KS", "C", "NT", "IPW", "family", "leaky", "grid_x", "grid_y", "block", "rows_per_block", "nblocks", "reducer",
@@ -272,11 +273,7 @@ CONV_DISPATCH_FIELDS = ("entry", "KS", "C", "NT", "IPW", "family", "leaky", "gri
 def conv_last_dispatch():
     """Which kernel instance this thread's last piso_conv2d_forward / piso_conv2d_wgrad ran (include/piso_hip.h: piso_conv_last_dispatch),
     as a dict; {} if the thread has not run a convolution."""
-    buf = (C.c_int * 32)()
-    n = lib.piso_conv_last_dispatch(buf, 32)
-    if n != 0 and n != len(CONV_DISPATCH_FIELDS):
-        raise PisoNativeError("piso_conv_last_dispatch returned %d fields, this binding knows %d" % (n, len(CONV_DISPATCH_FIELDS)))
-    return {k: buf[i] for i, k in enumerate(CONV_DISPATCH_FIELDS[:n])}
+    return _last_dispatch(lib.piso_conv_last_dispatch, "piso_conv_last_dispatch", CONV_DISPATCH_FIELDS)
 
 
 MG_DISPATCH_FIELDS = ("levels", "tail_first", "sweeps", "iterations", "cycles", "residual_recomputations")
@@ -284,8 +281,4 @@ MG_DISPATCH_FIELDS = ("levels", "tail_first", "sweeps", "iterations", "cycles", 
 
 def mg_last_dispatch():
     """What this thread's last multigrid solve / cycle ran (include/piso_hip.h: piso_mg_last_dispatch), as a dict; {} if none."""
-    buf = (C.c_int * 32)()
-    n = lib.piso_mg_last_dispatch(buf, 32)
-    if n != 0 and n != len(MG_DISPATCH_FIELDS):
-        raise PisoNativeError("piso_mg_last_dispatch returned %d fields, this binding knows %d" % (n, len(MG_DISPATCH_FIELDS)))
-    return {k: buf[i] for i, k in enumerate(MG_DISPATCH_FIELDS[:n])}
+    return _last_dispatch(lib.piso_mg_last_dispatch, "piso_mg_last_dispatch", MG_DISPATCH_FIELDS)

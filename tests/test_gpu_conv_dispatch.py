@@ -1,6 +1,6 @@
 """Which kernel instance does a closure convolution run, and is every instance, seam and edge of csrc/conv.hip right - term by term?
 
-piso_conv2d_forward / piso_conv2d_wgrad pick (csrc/conv.hip: launch_forward, launch_wgrad, piso_conv2d_wgrad)
+piso_conv2d_forward / piso_conv2d_wgrad pick (csrc/conv_dispatch.h: conv_plan, the instance table)
   forward  the instance (KS, CINP, NT) of conv_forward_kernel, or of conv_forward_lds_kernel where CINP >= 16, KS >= 3 and option conv_lds is
            not 0; LEAKY as asked; one workgroup per four 64-pixel tiles
   wgrad    PACK4 (7 x 7, cin <= 4), conv_wgrad64[_lds]_kernel (3 x 3, 64 -> 64) or the generic instance (KS, MTI, NT, IPW), staged through LDS
@@ -472,6 +472,35 @@ def test_leaky_relu_backward_matches_torch_bitwise(n):
 
 
 # ---- refusals launch nothing: status PISO_ERR_INVALID_ARG, the record and the output untouched
+# name, entry, pointers (fwd: in, w_laid_out, out; wg: in, grad_out, dw, workspace - "p" a valid one, "0" NULL, "+4" four bytes off 16-byte
+# alignment), H, W, cin, cout, ks, pad, wg: workspace_bytes ("nbytes": what 5 x 5 16 -> 16 needs, "short": one byte less, "roomy": what
+# 5 x 5 64 -> 64 needs - enough for every shape below, were it to launch)
+REFUSALS = [("null in", "fwd", "0 p p", 6, 20, 16, 16, 5, 2), ("null w", "fwd", "p 0 p", 6, 20, 16, 16, 5, 2), ("null out", "fwd", "p p 0", 6, 20, 16, 16, 5, 2),
+            ("Ho < 1", "fwd", "p p p", 4, 20, 16, 16, 5, 0), ("Wo < 1", "fwd", "p p p", 6, 3, 16, 16, 5, 0), ("cin 5", "fwd", "p p p", 6, 20, 5, 16, 5, 2),
+            ("cin 0", "fwd", "p p p", 6, 20, 0, 16, 5, 2), ("cout 65", "fwd", "p p p", 6, 20, 16, 65, 5, 2), ("cout 0", "fwd", "p p p", 6, 20, 16, 0, 5, 2),
+            ("cin 80", "fwd", "p p p", 6, 20, 80, 16, 5, 2), ("not instantiated 5x5 64>64", "fwd", "p p p", 6, 20, 64, 64, 5, 2),
+            ("not instantiated 2x2", "fwd", "p p p", 6, 20, 16, 16, 2, 0), ("in off 16-byte alignment", "fwd", "+4 p p", 6, 20, 16, 16, 5, 2),
+            ("w off 16-byte alignment", "fwd", "p +4 p", 6, 20, 16, 16, 5, 2),
+            ("wg null in", "wg", "0 p p p", 6, 20, 16, 16, 5, 2, "nbytes"), ("wg null g", "wg", "p 0 p p", 6, 20, 16, 16, 5, 2, "nbytes"),
+            ("wg null dw", "wg", "p p 0 p", 6, 20, 16, 16, 5, 2, "nbytes"), ("wg null workspace", "wg", "p p p 0", 6, 20, 16, 16, 5, 2, "nbytes"),
+            ("wg workspace one byte short", "wg", "p p p p", 6, 20, 16, 16, 5, 2, "short"), ("wg Ho < 1", "wg", "p p p p", 4, 20, 16, 16, 5, 0, "nbytes"),
+            ("wg Wo < 1", "wg", "p p p p", 6, 4, 16, 16, 5, 0, "nbytes"), ("wg cout 65", "wg", "p p p p", 6, 20, 16, 65, 5, 2, "roomy"),
+            ("wg cin 65", "wg", "p p p p", 6, 20, 65, 16, 5, 2, "roomy"), ("wg cin 0", "wg", "p p p p", 6, 20, 0, 16, 5, 2, "nbytes"),
+            ("wg not instantiated 5x5 64>64", "wg", "p p p p", 6, 20, 64, 64, 5, 2, "roomy"), ("wg not instantiated 7x7 4>32", "wg", "p p p p", 9, 20, 4, 32, 7, 3, "roomy"),
+            ("wg in off 16-byte alignment", "wg", "+4 p p p", 6, 20, 16, 16, 5, 2, "nbytes"), ("wg g off 16-byte alignment", "wg", "p +4 p p", 6, 20, 16, 16, 5, 2, "nbytes"),
+            ("wg dw off 16-byte alignment", "wg", "p p +4 p", 6, 20, 16, 16, 5, 2, "nbytes"),
+            ("wg workspace off 16-byte alignment", "wg", "p p p +4", 6, 20, 16, 16, 5, 2, "nbytes")]
+assert len({c[0] for c in REFUSALS}) == len(REFUSALS) == 30
+
+
+def workspace_bytes(ks, cin, cout):
+    """include/piso_hip.h: 256 band partials of [ks][ks][cin rounded up to 16][cout rounded up to 16] floats."""
+    return 256 * ks * ks * (-(-cin // 16) * 16) * (-(-cout // 16) * 16) * 4
+
+
+REFUSAL_BYTES = {"nbytes": workspace_bytes(5, 16, 16), "short": workspace_bytes(5, 16, 16) - 1, "roomy": workspace_bytes(5, 64, 64)}
+
+
 @pytest_gpu
 def test_refusals_leave_record_and_output_untouched(piso_option):
     import diffpiso._native as N
@@ -482,40 +511,29 @@ def test_refusals_leave_record_and_output_untouched(piso_option):
     before = N.conv_last_dispatch()
     assert before["entry"] == 1 and before["KS"] == 5
 
-    def fwd_call(in_, wl, out, H, W, cin, cout, ks, pad):
-        return N.lib.piso_conv2d_forward(in_, wl, out, H, W, cin, cout, ks, pad, 0, N.stream_ptr())
-
     big = torch.zeros(1 << 20, dtype=torch.float32, device="cuda")            # operands large enough for every shape below, were it to launch
     buf, out = _guarded(1 << 16)
+    assert N.lib.piso_conv2d_wgrad_workspace_bytes(5, 16, 16) == REFUSAL_BYTES["nbytes"] and N.lib.piso_conv2d_wgrad_workspace_bytes(5, 64, 64) == REFUSAL_BYTES["roomy"]
+    ws = torch.empty(REFUSAL_BYTES["roomy"], dtype=torch.uint8, device="cuda")
     p, po = C.c_void_p(big.data_ptr()), C.c_void_p(out.data_ptr())
-    off4 = C.c_void_p(big.data_ptr() + 4)
-    cases = {"null in": fwd_call(None, p, po, 6, 20, 16, 16, 5, 2), "null w": fwd_call(p, None, po, 6, 20, 16, 16, 5, 2), "null out": fwd_call(p, p, None, 6, 20, 16, 16, 5, 2),
-             "Ho < 1": fwd_call(p, p, po, 4, 20, 16, 16, 5, 0), "Wo < 1": fwd_call(p, p, po, 6, 3, 16, 16, 5, 0), "cin 5": fwd_call(p, p, po, 6, 20, 5, 16, 5, 2),
-             "cin 0": fwd_call(p, p, po, 6, 20, 0, 16, 5, 2), "cout 65": fwd_call(p, p, po, 6, 20, 16, 65, 5, 2), "cout 0": fwd_call(p, p, po, 6, 20, 16, 0, 5, 2),
-             "cin 80": fwd_call(p, p, po, 6, 20, 80, 16, 5, 2), "not instantiated 5x5 64>64": fwd_call(p, p, po, 6, 20, 64, 64, 5, 2),
-             "not instantiated 2x2": fwd_call(p, p, po, 6, 20, 16, 16, 2, 0), "in off 16-byte alignment": fwd_call(off4, p, po, 6, 20, 16, 16, 5, 2),
-             "w off 16-byte alignment": fwd_call(p, off4, po, 6, 20, 16, 16, 5, 2)}
-    nbytes = N.lib.piso_conv2d_wgrad_workspace_bytes(5, 16, 16)
-    roomy = N.lib.piso_conv2d_wgrad_workspace_bytes(5, 64, 64)                 # enough for every shape below, were it to launch
-    ws = torch.empty(roomy, dtype=torch.uint8, device="cuda")
-    pw = C.c_void_p(ws.data_ptr())
 
-    def wg_call(in_, g, dw, H, W, cin, cout, ks, pad, wsp=pw, nb=nbytes):
-        return N.lib.piso_conv2d_wgrad(in_, g, dw, H, W, cin, cout, ks, pad, wsp, C.c_size_t(nb), N.stream_ptr())
+    def pointer(token, base):
+        return None if token == "0" else C.c_void_p(base + 4) if token == "+4" else C.c_void_p(base)
 
-    cases.update({"wg null in": wg_call(None, p, po, 6, 20, 16, 16, 5, 2), "wg null g": wg_call(p, None, po, 6, 20, 16, 16, 5, 2), "wg null dw": wg_call(p, p, None, 6, 20, 16, 16, 5, 2),
-                  "wg null workspace": wg_call(p, p, po, 6, 20, 16, 16, 5, 2, wsp=None), "wg workspace one byte short": wg_call(p, p, po, 6, 20, 16, 16, 5, 2, nb=nbytes - 1),
-                  "wg Ho < 1": wg_call(p, p, po, 4, 20, 16, 16, 5, 0), "wg Wo < 1": wg_call(p, p, po, 6, 4, 16, 16, 5, 0), "wg cout 65": wg_call(p, p, po, 6, 20, 16, 65, 5, 2, nb=roomy),
-                  "wg cin 65": wg_call(p, p, po, 6, 20, 65, 16, 5, 2, nb=roomy), "wg cin 0": wg_call(p, p, po, 6, 20, 0, 16, 5, 2),
-                  "wg not instantiated 5x5 64>64": wg_call(p, p, po, 6, 20, 64, 64, 5, 2, nb=roomy), "wg not instantiated 7x7 4>32": wg_call(p, p, po, 9, 20, 4, 32, 7, 3, nb=roomy),
-                  "wg in off 16-byte alignment": wg_call(off4, p, po, 6, 20, 16, 16, 5, 2), "wg g off 16-byte alignment": wg_call(p, off4, po, 6, 20, 16, 16, 5, 2),
-                  "wg dw off 16-byte alignment": wg_call(p, p, C.c_void_p(out.data_ptr() + 4), 6, 20, 16, 16, 5, 2),
-                  "wg workspace off 16-byte alignment": wg_call(p, p, po, 6, 20, 16, 16, 5, 2, wsp=C.c_void_p(ws.data_ptr() + 4), nb=nbytes)})
+    cases = {}
+    for name, entry, ptrs, H, W, cin, cout, ks, pad, *nb in REFUSALS:
+        t = ptrs.split()
+        a = [pointer(t[0], big.data_ptr()), pointer(t[1], big.data_ptr()), pointer(t[2], out.data_ptr())]
+        if entry == "fwd":
+            cases[name] = N.lib.piso_conv2d_forward(a[0], a[1], a[2], H, W, cin, cout, ks, pad, 0, N.stream_ptr())
+        else:
+            cases[name] = N.lib.piso_conv2d_wgrad(a[0], a[1], a[2], H, W, cin, cout, ks, pad, pointer(t[3], ws.data_ptr()), C.c_size_t(REFUSAL_BYTES[nb[0]]), N.stream_ptr())
     for n_null in ("g", "out", "gp"):
         a = [p, p, po]
         a["g out gp".split().index(n_null)] = None
         cases["leaky null " + n_null] = N.lib.piso_leaky_relu_backward(a[0], a[1], a[2], C.c_size_t(16), N.stream_ptr())
     torch.cuda.synchronize()
+    assert len(cases) == 33
     assert {k: v for k, v in cases.items() if v != INVALID} == {}
     assert N.conv_last_dispatch() == before
     assert bool((buf == SENTINEL).all())
@@ -576,6 +594,50 @@ def test_table_literals_agree_with_the_dispatch_rules(rid):
     want = expected_record(r["entry"], r["H"], r["W"], r["cin"], r["cout"], r["ks"], r["pad"], r["lds"])
     want["leaky"] = r["leaky"]
     assert r["expect"] == want
+
+
+def _host_compiler():
+    """A C++17 host compiler: (argv prefix, its name), or None."""
+    import shutil
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    for cxx in ("c++", "g++", "clang++", os.path.join(rocm, "llvm", "bin", "clang++"), os.path.join(rocm, "lib", "llvm", "bin", "clang++")):
+        path = shutil.which(cxx)
+        if path:
+            return [path], cxx
+    hipcc = shutil.which("hipcc") or shutil.which(os.path.join(rocm, "bin", "hipcc"))
+    return ([hipcc, "-x", "c++"], "hipcc -x c++") if hipcc else None
+
+
+def test_conv_plan_on_the_host(tmp_path):
+    """conv_plan (csrc/conv_dispatch.h) is pure: tests/conv_plan_driver.cpp, built with a host compiler from a translation unit that includes
+    nothing of HIP, plans every row of ROWS - the record it would leave must equal the row's literal expectation field for field - and every
+    case of REFUSALS (null and misaligned pointers as the query's flags): PISO_ERR_INVALID_ARG with the entry point's message."""
+    import subprocess
+    import diffpiso._native as N
+    cxx = _host_compiler()
+    if cxx is None:
+        pytest.skip("no C++17 host compiler (tried c++, g++, clang++, ROCm's clang++, hipcc -x c++)")
+    exe = str(tmp_path / "conv_plan_driver")
+    subprocess.run(cxx[0] + ["-std=c++17", "-O1", "-o", exe, os.path.join(os.path.dirname(os.path.abspath(__file__)), "conv_plan_driver.cpp")], check=True)
+    q = ["%d %d %d %d %d %d %d %d %d 0 0 0 -1" % (1 if r["entry"] == "fwd" else 2, r["H"], r["W"], r["cin"], r["cout"], r["ks"], r["pad"], r["leaky"], -1 if r["lds"] else 0)
+         for r in ROWS]
+    for name, entry, ptrs, H, W, cin, cout, ks, pad, *nb in REFUSALS:
+        t = ptrs.split()
+        q.append("%d %d %d %d %d %d %d 0 -1 %d %d %d %d" % (1 if entry == "fwd" else 2, H, W, cin, cout, ks, pad, "0" in t, "+4" in t[:2], "+4" in t[2:],
+                                                         REFUSAL_BYTES[nb[0]] if nb else 0))
+    res = subprocess.run([exe], input="\n".join(q) + "\n", capture_output=True, text=True, check=True).stdout.splitlines()
+    assert len(res) == len(ROWS) + len(REFUSALS)
+    bad = {}
+    for r, line in zip(ROWS, res):
+        status, msg, *rec = line.split("\t")
+        got = dict(zip(N.CONV_DISPATCH_FIELDS, map(int, rec)))
+        if (status, msg) != ("0", "-") or len(rec) != len(N.CONV_DISPATCH_FIELDS) or got != r["expect"]:
+            bad[r["id"]] = (status, msg, got, r["expect"])
+    for (name, entry, *_), line in zip(REFUSALS, res[len(ROWS):]):
+        status, msg, *rec = line.split("\t")
+        if status != "1" or not msg.startswith("piso_conv2d_forward: " if entry == "fwd" else "piso_conv2d_wgrad: "):
+            bad[name] = (status, msg)
+    assert bad == {}, "planned with %s" % cxx[1]
 
 
 def test_record_fields_of_the_binding_are_the_header_s():
