@@ -6,6 +6,9 @@
 // (solid cells, padding): x = 0 there, it joins no aggregate, couplings into it are dropped.  A non-zero border entry in a
 // non-periodic direction (which makes the reference stencil read the neighbouring row) is refused, and so is a zero-diagonal row that
 // still has entries, and rank_deficient = 1 on a matrix whose rows do not sum to zero: PISO_ERR_UNSUPPORTED_PATTERN, never another system.
+// PRECONDITION, not checked: the present cells are CONNECTED.  A pocket of fluid enclosed by solid cells is a second null vector of L
+// (rank deficient) or a singular block (open borders); the iteration then does not converge - it runs to max_iterations with a finite x,
+// never reports fewer - and neither does the plain CG.  Detecting it on the device is not attempted.
 //
 // Hierarchy.  2 x 2 aggregation (ceil), piecewise-constant P, A_c = kGalerkin P^T A P built on the device level by level, every level
 // in the same five-array layout (couplings across an aggregate face are summed into the coarse off-diagonal, couplings inside go to the

@@ -649,6 +649,9 @@ class PisoPressureSolverMultigrid(PisoPressureSolverCudaCustom):
     iterations here (a few dozen suffice).  Measured faster than the plain solver from 256 x 256 cells up (3x at 256^2, 25 - 77x at
     2048^2; DESIGN.md 3.7 has the table); not measured on smaller grids, where the plain solver's one-workgroup kernels have no
     launch or host round trip per iteration and are the better choice.  fp64, one GPU: cast_to_double=False and a slab communicator are refused.
+    The fluid cells must be CONNECTED: a pocket of fluid enclosed by solid cells is not detected, and the solve then runs to `max_iterations`
+    without converging (as the plain solver does).  Grids whose hierarchy stops after 0 or 1 coarsenings (a dimension below 8 or 16 cells
+    next to a long one) are preconditioned poorly: ~200 iterations instead of tens.
     Forward and adjoint solves, `last_iterations`, `stats` and SimulationParameters(pressure_solver=...) work as with the plain
     solver."""
 

@@ -336,6 +336,8 @@ void piso_cg_verify_stats(long long* runs_out, int* failures_out);
  * polling cadence, and a solve is reproducible bit for bit.  NaN input never counts as converged: max_iterations, NaN in x.
  * Refused with PISO_ERR_UNSUPPORTED_PATTERN: a non-zero border entry in a non-periodic direction, a zero-diagonal row with entries,
  * rank_deficient = 1 on a matrix whose rows do not sum to zero.  nx, ny >= 4; workspace too small: PISO_ERR_INVALID_ARG.
+ * Precondition (not checked): the cells with a non-zero diagonal are connected through their couplings.  With a pocket of fluid enclosed
+ * by solid cells the solve does not converge: it returns max_iterations and a finite x (the plain CG does not solve that system either).
  * Options: "mg_tail" 0 runs the coarse levels as launches of their own instead of inside one workgroup (same result),
  * "mg_check_every" sets the iterations queued between two host looks (default 4; same result and count). */
 size_t piso_mg_workspace_bytes(int nx, int ny);

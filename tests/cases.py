@@ -144,12 +144,30 @@ def dev(a, dtype=None):
     return t.cuda()
 
 
-def laplace_case(name, ny, nx, seed, dtype=np.float64):
+def punch_solids(c, solids):
+    """Clears the cells `solids` [(j, i), ...] in the padded `active` and `accessible` masks of a case, in place, and wraps the padded
+    ring on the periodic axes afterwards: the Laplace assembly reads a cell's neighbour across the seam from the ring, and a ring that
+    still says "fluid" next to a solid seam cell leaves a coupling into the solid (an asymmetric matrix whose rows do not sum to zero)."""
+    ny, nx = c["ny"], c["nx"]
+    per_y, per_x = c["periodic_yx"]
+    for m in (c["active"], c["accessible"]):
+        for j, i in solids:
+            assert 0 <= j < ny and 0 <= i < nx, (j, i)
+            m[0, j + 1, i + 1, 0] = 0
+        if per_y:
+            m[0, 0], m[0, ny + 1] = m[0, ny].copy(), m[0, 1].copy()
+        if per_x:
+            m[0, :, 0], m[0, :, nx + 1] = m[0, :, nx].copy(), m[0, :, 1].copy()
+
+
+def laplace_case(name, ny, nx, seed, dtype=np.float64, solids=None):
     """The pressure system of a case at test size, on the host: (oracle set-up, L [nx * ny, 5] from the oracle's Laplace matrix
     of random face weights in [0.5, 1.5), assembled in `dtype`; float64 right-hand side - zero-mean where the operator is rank
-    deficient)."""
+    deficient).  `solids`: cells [(j, i), ...] made solid first (punch_solids); the right-hand side is zero there."""
     from oracle import native as O, piso_ref as R
     c = make_case(name, ny, nx, seed=seed)
+    if solids:
+        punch_solids(c, solids)
     s = oracle_setup(c)
     rng = np.random.default_rng(seed)
     a0_t = np.zeros((1, ny + 1, nx + 1, 2), f32)
@@ -165,6 +183,73 @@ def laplace_case(name, ny, nx, seed, dtype=np.float64):
     if s.rank_deficient:
         b -= b.sum() / act.sum() * act
     return s, L, b.ravel()
+
+
+def check_pressure_matrix(L, nx, ny, per_x, per_y, rank_deficient):
+    """What every solver of the pressure system may assume of a matrix with solid cells, asserted: symmetric, no coupling from a present
+    into an absent cell, no entries in a zero-diagonal row, rows that sum to zero where `rank_deficient`, and present cells that form
+    exactly ONE connected component.  -> the number of absent cells."""
+    import scipy.sparse as sp
+    from scipy.sparse.csgraph import connected_components
+    from tests.mg_reference import matrix
+    A = matrix(L, nx, ny, per_x, per_y)
+    d = A.diagonal()
+    present = d != 0
+    scale = abs(A).max()
+    assert abs(A - A.T).max() <= 1e-13 * scale, "not symmetric"
+    assert A[present][:, ~present].nnz == 0, "coupling from a present into an absent cell"
+    assert A[~present].nnz == 0, "a zero-diagonal row has entries"
+    if rank_deficient:
+        assert np.abs(A @ np.ones(nx * ny)).max() <= 1e-9 * np.abs(d[present]).mean(), "rows do not sum to zero"
+    ncomp, _ = connected_components(sp.csr_matrix(A[present][:, present]), directed=False)
+    assert ncomp == 1, "%d connected components of present cells" % ncomp
+    return int((~present).sum())
+
+
+SOLID_PATTERNS = ("none", "cell_ee", "cell_eo", "cell_oe", "cell_oo", "block2", "block4", "block8", "block2_odd", "wall", "corners",
+                  "seam", "random10")
+# seeds of "random10" by (ny, nx), re-drawn here until check_pressure_matrix passes on all four set-ups and no fluid cell is enclosed by
+# four solids (such a cell has a zero diagonal: it would be absent with a right-hand side)
+_RANDOM10_SEED = {(33, 70): 1, (130, 129): 2}
+
+
+def _block(j0, i0, h, w):
+    return [(j, i) for j in range(j0, j0 + h) for i in range(i0, i0 + w)]
+
+
+def solid_pattern(pattern, ny, nx):
+    """The named solid patterns of the multigrid tests on a grid of ny x nx: a list of (j, i).  "cell_<j parity><i parity>": one cell;
+    "block<k>": k x k cells aligned to the aggregates of level log2 k (a coarse cell with no present cell on k / 2 ... levels);
+    "block2_odd": 2 x 2 cells across four aggregates; "wall": one cell thick across most of the height, one gap; "corners": the four
+    corner cells (one 2 x 2 block across both seams where both axes are periodic); "seam": a column on each side of the x seam;
+    "random10": 10 % of the cells.  Not in SOLID_PATTERNS: "blocks_wall" (an 8 x 8 block, a 32 x 32 block and a 400-cell wall, for a grid of
+    about 1030 x 520) and "pocket" (fluid enclosed by solids: what check_pressure_matrix refuses)."""
+    j8, i8 = 8 * (ny // 16), 8 * (nx // 16)
+    if pattern == "none":
+        return []
+    if pattern.startswith("cell_"):
+        return [(j8 + 2 + (pattern[5] == "o"), i8 + 2 + (pattern[6] == "o"))]
+    if pattern in ("block2", "block4", "block8"):
+        k = int(pattern[5:])
+        return _block(j8, i8, k, k)
+    if pattern == "block2_odd":
+        return _block(j8 + 1, i8 + 1, 2, 2)
+    if pattern == "wall":
+        return [(j, nx // 2 + 1) for j in range(2, ny - 2) if j != ny // 2]
+    if pattern == "corners":
+        return [(0, 0), (0, nx - 1), (ny - 1, 0), (ny - 1, nx - 1)]
+    if pattern == "seam":
+        return [(j, i) for j in range(ny // 4, ny // 2) for i in (0, nx - 1)]
+    if pattern == "random10":
+        rng = np.random.default_rng(_RANDOM10_SEED[(ny, nx)])
+        k = rng.choice(ny * nx, size=ny * nx // 10, replace=False)
+        return [(int(c) // nx, int(c) % nx) for c in np.sort(k)]
+    if pattern == "blocks_wall":                           # (large grids: coarse cells with no present cell down to level 5)
+        return (_block(8 * (ny // 32), 8 * (nx // 32), 8, 8) + _block(32 * (ny // 64), 32 * (nx // 64), 32, 32) +
+                [(j, 3 * nx // 4 + 1) for j in range(ny // 8, ny // 8 + 401) if j != ny // 2])
+    if pattern == "pocket":                                # NOT a valid pattern: 3 x 3 fluid cells enclosed by a ring of solids
+        return [c for c in _block(j8 + 1, i8 + 1, 5, 5) if c not in _block(j8 + 2, i8 + 2, 3, 3)]
+    raise ValueError(pattern)
 
 
 def pressure_system(nx, ny, walls=False, seed=11):

@@ -1,12 +1,15 @@
 """The multigrid-preconditioned pressure CG, checked on the host through its numpy twin (tests/mg_reference.py): the cycle is a
 symmetric definite operator, the preconditioned iteration reaches the oracle's answer in tens of iterations where the plain CG of
 the oracle needs hundreds.  The GPU tests (test_gpu_mg.py) hold the HIP solver to this twin."""
+import os
+import re
+
 import numpy as np
 import pytest
 
 from oracle import native as O
 from tests import mg_reference as M
-from tests.cases import laplace_case
+from tests.cases import SOLID_PATTERNS, check_pressure_matrix, laplace_case, solid_pattern
 
 CASES = ("periodic", "xper_ywall", "cavity", "spatial_ml")
 SHAPES = ((33, 70), (64, 256), (130, 129))
@@ -106,3 +109,135 @@ def test_border_entry_in_a_non_periodic_direction_is_refused():
     L[3, 0] = 0.25                                             # a -y entry in the first row of a wall-bounded grid
     with pytest.raises(ValueError):
         M.Hierarchy(L, nx, ny, False, False)
+
+
+# ---- the plan: which hierarchy a grid gets, restated from the header of csrc/mg.hip -----------------------------------------------------
+MG_HIP = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "differentiable-piso_amd", "csrc", "mg.hip")
+# grid (nx, ny) -> (levels, tail_first): every class of hierarchy mg_plan can produce (test_gpu_mg_hierarchy.py runs each on the GPU)
+HIERARCHY_CLASSES = {(4, 4): (1, 0), (5, 7): (1, 0), (6, 600): (1, 0), (6, 700): (1, -1), (7, 1200): (2, 1), (8, 4000): (2, -1),
+                     (65, 64): (5, 1), (8, 512): (2, 0)}
+
+
+def test_constants_of_the_twin_equal_the_text_of_mg_hip():
+    text = open(MG_HIP).read()
+    want = dict(kMinDim=M.MIN_DIM, kTailCells=M.TAIL_CELLS, kTailLds=M.TAIL_LDS, kTailMaxLevels=M.TAIL_MAX_LEVELS, kMgMaxLevels=M.MAX_LEVELS,
+                kCoarsestSweeps=M.COARSEST_SWEEPS, kOmega=M.OMEGA, kGalerkin=M.S_GALERKIN, kGuard=M.GUARD)
+    for name, value in want.items():
+        found = re.findall(r"constexpr\s+(?:int|double)\s+%s\s*=\s*([-+0-9.eE]+)\s*;" % name, text)
+        assert len(found) == 1, (name, found)
+        assert float(found[0]) == value, (name, found[0], value)
+
+
+@pytest.mark.parametrize("grid", sorted(HIERARCHY_CLASSES))
+def test_plan_gives_every_class_of_hierarchy(grid):
+    for nx, ny in (grid, grid[::-1]):
+        sizes, tail_first = M.plan(nx, ny)
+        assert (len(sizes), tail_first) == HIERARCHY_CLASSES[grid], (nx, ny, sizes, tail_first)
+        H = M.Hierarchy(np.tile([0.0, 0.0, -1.0, 0.0, 0.0], (nx * ny, 1)), nx, ny, False, False)
+        assert [(lv[2], lv[3]) for lv in H.levels] == sizes
+    assert M.plan(64, 64)[1] == 0 and M.plan(63, 65)[1] == 0 and M.plan(65, 63)[1] == 0     # the largest level-0 tails
+
+
+def test_the_tail_starts_at_level_zero_whenever_level_zero_fits():
+    """mg_tail's three static arrays (r and z of kTailLds cells, a scratch of kTailCells) rest on this: once level 0 has at most kTailCells
+    cells, neither the LDS budget nor the level count binds."""
+    worst_cells, worst_levels, walked = 0, 0, 0
+    for nx in range(M.MIN_DIM, M.TAIL_CELLS // M.MIN_DIM + 1):
+        for ny in range(M.MIN_DIM, M.TAIL_CELLS // nx + 1):
+            sizes, tail_first = M.plan(nx, ny)
+            assert tail_first == 0, (nx, ny, sizes)
+            worst_cells = max(worst_cells, sum(a * b for a, b in sizes))
+            worst_levels = max(worst_levels, len(sizes))
+            walked += 1
+    print("%d grids: at most %d tail cells (kTailLds %d), at most %d levels (kTailMaxLevels %d)"
+          % (walked, worst_cells, M.TAIL_LDS, worst_levels, M.TAIL_MAX_LEVELS))
+    assert worst_cells <= M.TAIL_LDS and worst_levels <= M.TAIL_MAX_LEVELS and walked > 10000
+
+
+# ---- solid cells ---------------------------------------------------------------------------------------------------------------------
+def _solid_system(name, shape, pattern, seed=3):
+    ny, nx = shape
+    s, L, b = laplace_case(name, ny, nx, seed, solids=solid_pattern(pattern, ny, nx))
+    per_y, per_x = (bool(v) for v in s.periodic_yx)
+    rd = bool(s.rank_deficient)
+    L = np.asarray(L, np.float64).reshape(-1, 5)
+    absent = check_pressure_matrix(L, nx, ny, per_x, per_y, rd)
+    assert np.all(b[L[:, 2] == 0] == 0)
+    return L, b, nx, ny, per_x, per_y, rd, absent
+
+
+@pytest.mark.parametrize("pattern", SOLID_PATTERNS)
+@pytest.mark.parametrize("shape", ((33, 70), (130, 129)))
+@pytest.mark.parametrize("name", CASES)
+def test_twin_with_solid_cells(name, shape, pattern):
+    L, b, nx, ny, per_x, per_y, rd, absent = _solid_system(name, shape, pattern)
+    H = M.Hierarchy(L, nx, ny, per_x, per_y)
+    present = L[:, 2] != 0
+    assert H.dead(0) == absent >= len(solid_pattern(pattern, ny, nx)) - (nx if name == "cavity" else 0)
+    assert np.array_equal(H.level_rows(0)[0], L)
+    rng = np.random.default_rng(1)
+    a, c = rng.standard_normal(nx * ny), rng.standard_normal(nx * ny)
+    za, zc = H.cycle(a), H.cycle(c)
+    assert abs(za @ c - a @ zc) <= 1e-12 * np.linalg.norm(a) * np.linalg.norm(c)
+    assert np.all(za[~present] == 0) and za @ a < 0 and zc @ c < 0
+    acc = 1e-10
+    x, it = M.pcg(L, b, nx, ny, per_x, per_y, acc, 200, rd, H=H)
+    # (the plain CG recomputes its residual every 1000 iterations here: with none it stagnates at 1e-5 on some of these patterns, e.g.
+    # xper_ywall 130 x 129 "cell_oe" and "wall" - solid cells make the shifted system singular and its recurrence drifts)
+    xo, ito = O.cg_solve(nx, ny, per_x, per_y, L, b, 1e-12, 50000, rd, 1000)
+    first, second, floor = M.residuals(L, b, x, nx, ny, per_x, per_y, rd)
+    print("%s %s %s: %d absent cells, dead per level %s, multigrid PCG %d iterations, plain CG %d; true residual %.2e, c sum(x) - mean(b) %.2e"
+          % (name, shape, pattern, absent, [H.dead(l) for l in range(len(H.levels))], it, ito, first, second))
+    assert it < 200 and ito < 50000
+    assert first < acc and second <= floor
+    d = (x - xo)[present]
+    if rd:
+        d = d - d.mean()
+    assert np.abs(d).max() <= 1e-8 * np.abs(xo).max()
+    assert np.all(x[~present] == 0)
+
+
+def test_aligned_blocks_kill_coarse_cells_level_by_level():
+    """What the named blocks are for: a k x k block aligned to the aggregates leaves a coarse cell with no present cell on log2 k levels."""
+    for pattern, want in (("cell_ee", [1, 0, 0, 0]), ("block2", [4, 1, 0, 0]), ("block4", [16, 4, 1, 0]), ("block8", [64, 16, 4, 1]),
+                          ("block2_odd", [4, 0, 0, 0])):
+        L, b, nx, ny, per_x, per_y, rd, absent = _solid_system("periodic", (130, 129), pattern)
+        H = M.Hierarchy(L, nx, ny, per_x, per_y)
+        assert [H.dead(l) for l in range(4)] == want, pattern
+
+
+def test_solid_on_a_periodic_seam_needs_the_wrapped_ring():
+    """Without the wrap of the padded ring the Laplace assembly keeps the coupling from the cell across the seam into the solid: an
+    asymmetric matrix whose rows do not sum to zero.  The twin takes it silently (the coupling multiplies x = 0) and the HIP solver
+    refuses it where rank deficient (test_gpu_mg_hierarchy.py): the two are NOT the same function on such input, so no test feeds it."""
+    from oracle import piso_ref as R
+    from tests import cases
+    ny, nx = 33, 70
+    c = cases.make_case("periodic", ny, nx, seed=3)
+    for m in (c["active"], c["accessible"]):
+        m[0, 10 + 1, 0 + 1, 0] = 0                              # cell (10, 0), ring left alone
+    s = cases.oracle_setup(c)
+    a0 = np.ones((1, ny + 1, nx + 1, 2), np.float32)
+    L = O.laplace_matrix(nx, ny, s.active, s.accessible, R.flatten_staggered(a0, False), np.float64).reshape(-1, 5)
+    assert L[10 * nx, 2] == 0 and L[10 * nx + nx - 1, 3] != 0     # (10, nx - 1) still couples into it across the seam
+    with pytest.raises(AssertionError, match="not symmetric"):
+        check_pressure_matrix(L, nx, ny, True, True, True)
+    L2 = laplace_case("periodic", ny, nx, 3, solids=[(10, 0)])[1].reshape(-1, 5)
+    assert L2[10 * nx, 2] == 0 and L2[10 * nx + nx - 1, 3] == 0
+    check_pressure_matrix(L2, nx, ny, True, True, True)
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_an_enclosed_fluid_pocket_is_outside_the_solvers_domain(name):
+    """Present cells must be CONNECTED.  A pocket of fluid enclosed by solids is a second null vector (rank deficient) or a singular block
+    (open borders: the pocket has no Dirichlet side); the checker refuses it, and the twin - like the plain CG - does not converge on it."""
+    ny, nx = 33, 70
+    s, L, b = laplace_case(name, ny, nx, 3, solids=solid_pattern("pocket", ny, nx))
+    per_y, per_x = (bool(v) for v in s.periodic_yx)
+    rd = bool(s.rank_deficient)
+    with pytest.raises(AssertionError, match="2 connected components"):
+        check_pressure_matrix(L, nx, ny, per_x, per_y, rd)
+    hist = []
+    x, it = M.pcg(L, b, nx, ny, per_x, per_y, 1e-10, 50, rd, history=hist)
+    print("%s pocket: recurred residual after 50 iterations %.2e (smallest on the way %.2e)" % (name, hist[-1], min(hist)))
+    assert it == 50 and len(hist) == 50 and min(hist) > 1e-10
