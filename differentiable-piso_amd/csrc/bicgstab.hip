@@ -1058,11 +1058,7 @@ struct BiRun {
   }
   int F(int stage) const { return pl.fold_ok ? stage + 1 : 0; }         // a stage as a launch's `fold` argument (0: stages are launches)
   BiPeer next_seq() { BiPeer b = bp; if (pl.slab) b.seq = ++pc->seq_ar; return b; }
-  int exchange_on(T* vec, hipStream_t st) {
-    if (pl.rccl) return comm_rccl_exchange_segments(pc, vec, sizeof(T) == 8 ? 1 : 0, msgs, st);
-    peer_exchange_segments<T><<<2, 256, 0, st>>>(bp.pv, vec, msgs[0], msgs[1], msgs[2], msgs[3], ++pc->seq_ex, pc->err);
-    return PISO_OK;
-  }
+  int exchange_on(T* vec, hipStream_t st) { return comm_exchange_segments(pc, vec, sizeof(T) == 8 ? 1 : 0, msgs, st); }
   int halo(T* vec) { return pl.slab ? exchange_on(vec, stream) : PISO_OK; }
   // one stage of the scalar recurrences (peer transport / one GPU: one launch; RCCL: the ranks' sums, an all-reduce, the rest)
   int scalar(int stage) {
@@ -1070,7 +1066,7 @@ struct BiRun {
     if (pl.slab && pl.rccl) {
       BiPeer b = bp;
       b.on = 2; bi_scalar<T><<<2, kBlock, 0, stream>>>(sa, stage, b);
-      { const int rc = comm_rccl_allreduce_f64(pc, bp.gsum, 8, stream); if (rc != PISO_OK) return rc; }
+      { const int rc = comm_allreduce_f64(pc, bp.gsum, 8, stream); if (rc != PISO_OK) return rc; }
       b.on = 3; bi_scalar<T><<<2, kBlock, 0, stream>>>(sa, stage, b);
     } else {
       bi_scalar<T><<<2, kBlock, 0, stream>>>(sa, stage, next_seq());
@@ -1111,7 +1107,6 @@ struct BiRun {
   }
   int pass(int max_it, bool& pattern_checked);
   int solve(float tol, int max_it);
-  int agree();
 };
 
 // the workspace, cut into the arrays of BiArgs (bi_workspace_bytes is the size of it)
@@ -1174,7 +1169,7 @@ template <typename T>
 int BiRun<T>::setup(const T* val, const int* rowptr, const int* col, const T* x0) {
   bi_init_scalars<T><<<1, 256, 0, stream>>>(a);
   bi_convert<T><<<grid_v(), kBlock, 0, stream>>>(a, val, rowptr, col, x0, pl.transpose);
-  if (pl.slab && pl.rccl) { const int rc = comm_rccl_allreduce_i32(pc, a.flags, 2, stream); if (rc != PISO_OK) return rc; }   // (sums: non-zero = set)
+  if (pl.slab && pl.rccl) { const int rc = comm_allreduce_i32(pc, a.flags, 2, stream); if (rc != PISO_OK) return rc; }   // (sums: non-zero = set)
   else if (pl.slab) bi_flags_allreduce<T><<<1, 64, 0, stream>>>(a, next_seq());
   launch_factor<T>(pl, a, stream);
   PISO_LAUNCH_CHECK();
@@ -1260,20 +1255,6 @@ int BiRun<T>::solve(float tol, int max_it) {
   return PISO_OK;
 }
 
-// peer transport: every rank returns the same status
-template <typename T>
-int BiRun<T>::agree() {
-  int herr = 0;
-  peer_agree_on_error<><<<1, 64, 0, stream>>>(bp.pv, pc->err, ++pc->seq_ar);
-  PISO_HIP_CHECK(hipMemcpyAsync(&herr, pc->err, sizeof(int), hipMemcpyDeviceToHost, stream));
-  PISO_HIP_CHECK(hipStreamSynchronize(stream));
-  if (herr) {
-    PISO_HIP_CHECK(hipMemsetAsync(pc->err, 0, sizeof(int), stream));
-    set_error_msg("piso_multi_bicgstab_ilu_slab: a wait on a peer's mailbox gave up (peer process gone or not running?)");
-    return PISO_ERR_HIP;
-  }
-  return PISO_OK;
-}
 template struct BiRun<float>;
 template struct BiRun<double>;
 
@@ -1300,7 +1281,7 @@ static int bi_solve(const T* val, const int* rowptr, const int* col, const T* rh
     set_error_msg("piso_multi_bicgstab_ilu: workspace too small");
     return PISO_ERR_INVALID_ARG;
   }
-  if (pc && pc->transport == TRANSPORT_PEER && !pc->connected) { set_error_msg("piso_multi_bicgstab_ilu_slab: the peer communicator is not connected"); return PISO_ERR_INVALID_ARG; }
+  if (pc) { const int rc = comm_ready(pc, "piso_multi_bicgstab_ilu_slab: the peer communicator is not connected"); if (rc != PISO_OK) return rc; }
   const RowMap M = make_row_map(slab_rows, nx, ny, per_x, per_y);
   const size_t ntot = (size_t)M.n_u + M.n_v;                 // elements of a vector as stored (one GPU: the whole grid's face rows)
   BiQuery q;
@@ -1321,7 +1302,8 @@ static int bi_solve(const T* val, const int* rowptr, const int* col, const T* rh
   record_dispatch(pl, sizeof(T), max_it);
   { const int rc = run.setup(val, rowptr, col, x0); if (rc != PISO_OK) return rc; }
   { const int rc = run.solve(tol, max_it); if (rc != PISO_OK) return rc; }
-  if (pl.slab && !pl.rccl) { const int rc = run.agree(); if (rc != PISO_OK) return rc; }
+  // peer transport: every rank returns the same status (true: the sums of a slab solve go through the mailbox even in a ring of one)
+  if (pl.slab && !pl.rccl) { const int rc = comm_agree(pc, "piso_multi_bicgstab_ilu_slab", stream, true); if (rc != PISO_OK) return rc; }
   PISO_HIP_CHECK(hipStreamSynchronize(stream));
   if (run.host.flags[1] && warning) {
     const uint8_t one = 1;

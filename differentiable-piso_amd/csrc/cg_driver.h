@@ -85,7 +85,6 @@ struct CgLoop {
   bool pending = false;                                  // x still lacks alpha_k p_k of the last executed iteration
   bool finished = false;
 };
-#define PISO_TRY(expr) do { const int _rc = (expr); if (_rc != PISO_OK) return _rc; } while (0)
 
 template <typename Link>
 inline int cg_iterate(Link& link, int total, int reset, bool fixed, int* iterations_out) {

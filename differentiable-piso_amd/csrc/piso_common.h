@@ -35,6 +35,9 @@ void set_error_msg(const char* what);
     }                                                         \
   } while (0)
 
+// pass a status that is not PISO_OK on to the caller
+#define PISO_TRY(expr) do { const int _rc = (expr); if (_rc != PISO_OK) return _rc; } while (0)
+
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // Bump allocator over the caller-provided workspace.

@@ -1,4 +1,4 @@
-// The communicator of the slab-decomposed solvers (cg_slab.hip, bicgstab.hip): RCCL or peer-mapped mailboxes (peer.h).
+// The communicator of the slab-decomposed solvers and the sharded step: RCCL or peer-mapped mailboxes (peer.h).  Interface of comm.hip.
 #pragma once
 #include <rccl/rccl.h>
 
@@ -30,16 +30,6 @@ struct PisoComm {
   int verify_failures = 0;            // ... and found wanting on some rank: restarted on the two-kernel iteration
 };
 
-// RCCL transport of what the peer kernels do through the mailboxes (defined in cg_slab.hip, where the RCCL entry points live):
-//   * the four halo messages of a globally indexed vector {to upper, to lower, from lower, from upper}: grouped send / recv of the
-//     segments, straight from / into the vector (no staging).  Sends and receives between one pair of ranks are matched in issue
-//     order, and with one or two ranks the lower and the upper neighbour are the same peer: every rank issues "to upper" before
-//     "to lower" and "from lower" before "from upper".  dtype: 0 float, 1 double, 2 int32;
-//   * in-place sum of `count` doubles / ints over the ranks.
-int comm_rccl_exchange_segments(PisoComm* pc, void* vec, int dtype, const HaloMsg* m4, hipStream_t stream);
-int comm_rccl_allreduce_f64(PisoComm* pc, double* buf, int count, hipStream_t stream);
-int comm_rccl_allreduce_i32(PisoComm* pc, int* buf, int count, hipStream_t stream);
-
 inline PeerView make_view(const PisoComm* pc, bool periodic_y) {
   PeerView v;
   for (int r = 0; r < kMaxRanks; ++r) v.mbox[r] = pc->mbox[r];
@@ -49,5 +39,22 @@ inline PeerView make_view(const PisoComm* pc, bool periodic_y) {
   return v;
 }
 
+// The host collectives (comm.hip): each is the only place that chooses a transport for its job, and queues it on stream `s`.
+//   * in-place sum of `count` doubles over the ranks (one rank: nothing); of ints, and the all-gather of doubles: RCCL only;
+//   * the halo rows -1 and ny of a slab vector whose owned rows start at `row0` (nx doubles a row; neighbours by periodic_y);
+//   * the four halo messages of a globally indexed vector {to upper, to lower, from lower, from upper}, always around the ring.
+//     RCCL: grouped send / recv of the segments, straight from / into the vector (no staging).  Sends and receives between one pair
+//     of ranks are matched in issue order, and with one or two ranks the lower and the upper neighbour are the same peer: every rank
+//     issues "to upper" before "to lower" and "from lower" before "from upper" (the rows likewise).  dtype: 0 float, 1 double, 2 int32;
+//   * comm_agree: every rank returns the same status.  Peer transport with more than one rank (ring_of_one: or a caller whose sums go
+//     through the mailbox even then): the error flags are summed over the ranks (peer.h).  Synchronises the stream; a set flag is
+//     cleared and fails the call with "<who>: a wait on a peer's mailbox gave up ...".  comm_ready: not connected yet, refused with `msg`.
+int comm_allreduce_f64(PisoComm* pc, double* buf, int count, hipStream_t s);
+int comm_allreduce_i32(PisoComm* pc, int* buf, int count, hipStream_t s);
+int comm_allgather_f64(PisoComm* pc, const double* src, double* dst, size_t count, hipStream_t s);
+int comm_exchange_rows(PisoComm* pc, bool periodic_y, double* row0, int nx, int ny, hipStream_t s);
+int comm_exchange_segments(PisoComm* pc, void* vec, int dtype, const HaloMsg* m4, hipStream_t s);
+int comm_agree(PisoComm* pc, const char* who, hipStream_t s, bool ring_of_one = false);
+int comm_ready(const PisoComm* pc, const char* msg);
 
 }  // namespace piso
