@@ -27,7 +27,7 @@ struct HostPoll {
 };
 static std::atomic<unsigned> g_persist_launches{0};   // persistent launches so far: the high half of their exchange tags
 static int g_persist_fallbacks = 0;            // solves that were restarted on the two-kernel path after an exchange timed out
-// option cg_xcd_map 1 (tests): the XCD every workgroup of the solve's LAST chip-wide persistent launch ran on (cg_persist1.h: hier_enter)
+// option cg_xcd_map 1 (tests): the XCD every workgroup of the solve's LAST chip-wide persistent launch ran on (cg_persist.h: hier_enter)
 static thread_local int tl_xcd_map[kPersistMaxGrid];
 static thread_local int tl_xcd_map_n = 0;
 static long long g_tiny_solves = 0;            // solves that ran inside one workgroup (cg_tiny.h)

@@ -22,7 +22,7 @@
 // owners (bitwise equal), using the published perimeter of z' - so one vector's perimeter crosses the fabric per iteration
 // instead of two, and nothing has to be visible between D and U of one iteration: one exchange.
 // Round 4: the exchange is a tree that follows the hardware (workgroup -> XCD leader through that XCD's L2 -> everybody: every wave
-// polls the eight XCD records itself, no second barrier; grid_exchange8_hier), the end cells of a region's rows are published as
+// polls the eight XCD records itself, no second barrier; grid_exchange8_hier in cg_persist.h), the end cells of a region's rows are published as
 // one packed block per region (kPack: the L2 was full of single-cell cache lines), z' of U's first rows is computed while the
 // exchange's records travel (kAhead), and whatever only the rare paths need is read again from the kernarg segment (karg).
 // The one-step recurrences start from directly summed quantities in every iteration (no drift); they replace two dot
@@ -34,50 +34,8 @@
 #include <type_traits>
 
 #include "cg_persist.h"
-#include "peer.h"
 
 namespace piso {
-
-// SLAB = true: the kernel works on ONE y-slab of a grid that is cut over the GPUs of a node (cg_slab.hip).  What changes:
-//   * the rows just below / above the slab belong to the neighbouring GPU: the edge regions publish their first / last row of z'
-//     ALSO into that neighbour's mailbox (peer-mapped memory, system-scope stores over xGMI) and read the neighbour's row from
-//     their own mailbox; r, p[] and x carry one halo row below (row -1) and above (row ny) as in the two-kernel slab path - the
-//     ring copies start from them and are written back to them when the segment ends;
-//   * the exchange's second level crosses the node: the XCD leaders store their records into every rank's mailbox, wave w of every
-//     workgroup adds rank w's records, the rank totals meet in LDS (bitwise the same totals on every GPU, so every GPU takes the
-//     same decisions; grid_exchange8_hier<..., XG>);
-//   * N of the slab's last row comes from the N array (its S twin lives on the neighbour), sums of the previous K2 from a.gB.
-struct NoSlab {};
-struct SlabCtl {
-  PeerView pv;
-  double ncells;           // cells of the GLOBAL grid
-  char *rows_own, *rows_lo, *rows_hi;   // the row areas (PeerLayout::kRows) of my mailbox and of the lower / upper neighbour's
-  unsigned hop_ticks;      // measurements only (option slab_hop_ticks): the XCD leaders' records leave this many 10 ns ticks late
-};
-// A kernel argument read AGAIN from the kernarg segment (scalar loads through a pointer the optimiser cannot see through).  The
-// row loops of the persistent kernels are bound by VALU issue and short of scalar registers: whatever only the rare paths need -
-// the mailbox addresses of the two edge waves of a slab, the pointers of the exit block - is fetched where it is used instead of
-// living in SGPRs across the loop (a spilled SGPR comes back through v_readlane, a VALU slot; an s_load costs none).
-// Persist1Kargs mirrors the argument list of cg_persist1 (arguments are laid out like the members of a struct); the slab kernel
-// compares one reloaded field with the argument itself at entry and fails the launch if the layouts ever disagree.
-template <typename T, typename SL>
-struct Persist1Kargs { CgArgs<T> a; PersistCtl c; int k_begin, k_end, sv, pend; SL sl; };
-template <typename F>
-__device__ __forceinline__ F karg(unsigned off) {
-  typedef __attribute__((address_space(4))) const char kchar;
-  typedef __attribute__((address_space(4))) const unsigned kword;
-  kchar* kp = (kchar*)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(kp));
-  static_assert(sizeof(F) % 4 == 0, "whole dwords");
-  constexpr int NW = (int)(sizeof(F) / 4);
-  unsigned w[NW];
-  kword* src = (kword*)(kp + off);
-#pragma unroll
-  for (int i = 0; i < NW; ++i) w[i] = src[i];              // (merged into s_load_dwordx2 / x4 / x8 / x16)
-  F out;
-  __builtin_memcpy(&out, w, sizeof(F));
-  return out;
-}
 
 // ---- the three shape parameters an A/B build may still override (-DPISO_PERSIST1_<NAME>=n with scripts/build_variant.py); everything
 // else that used to be a compile-time switch here is folded to the variant that shipped (the measurements that decided each one
@@ -97,530 +55,6 @@ __device__ __forceinline__ F karg(unsigned off) {
 #ifndef PISO_PERSIST1_KEEP_Z_REGS
 #define PISO_PERSIST1_KEEP_Z_REGS 32
 #endif
-// s_sleep units (64 cycles) of the exchanges' polling (constants, not switches):
-constexpr int kPollDelay = 24;                   // between publishing a record and the first polling pass (flat exchange)
-constexpr int kPollDelay2 = 40;                  // tree, second level, behind the rows computed ahead (2048^2: 24 -> 9.12, 32 / 40 -> 8.94 us per iteration)
-constexpr int kPollDelay2NoAhead = 8;            // ... where nothing is computed ahead (512^2 / 1024 x 256: 24 -> 8: 4.27 -> 4.15 us, 0: 4.22)
-constexpr int kPollDelay2Xg = 8;                 // ... of the slab instance's node level (ring of one, 2048^2: 40 -> 8: 10.05 -> 9.67 us)
-constexpr int kLocalDelay = 8;                   // XCD-local exchange with one working wave per SIMD
-constexpr int kPollSleep = 1;                    // between two polling passes
-constexpr int kX1Values = 8;                     // sums per exchange
-constexpr int kX1RecWords = 16;                  // 8-byte words per record: 2 per sum {32 payload bits | 32-bit epoch}
-
-// Grid-wide exchange of kX1Values partial sums per workgroup that doubles as the grid barrier (measured 4.4 us for 256 workgroups
-// against 11.3 us for "atomic counter + fence + read the partials", scripts/barrier_bench.hip):
-//   * every workgroup publishes one record: each double travels as two 8-byte words {32 payload bits | 32-bit epoch}, written and
-//     read with relaxed agent-scope atomics (single-copy atomic, coherent across the 8 XCDs' L2s);
-//   * the waves poll all records until they carry the current epoch and add them in a fixed order, so every workgroup obtains
-//     bitwise the same totals - no counter, no fence, one memory round trip;
-//   * records alternate between two arrays (epoch parity): a fast workgroup may publish epoch e+1 while a slow one still reads
-//     epoch e, and nobody can reach e+2 before everybody has published e+1.
-// DATA written before the exchange (the published perimeter rows) is stored write-through at agent scope (sc1) and drained
-// (s_waitcnt vmcnt) by every wave before the workgroup publishes; readers load it at agent scope as well.  Measured: with one 128-byte record per LANE (64 cache
-// lines per load instruction) the exchange is bound by the number of fabric transactions (11 us per exchange at 256
-// workgroups).  Here the polling is COALESCED and spread over all 8 waves: lane l reads word l % 16 of record 4 i + l / 16, so
-// one load instruction covers four whole records (512 contiguous bytes); wave w polls records 32 w .. 32 w + 31 with 8 loads
-// per lane, one round trip once the records are there.  Lane pairs (2 q, 2 q + 1) hold the two halves of sum q.
-constexpr int kX1Sm = 160;                        // LDS words per parity: [8 sums][8 waves] | [8 waves][8 sums] | 8 flags
-struct NoPrefetch { __device__ __forceinline__ void operator()() const {} };
-
-// ---- wave-level reductions of the exchange on as few VALU instructions as possible (the row loops around the exchange are
-// bound by VALU issue, and every instruction of a 64-wide wave costs the same ~4.5 SIMD cycles whatever it does).
-// 64-bit moves between lanes: DPP inside a row of 16 lanes (VALU, two instructions), the LDS crossbar (ds_bpermute: no VALU
-// slot) across rows.
-template <int CTRL, int BANK>
-__device__ __forceinline__ double dpp_update(double old, double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v), o = (unsigned long long)__double_as_longlong(old);
-  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)o, (int)(unsigned)b, CTRL, 0xf, BANK, false);
-  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)(o >> 32), (int)(unsigned)(b >> 32), CTRL, 0xf, BANK, false);
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-__device__ __forceinline__ double lanes_xor4(double v) {    // lane l <- lane l ^ 4: row_shl:4 into banks 0, 2 / row_shr:4 into banks 1, 3
-  return dpp_update<0x114, 0xa>(dpp_update<0x104, 0x5>(v, v), v);
-}
-__device__ __forceinline__ double lanes_xor8(double v) { return dpp_move<0x128>(v); }                  // row_ror:8
-// v + (v of lane l ^ 16) and v + (v of lane l ^ 32): gfx950's v_permlane16_swap / v_permlane32_swap exchange the odd rows (the upper
-// half) of one register with the even rows (the lower half) of another - two swaps of the value with itself leave "mine" and "the
-// partner's" in two registers of EVERY lane, no trip through the LDS crossbar (ds_bpermute: ~100 cycles each in a dependent chain
-// that every wave of the chip waits for).  Both lanes of a pair add the same two numbers (a + b, b + a: the same bits), as before.
-template <int ROWS>
-__device__ __forceinline__ double sum_xor_rows(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  const unsigned lo = (unsigned)b, hi = (unsigned)(b >> 32);
-  const auto r0 = ROWS == 16 ? __builtin_amdgcn_permlane16_swap(lo, lo, false, false) : __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-  const auto r1 = ROWS == 16 ? __builtin_amdgcn_permlane16_swap(hi, hi, false, false) : __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-  const double x = __longlong_as_double((long long)(((unsigned long long)r1[0] << 32) | r0[0]));
-  const double y = __longlong_as_double((long long)(((unsigned long long)r1[1] << 32) | r0[1]));
-  return x + y;
-}
-__device__ __forceinline__ double sum_xor16(double v) { return sum_xor_rows<16>(v); }
-__device__ __forceinline__ double sum_xor32(double v) { return sum_xor_rows<32>(v); }
-// Eight per-lane partial sums -> lane l holds the WAVE total of value l & 7.  Reduce-scatter butterfly over lane bits 0, 1, 2 (a
-// lane keeps half of its values and receives the partner's contribution to them: 7 + 7 + ... instructions instead of three full
-// butterflies of eight values), then plain butterflies of the ONE remaining value over bits 3 (DPP), 4 and 5 (LDS crossbar).
-// ~56 VALU instructions; eight wave_sum_uniform calls are ~190.  Every step adds a lane's value and its partner's: both lanes of
-// a pair compute a + b and b + a - the same bits.
-__device__ __forceinline__ double wave_reduce_scatter8(const double (&v)[8]) {
-  const int lane = threadIdx.x & 63;
-  const bool b0 = (lane & 1) != 0, b1 = (lane & 2) != 0, b2 = (lane & 4) != 0;
-  double a[4], b[2];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)                                // a[j]: value 2 j + b0, summed over lane pairs
-    a[j] = (b0 ? v[2 * j + 1] : v[2 * j]) + dpp_move<0xB1>(b0 ? v[2 * j] : v[2 * j + 1]);      // quad_perm [1,0,3,2]
-#pragma unroll
-  for (int m = 0; m < 2; ++m)                                // b[m]: value 4 m + 2 b1 + b0, summed over quads
-    b[m] = (b1 ? a[2 * m + 1] : a[2 * m]) + dpp_move<0x4E>(b1 ? a[2 * m] : a[2 * m + 1]);      // quad_perm [2,3,0,1]
-  double c = (b2 ? b[1] : b[0]) + lanes_xor4(b2 ? b[0] : b[1]);                                 // value l & 7, summed over 8 lanes
-  c += lanes_xor8(c);
-  c = sum_xor16(c);
-  c = sum_xor32(c);
-  return c;
-}
-// slot / nslots: this workgroup's record and the number of records in play (blockIdx.x / gridDim.x, or the rank / size of the
-// XCD-local group).  LOCAL: every participant runs on the same XCD - records are stored without sc1 (they stay in that XCD's L2)
-// and polled with sc1 loads (L1 bypassed, L2-served): an L2 round trip instead of two trips through the fabric.
-template <typename T, bool LOCAL = false, typename F = NoPrefetch>
-__device__ __forceinline__ bool grid_exchange8(const PersistCtl& c, T (&v)[kX1Values], unsigned epoch, T* smem, int slot, int nslots,
-                                               F after_drain = F(), unsigned long long* tsub = nullptr) {
-  // tsub (diagnostic builds): clocks of [0] reduction + drain of this wave's stores, [1] first barrier, [2] publish + polling,
-  // [3] wave sums + second barrier
-  unsigned long long t0 = (kPersistDiag && tsub) ? wall_clock64() : 0;
-  auto tsplit = [&](int q) __attribute__((always_inline)) {
-    if (kPersistDiag && tsub) { const unsigned long long t = wall_clock64(); tsub[q] += t - t0; t0 = t; }
-  };
-  typedef unsigned long long u64;
-  constexpr int NV = kX1Values;
-  static_assert(kPersistMaxGrid == kPersistWaves * 32 && (kPersistWaves & (kPersistWaves - 1)) == 0, "every wave polls 32 records");
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  T* sm = smem + (epoch & 1) * kX1Sm;                       // parity double buffer: two __syncthreads per exchange
-  {
-    double vd[NV];
-#pragma unroll
-    for (int q = 0; q < NV; ++q) vd[q] = (double)v[q];
-    const double mine = wave_reduce_scatter8(vd);              // lane l: value l & 7, summed over this wave
-    if (lane < NV) sm[lane * kPersistWaves + wave] = (T)mine;
-  }
-  // EVERY vector-memory operation of this wave has completed - in particular its write-through perimeter stores - before the
-  // workgroup's record says so.  (A counted wait that lets the two prefetch loads issued behind the last store stay in flight
-  // would save ~0.4 us; it relies on loads and stores retiring in one order, which is not promised.)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  after_drain();
-  tsplit(0);
-  __syncthreads();                                            // every wave of the workgroup has drained its stores
-  tsplit(1);
-  u64* rec = c.rec + (size_t)(epoch & 1) * kPersistMaxGrid * kX1RecWords;
-  if (wave == 0) {
-    // lane l < 16 publishes word l: sum l / 2, low half (even l) or high half (odd l) - one store instruction, one cache line
-    const int vq = (lane >> 1) & (NV - 1);
-    T s = 0;
-    for (int w = 0; w < kPersistWaves; ++w) s += sm[vq * kPersistWaves + w];
-    const u64 bits = (u64)__double_as_longlong((double)s);
-    const u64 word = (lane & 1) ? ((bits & 0xffffffff00000000ull) | epoch) : (((bits & 0xffffffffull) << 32) | epoch);
-    if (lane < kX1RecWords) {
-      if constexpr (LOCAL) __hip_atomic_store(rec + (size_t)slot * kX1RecWords + lane, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      else __hip_atomic_store(rec + (size_t)slot * kX1RecWords + lane, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  // (Tried: no barrier here - every wave counts itself in through LDS and the LAST one publishes.  Wave 0 waits 2.3 us of a 7 us
-  // exchange in this barrier, but without it the exchange took 8.3 us and the row loops slowed down - 21 us per iteration
-  // against 17: the waves that arrive early poll, and their polling competes with the stores of the ones still working.)
-  bool good = true;
-  {
-    const int wd = lane & 15, sub = lane >> 4;               // my word of the record, my record inside a group of four
-    u64 w[8];
-    bool okl[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      w[i] = 0;
-      okl[i] = ((wave * 8 + i) * 4 + sub) >= nslots;           // records beyond the grid count as arrived (payload 0)
-    }
-    unsigned spins = 0;
-    // a first poll that finds every record beats two passes: the records of 256 workgroups that finish their row loops together
-    // need ~0.6 us to become visible; measured at 2048^2: no delay 11.7, s_sleep 16 .. 32 11.4, 48 11.7, 64 11.9 us per iteration
-    if constexpr (!LOCAL) { if (kPollDelay > 0) __builtin_amdgcn_s_sleep(kPollDelay); }
-    while (true) {
-      bool ok = true;
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        if (!okl[i]) w[i] = __hip_atomic_load(rec + (size_t)((wave * 8 + i) * 4 + sub) * kX1RecWords + wd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        if (!okl[i]) okl[i] = (unsigned)(w[i] & 0xffffffffull) == epoch;
-        ok = ok && okl[i];
-      }
-      if (__all(ok)) break;
-      if (++spins > (1u << 22)) { good = false; break; }
-      __builtin_amdgcn_s_sleep(kPollSleep);
-    }
-    tsplit(2);
-    // even lanes assemble their sum from their own word (low half) and the neighbour lane's (high half); records of a lane
-    // are added in order, then the four records-per-instruction rows, then (after the barrier) the eight waves
-    double acc = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const unsigned hi_other = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)(w[i] >> 32), 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
-      const u64 bits = (w[i] >> 32) | ((u64)hi_other << 32);
-      acc += __longlong_as_double((long long)bits);          // (odd lanes add garbage that nobody reads; absent records add 0)
-    }
-    acc = sum_xor16(acc);                                 // the four records-per-instruction groups of lanes (LDS crossbar)
-    acc = sum_xor32(acc);
-    if (lane < 2 * NV && !(lane & 1)) sm[64 + wave * NV + (lane >> 1)] = (T)acc;   // this wave's 32 records, value lane / 2
-    if (lane == 0) {
-      sm[128 + wave] = good ? (T)0 : (T)1;
-      if (!good) *c.err = 1;
-    }
-  }
-  __syncthreads();
-  tsplit(3);
-  {
-    // one read fetches all 8 x 8 wave sums (lane l: wave l / 8, value l % 8); butterflies over the wave index leave every lane
-    // with the total of value l % 8 - the same bits in every wave of every workgroup (same inputs, same order)
-    double t = (double)sm[64 + lane];
-    t += lanes_xor8(t);
-    t = sum_xor16(t);
-    t = sum_xor32(t);
-#pragma unroll
-    for (int q = 0; q < NV; ++q) v[q] = (T)read_lane_c(t, q);
-    const T bad = sm[128 + (lane & (kPersistWaves - 1))];
-    good = !__any(bad != (T)0);
-  }
-  return good;
-}
-
-// ---- The same exchange as a TREE that follows the hardware (chip-wide launches; round 4): workgroup -> XCD leader -> everybody.
-//   level 1  every workgroup stores its record WITHOUT sc1 into the records of ITS XCD (slot = 32 xcd + arrival rank on that XCD;
-//            the store stays in that XCD's L2); wave 0 of the XCD's leader (arrival rank 0) polls the XCD's records with sc1 loads
-//            (L1 bypassed, served by the L2 both share) and adds them in rank order;
-//   level 2  the leader publishes the XCD's sums as one record through the fabric (sc1 store); EVERY wave of every workgroup polls
-//            the eight XCD records itself (two coalesced loads per lane) and adds them in XCD order - bitwise the same totals in
-//            every wave of the chip, no second barrier, no LDS round trip behind the polling.
-// Measured (scripts/barrier_bench.hip, 256 workgroups, 3 sums): 2.40 us per exchange against 3.7-5.3 us for the flat all-to-all
-// variants (every workgroup polling 256 records through the fabric: 8 MB of polling reads per pass; here 4 KB per XCD at level 1
-// and 2 MB at level 2).  hx packs what a workgroup learnt at entry (hier_enter): bits 0-2 XCD, 3-8 arrival rank, 9-14 workgroups
-// on my XCD, 15-22 XCDs that hold workgroups.  A wave whose polling gives up sets the workgroup's LDS flag and the launch's
-// error word; all waves of the workgroup read the flag behind the next barrier and leave the loop together.
-__device__ __forceinline__ unsigned long long* hier_level2(const PersistCtl& c) {
-  return c.rec + (size_t)2 * kPersistMaxGrid * kX1RecWords;                 // right behind the level-1 records (kPersistRecWords)
-}
-// entry of a chip-wide launch: which XCD am I on, how many workgroups does every XCD hold, and which of them am I?  One returning
-// atomic per workgroup, then everybody waits for everybody ONCE per launch (c.xcd[0..7] arrivals per XCD, [9] arrivals in all;
-// zeroed by the host before the launch).  My place among my XCD's workgroups is my place by WORKGROUP INDEX, not by arrival: the
-// leader adds the records in that order, so two launches that the hardware deals to the XCDs the same way add in the same order
-// and a solve is reproducible bit for bit from run to run (by arrival order the forward solves of the 2048^2 benchmark took
-// 325 - 360 iterations on the same input, now and then 1 005).  Every workgroup leaves its XCD in a table before it counts itself in.
-__device__ __forceinline__ unsigned hier_enter(const PersistCtl& c, int* lds2) {      // lds2: [0] hx, [1] launch cannot run, [2] sticky flag of the exchanges
-  int* const table = c.xcd + kPersistXcdTable;
-  if (threadIdx.x == 0) {
-    const int xcc = (int)(__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & 7);       // HW_REG_XCC_ID[3:0]
-    __hip_atomic_store(table + blockIdx.x, xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int arrival = __hip_atomic_fetch_add(c.xcd + xcc, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_fetch_add(c.xcd + 9, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);     // (release: my table entry is out before I count)
-    unsigned spins = 0;
-    bool ok = arrival < 32;
-    while (ok && __hip_atomic_load(c.xcd + 9, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < (int)gridDim.x) {
-      if (++spins > (1u << 22)) { ok = false; break; }
-      __builtin_amdgcn_s_sleep(2);
-    }
-    unsigned present = 0, mine = 0;
-    for (int x = 0; x < kXcds; ++x) {
-      const int n = __hip_atomic_load(c.xcd + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (n > 0) present |= 1u << x;
-      if (n > 32) ok = false;
-      if (x == xcc) mine = (unsigned)n;
-    }
-    if (!ok) *c.err = 1;
-    lds2[0] = (int)((unsigned)xcc | ((mine & 63u) << 9) | (present << 15));
-    lds2[1] = ok ? 0 : 1;
-    lds2[2] = 0;
-  }
-  __syncthreads();
-  if (threadIdx.x < 64 && !lds2[1]) {                        // wave 0: the workgroups of my XCD with a smaller index
-    const int xcc = lds2[0] & 7;
-    int before = 0;
-    for (int b = (int)threadIdx.x; b < (int)gridDim.x; b += 64)
-      before += (b < (int)blockIdx.x && __hip_atomic_load(table + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == xcc) ? 1 : 0;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off, 64);
-    if (threadIdx.x == 0) lds2[0] |= (before & 63) << 3;
-  }
-  __syncthreads();
-  return (unsigned)__builtin_amdgcn_readfirstlane(lds2[0]);
-}
-// XG (slab instance, round 5): the node's level of the exchange rides on the tree's second level instead of following it.  The XCD
-// leaders store their XCD's record straight into EVERY rank's mailbox (system-scope stores over xGMI; the own mailbox included);
-// wave w of every workgroup polls the eight XCD records of RANK w in its own mailbox and adds them in XCD order, the rank totals
-// meet in LDS behind one barrier and every wave adds them by the same butterfly over the rank index - bitwise the same totals in
-// every wave of every GPU.  (Round 4 had a serial level here: workgroup 0 waited for the chip's totals, wrote them to the peers,
-// and wave 0 of every workgroup polled again - one more uncached round trip per iteration.)  All eight records of a rank also
-// certify that every row this rank stored into a peer's mailbox has completed: its workgroups drained their stores before they
-// published, and a leader publishes only after it has seen all workgroups of its XCD.  An XCD that holds no workgroups (small
-// grids) is published with zero sums by the leader of the rank's lowest XCD in play.  sl_off: where the SlabCtl sits in the
-// kernarg segment - mailbox addresses, rank and world are fetched where they are used (karg), not held in SGPRs across the loops.
-constexpr int kX1SmX = 80;                        // LDS words of the node level per parity: [8 ranks][8 sums], 8 flags
-template <typename T, int DELAY2, bool XG = false, typename F = NoPrefetch>
-__device__ __forceinline__ bool grid_exchange8_hier(const PersistCtl& c, T (&v)[kX1Values], unsigned epoch, T* smem, unsigned hx, int* flag,
-                                                    F while_records_travel = F(), unsigned long long* tsub = nullptr, unsigned sl_off = 0,
-                                                    T* smx2 = nullptr) {
-  unsigned long long t0 = (kPersistDiag && tsub) ? wall_clock64() : 0;
-  auto tsplit = [&](int q) __attribute__((always_inline)) {
-    if (kPersistDiag && tsub) { const unsigned long long t = wall_clock64(); tsub[q] += t - t0; t0 = t; }
-  };
-  typedef unsigned long long u64;
-  constexpr int NV = kX1Values;
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  T* sm = smem + (epoch & 1) * kX1Sm;                       // parity double buffer (one barrier per exchange separates writers and readers)
-  {
-    double vd[NV];
-#pragma unroll
-    for (int q = 0; q < NV; ++q) vd[q] = (double)v[q];
-    const double mine = wave_reduce_scatter8(vd);              // lane l: value l & 7, summed over this wave
-    if (lane < NV) sm[lane * kPersistWaves + wave] = (T)mine;
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // every perimeter store of this wave has completed (see grid_exchange8)
-  tsplit(0);
-  __syncthreads();
-  tsplit(1);
-  // A polling pass of an EARLIER exchange gave up somewhere in this workgroup: the flag is sticky, every wave reads it here behind the
-  // barrier and all of them leave together at the end of this exchange - the wave that gave up included: it returned "healthy" like
-  // its siblings.  (No return from here: an exit in the middle of the iteration loop turns its control flow into exec-mask flow and
-  // the iteration counter into a vector register.  The polling loops below give up at once instead: spin0.)
-  const bool good = __builtin_amdgcn_readfirstlane(*flag) == 0;
-  const unsigned spin0 = good ? 0u : (1u << 30);
-  const int xcc = (int)(hx & 7u), rank = (int)((hx >> 3) & 63u), nmine = (int)((hx >> 9) & 63u);
-  const unsigned present = (hx >> 15) & 0xffu;
-  u64* rec1 = c.rec + (size_t)(epoch & 1) * kPersistMaxGrid * kX1RecWords + (size_t)xcc * 32 * kX1RecWords;
-  u64* rec2 = hier_level2(c) + (size_t)(epoch & 1) * kXcds * kX1RecWords;
-  // lane l polls word l % 16 of record 4 i + l / 16, i.e. 8-byte word 64 i + l of the record array: ONE per-lane offset, made opaque
-  // so that nothing derived from it is hoisted out of the iteration loop into vector registers that live across the row loops
-  int lw = lane;
-  asm volatile("" : "+v"(lw));
-  bool mygood = true;
-  if (wave == 0) {
-    {
-      // lane l < 16 publishes word l: sum l / 2, low half (even l) or high half (odd l) - one store instruction, one cache line
-      const int vq = (lane >> 1) & (NV - 1);
-      T s = 0;
-      for (int w = 0; w < kPersistWaves; ++w) s += sm[vq * kPersistWaves + w];
-      const u64 bits = (u64)__double_as_longlong((double)s);
-      const u64 word = (lane & 1) ? ((bits & 0xffffffff00000000ull) | epoch) : (((bits & 0xffffffffull) << 32) | epoch);
-      if (lane < kX1RecWords) __hip_atomic_store(rec1 + (size_t)rank * kX1RecWords + lane, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    if (rank == 0) {                                          // the XCD's leader: the records of my XCD (through its L2), in rank order
-      // (branch-free passes: all eight loads every time, records beyond the XCD's count masked by one compare against a scalar -
-      // per-record arrival flags are eight lane masks = sixteen SGPRs the row loops then spill)
-      u64 w[8];
-      // (opaque: left visible, the eight bounds lim - 64 i are constants of the launch that live in SGPRs across the row loops - spilled,
-      // and a spilled SGPR comes back through v_readlane; recomputed here they are eight scalar subtractions per exchange)
-      int lim = nmine * kX1RecWords;                          // words of the XCD's block that belong to records in play
-      asm volatile("" : "+s"(lim));
-      unsigned spins = spin0;
-      while (true) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) w[i] = __hip_atomic_load(rec1 + lw + i * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        unsigned bad = 0;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) bad |= (lw < lim - i * 64) ? ((unsigned)(w[i] & 0xffffffffull) ^ epoch) : 0u;
-        if (__all(bad == 0)) break;
-        if (++spins > (1u << 22)) { mygood = false; break; }
-      }
-      double acc = 0;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const unsigned hi_other = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)(w[i] >> 32), 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
-        const double val = __longlong_as_double((long long)((w[i] >> 32) | ((u64)hi_other << 32)));   // (odd lanes: garbage that nobody reads)
-        acc += (lw < lim - i * 64) ? val : 0.0;
-      }
-      acc = sum_xor16(acc);
-      acc = sum_xor32(acc);                                // even lane 2 q (of every group of 16): the XCD's sum of value q
-      const double other = dpp_move<0xB1>(acc);              // odd lanes: the even neighbour's sum
-      const u64 bits = (u64)__double_as_longlong((lane & 1) ? other : acc);
-      const u64 word = (lane & 1) ? ((bits & 0xffffffff00000000ull) | epoch) : (((bits & 0xffffffffull) << 32) | epoch);
-      if constexpr (!XG) {
-        if (lane < kX1RecWords) __hip_atomic_store(rec2 + (size_t)xcc * kX1RecWords + lane, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      } else {
-        constexpr unsigned pvo = (unsigned)offsetof(SlabCtl, pv);
-        const int world = karg<int>(sl_off + pvo + (unsigned)offsetof(PeerView, world));
-        const int myrank = karg<int>(sl_off + pvo + (unsigned)offsetof(PeerView, rank));
-        // (measurements only - SlabCtl::hop_ticks > 0: the records leave this many 10 ns ticks late, as if the link had that latency)
-        const unsigned hop = karg<unsigned>(sl_off + (unsigned)offsetof(SlabCtl, hop_ticks));
-        if (hop) { const unsigned long long t_go = wall_clock64() + hop; while (wall_clock64() < t_go) __builtin_amdgcn_s_sleep(1); }
-        const bool lowest = (present & ((1u << xcc) - 1u)) == 0;     // (scalar) the leader that also speaks for the XCDs without workgroups
-        for (int p = 0; p < world; ++p) {
-          char* mb = karg<char*>(sl_off + pvo + (unsigned)offsetof(PeerView, mbox) + 8u * (unsigned)p);
-          if (lane < kX1RecWords) peer_store(reinterpret_cast<peer_u64*>(mb + PeerLayout::xcd_rec(epoch & 1, myrank, xcc)) + lane, word);
-          if (lowest && present != 0xffu) {
-            for (int x = 0; x < kXcds; ++x)
-              if (!((present >> x) & 1u) && lane < kX1RecWords)
-                peer_store(reinterpret_cast<peer_u64*>(mb + PeerLayout::xcd_rec(epoch & 1, myrank, x)) + lane, (peer_u64)epoch);
-          }
-        }
-      }
-    }
-  }
-  // the records need a microsecond or two to make their way: work that does not depend on the sums goes here (the row loops
-  // are bound by VALU issue, and the SIMDs idle while the exchange is in flight)
-  while_records_travel();
-  if constexpr (!XG) {
-    // every wave: the eight XCD records (lane l: word l % 16 of record 4 i + l / 16), added in XCD order
-    u64 w[2];
-    unsigned spins = spin0;
-    if (DELAY2 > 0) __builtin_amdgcn_s_sleep(DELAY2);
-    while (true) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) w[i] = __hip_atomic_load(rec2 + lw + i * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      unsigned bad = 0;
-#pragma unroll
-      for (int i = 0; i < 2; ++i)                            // (XCDs without workgroups: nothing to wait for, payload 0)
-        bad |= (((present >> (i * 4)) >> (lw >> 4)) & 1u) ? ((unsigned)(w[i] & 0xffffffffull) ^ epoch) : 0u;
-      if (__all(bad == 0)) break;
-      if (++spins > (1u << 22)) { mygood = false; break; }
-      __builtin_amdgcn_s_sleep(kPollSleep);
-    }
-    tsplit(2);
-    double acc = 0;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const unsigned hi_other = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)(w[i] >> 32), 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
-      const double val = __longlong_as_double((long long)((w[i] >> 32) | ((u64)hi_other << 32)));
-      acc += (((present >> (i * 4)) >> (lw >> 4)) & 1u) ? val : 0.0;
-    }
-    acc = sum_xor16(acc);
-    acc = sum_xor32(acc);                                  // lane 2 q: the total of value q - the same bits in every wave of the chip
-#pragma unroll
-    for (int q = 0; q < NV; ++q) v[q] = (T)read_lane_c(acc, 2 * q);
-    if (!mygood) {                                              // (wave-uniform)
-      if (lane == 0) { *flag = 1; *c.err = 1; }
-    }
-    tsplit(3);
-    return good;
-  } else {
-    // wave w: the eight XCD records of rank w in MY mailbox (every XCD slot of a rank in play is published, see above)
-    T* smx = smx2 + (epoch & 1) * kX1SmX;
-    constexpr unsigned pvo = (unsigned)offsetof(SlabCtl, pv);
-    const int world = karg<int>(sl_off + pvo + (unsigned)offsetof(PeerView, world));
-    double acc = 0;
-    if (wave < world) {
-      const char* own = karg<char*>(sl_off + (unsigned)offsetof(SlabCtl, rows_own)) - PeerLayout::kRows;
-      const peer_u64* recs = reinterpret_cast<const peer_u64*>(own + PeerLayout::xcd_rec(epoch & 1, wave, 0));
-      peer_u64 w[2];
-      unsigned spins = spin0;
-      if (DELAY2 > 0) __builtin_amdgcn_s_sleep(DELAY2);
-      while (true) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) w[i] = peer_load(recs + lw + i * 64);
-        unsigned bad = 0;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) bad |= (unsigned)(w[i] & 0xffffffffull) ^ epoch;
-        if (__all(bad == 0)) break;
-        if (++spins > kPeerSpinLimit) { mygood = false; break; }      // (kPeerSpinLimit < spin0)
-        __builtin_amdgcn_s_sleep(kPollSleep);
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const unsigned hi_other = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)(w[i] >> 32), 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
-        acc += __longlong_as_double((long long)((w[i] >> 32) | ((peer_u64)hi_other << 32)));
-      }
-      acc = sum_xor16(acc);
-      acc = sum_xor32(acc);                                // lane 2 q: rank w's total of value q (XCD order)
-    }
-    tsplit(2);
-    if (lane < 2 * NV && !(lane & 1)) smx[wave * NV + (lane >> 1)] = (T)acc;       // (a wave without a rank: zeros)
-    if (!mygood) {
-      if (lane == 0) { *flag = 1; *c.err = 1; }
-    }
-    __syncthreads();
-    {
-      // one read fetches the 8 x 8 rank totals (lane l: rank l / 8, value l % 8); the butterfly over the rank index leaves every
-      // lane with the node's total of value l % 8 - the same order of additions in every wave of every GPU
-      double t = (double)smx[lane];
-      t += lanes_xor8(t);
-      t = sum_xor16(t);
-      t = sum_xor32(t);
-#pragma unroll
-      for (int q = 0; q < NV; ++q) v[q] = (T)read_lane_c(t, q);
-    }
-    tsplit(3);
-    return good && __builtin_amdgcn_readfirstlane(*flag) == 0;
-  }
-}
-
-// ---- XCD-local launches (LOCAL, at most 32 workgroups, all on one XCD): the same idea in one level.  Wave 0 publishes the workgroup's
-// record (plain store: it stays in the XCD's L2), then EVERY wave polls the group's records itself (sc1 loads: L1 bypassed, served
-// by that L2; eight coalesced loads per lane cover 32 records) and adds them in slot order - no second barrier, no LDS round trip
-// behind the polling (0.36 us of a 3.5 us iteration at 256^2).  Error handling as in grid_exchange8_hier (sticky LDS flag).
-template <typename T>
-__device__ __forceinline__ bool grid_exchange8_local(const PersistCtl& c, T (&v)[kX1Values], unsigned epoch, T* smem, int slot, int nslots, int* flag,
-                                                     unsigned long long* tsub = nullptr) {
-  unsigned long long t0 = (kPersistDiag && tsub) ? wall_clock64() : 0;
-  auto tsplit = [&](int q) __attribute__((always_inline)) {
-    if (kPersistDiag && tsub) { const unsigned long long t = wall_clock64(); tsub[q] += t - t0; t0 = t; }
-  };
-  typedef unsigned long long u64;
-  constexpr int NV = kX1Values;
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  T* sm = smem + (epoch & 1) * kX1Sm;
-  {
-    double vd[NV];
-#pragma unroll
-    for (int q = 0; q < NV; ++q) vd[q] = (double)v[q];
-    const double mine = wave_reduce_scatter8(vd);
-    if (lane < NV) sm[lane * kPersistWaves + wave] = (T)mine;
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  tsplit(0);
-  __syncthreads();
-  tsplit(1);
-  const bool good = __builtin_amdgcn_readfirstlane(*flag) == 0;      // (sticky, read behind the barrier: all waves leave together, see grid_exchange8_hier)
-  const unsigned spin0 = good ? 0u : (1u << 30);
-  u64* rec = c.rec + (size_t)(epoch & 1) * kPersistMaxGrid * kX1RecWords;
-  int lw = lane;
-  asm volatile("" : "+v"(lw));
-  bool mygood = true;
-  if (wave == 0) {
-    const int vq = (lane >> 1) & (NV - 1);
-    T s = 0;
-    for (int w = 0; w < kPersistWaves; ++w) s += sm[vq * kPersistWaves + w];
-    const u64 bits = (u64)__double_as_longlong((double)s);
-    const u64 word = (lane & 1) ? ((bits & 0xffffffff00000000ull) | epoch) : (((bits & 0xffffffffull) << 32) | epoch);
-    if (lane < kX1RecWords) __hip_atomic_store(rec + (size_t)slot * kX1RecWords + lane, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  }
-  {
-    u64 w[8];
-    const int lim = nslots * kX1RecWords;
-    unsigned spins = spin0;
-    // (one working wave per SIMD - c.waves = 4: the record needs ~0.2 us to arrive and a first pass that misses it queues in front
-    // of the one that would find it: 256^2 3.33 -> 3.15 us per iteration with 8 units, 4: 3.21, 12: 3.23; with two working waves per
-    // SIMD - 512 x 256 - any delay loses: 3.84 / 3.83 / 3.92 / 4.00 / 4.10 with 0 / 4 / 8 / 12 / 16)
-    if (kLocalDelay > 0 && c.waves < kPersistWaves) __builtin_amdgcn_s_sleep(kLocalDelay);
-    while (true) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) w[i] = __hip_atomic_load(rec + lw + i * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      unsigned bad = 0;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) bad |= (lw < lim - i * 64) ? ((unsigned)(w[i] & 0xffffffffull) ^ epoch) : 0u;
-      if (__all(bad == 0)) break;
-      if (++spins > (1u << 22)) { mygood = false; break; }
-      __builtin_amdgcn_s_sleep(kPollSleep);
-    }
-    tsplit(2);
-    double acc = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const unsigned hi_other = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)(w[i] >> 32), 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
-      const double val = __longlong_as_double((long long)((w[i] >> 32) | ((u64)hi_other << 32)));
-      acc += (lw < lim - i * 64) ? val : 0.0;
-    }
-    acc = sum_xor16(acc);
-    acc = sum_xor32(acc);
-#pragma unroll
-    for (int q = 0; q < NV; ++q) v[q] = (T)read_lane_c(acc, 2 * q);
-  }
-  if (!mygood) {
-    if (lane == 0) { *flag = 1; *c.err = 1; }
-  }
-  tsplit(3);
-  return good;
-}
 
 // x-neighbours across the lanes of a wave.  The values beyond the two ends of the strip (`ring`: the left neighbour of row j in
 // lane j, the right neighbour in lane 48 + j) enter through the `old` operand of the wave shift: one row-local DPP shift brings
@@ -677,14 +111,13 @@ constexpr int kSystem = 17;                       // buffer cache policy sc0 | s
 // about them is zero by construction (zero coefficients, zero right-hand side).
 // LOCAL = true: XCD-local mode for grids that need at most one XCD's worth of workgroups (the small BASELINE configurations,
 // where an iteration is nothing but the exchange: 4.3 us with 16 workgroups spread over the chip).  The launch has 8 x c.local_n
-// workgroups; every one counts itself in on its XCD (HW_REG_XCC_ID), the workgroup that completes the first quota of c.local_n
-// names its XCD the winner, the c.local_n first arrivals there run the solve with their arrival ranks as workgroup numbers and
-// everybody else exits.  Some XCD always collects a quota (8 x local_n workgroups over 8 XCDs), whatever the dispatcher does:
-// placement decides nothing but speed.  Inside the group, published data and records are stored WITHOUT sc1 (they stay in the
-// XCD's L2) and read with sc1 loads (L1 bypassed, L2-served).
+// workgroups, of which the c.local_n that local_enter elects run the solve.  Inside the group, published data and records are
+// stored WITHOUT sc1 (they stay in the XCD's L2) and read with sc1 loads (L1 bypassed, L2-served).
 template <typename T, typename CT, int R, int NQ, bool RECON, bool SYM, bool SLAB = false, bool RAGGED = false, bool LOCAL = false>
 __global__ __launch_bounds__(kPersistThreads) void cg_persist1(CgArgs<T> a, PersistCtl c, int k_begin, int k_end, int sv, int pend,
                                                                std::conditional_t<SLAB, SlabCtl, NoSlab> sl = {}) {
+  // The body in order: 1 entry state, 2 coefficient pipeline (and the lambdas of the row loops), then per iteration 3 D, 4 exchange +
+  // scalars, 5 U, and 6 exit.  One function on purpose: the lambdas share the register file, a state struct would not.
   static_assert(!(SLAB && RAGGED), "a slab is never padded");
   static_assert(!(SLAB && LOCAL), "a slab's neighbours are other GPUs");
   // cache policy of what other workgroups read inside the launch (non-temporal hints on the published rows / the halo loads were
@@ -706,10 +139,9 @@ __global__ __launch_bounds__(kPersistThreads) void cg_persist1(CgArgs<T> a, Pers
   // broadcast read per row and pass that every lane receives (ring_issue) and no VALU slot at all.
   // (the slab variant and the fp64-coefficient fallback have no registers for the values in flight: they keep the DPP shifts)
   constexpr bool kRingLds = sizeof(CT) == 4;
-  // kParkRing: the ring-column copies of p AND r (one value per lane) live in the wave's LDS ring block between their two uses per
-  // iteration (D's start, U's end) instead of in registers across both row loops
-  constexpr bool kParkRing = kRingLds;
-  constexpr int kRingBytes = 64 * (int)sizeof(T) + 64 * (int)sizeof(CT) + (kParkRing ? 64 * (int)sizeof(T) : 0);
+  // ... and with kRingLds the ring-column copies of p AND r (one value per lane) live in the wave's LDS ring block between their two
+  // uses per iteration (D's start, U's end) instead of in registers across both row loops
+  constexpr int kRingBytes = 64 * (int)sizeof(T) + 64 * (int)sizeof(CT) + (kRingLds ? 64 * (int)sizeof(T) : 0);
   constexpr unsigned kRingR = 64u * (unsigned)sizeof(T) + 64u * (unsigned)sizeof(CT);      // byte offset of the parked r column inside a ring block
   __shared__ __attribute__((aligned(16))) unsigned char ring_s[kRingLds ? kPersistWaves * NQ * kRingBytes : 16];
   const int nx = a.nx, ny = a.ny;
@@ -720,41 +152,17 @@ __global__ __launch_bounds__(kPersistThreads) void cg_persist1(CgArgs<T> a, Pers
   int nslots = (int)gridDim.x;                             // workgroups that take part in the exchanges
   if constexpr (LOCAL) {
     __shared__ int local_rank_s;
-    if (threadIdx.x == 0) {
-      const int xcc = (int)(__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & 7);       // HW_REG_XCC_ID[3:0]
-      const int arrival = __hip_atomic_fetch_add(c.xcd + xcc, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      int rank = -1;
-      if (arrival < c.local_n) {
-        if (arrival == c.local_n - 1) {                    // my XCD's quota is complete: the first such XCD wins
-          int none = 0;
-          __hip_atomic_compare_exchange_strong(c.xcd + 8, &none, xcc + 1, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        int winner = 0;
-        unsigned spins = 0;
-        while ((winner = __hip_atomic_load(c.xcd + 8, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0) {
-          if (++spins > (1u << 22)) break;                 // (cannot happen: some XCD completes a quota; never hang all the same)
-          __builtin_amdgcn_s_sleep(2);
-        }
-        if (winner == xcc + 1) rank = arrival;
-        else if (winner == 0) { *c.err = 1; }
-      }
-      local_rank_s = rank;
-    }
-    __syncthreads();
-    wg = __builtin_amdgcn_readfirstlane(local_rank_s);     // (wave-uniform BY CONSTRUCTION: an LDS read is a vector value to the compiler - every offset derived
-                                                           //  from it became per-lane arithmetic, and the halo loads' resources were built in waterfall loops)
+    wg = local_enter(c, &local_rank_s);
     if (wg < 0) return;                                    // not in the group that runs the solve
     nslots = c.local_n;
   }
   const int slot = LOCAL ? wg : (int)blockIdx.x;           // my exchange record
-  // chip-wide launches: the exchange is a tree over the XCDs (grid_exchange8_hier); where am I in it?
-  constexpr bool kHier = !LOCAL;
-  static_assert(!SLAB || kHier, "the node level of the slab instance rides on the tree exchange");
+  // chip-wide launches: the exchange is a tree over the XCDs (grid_exchange8_hier); where am I in it?  XCD-local launches: every
+  // wave polls the group's records itself (grid_exchange8_local)
   unsigned hx = 0;
-  constexpr bool kLocalAll = LOCAL;     // XCD-local launches: every wave polls the group's records itself
-  __shared__ int hier_s[(kHier || kLocalAll) ? 4 : 1];
-  if constexpr (kLocalAll) { if (threadIdx.x == 0) hier_s[2] = 0; }          // (the sticky flag; the barriers of the set-up below publish it)
-  if constexpr (kHier) {
+  __shared__ int hier_s[4];
+  if constexpr (LOCAL) { if (threadIdx.x == 0) hier_s[2] = 0; }          // (the sticky flag; the barriers of the set-up below publish it)
+  if constexpr (!LOCAL) {
     hx = hier_enter(c, hier_s);
     if (hier_s[1]) return;                                 // (every workgroup of the launch fails this the same way)
   }
@@ -829,7 +237,7 @@ __global__ __launch_bounds__(kPersistThreads) void cg_persist1(CgArgs<T> a, Pers
     return j;
   };
 
-  // ---- the state of the two-kernel path: r and the direction p_{k-1} of my regions into registers, x into LDS
+  // ---- 1 ENTRY STATE.  The state of the two-kernel path: r and the direction p_{k-1} of my regions into registers, x into LDS
   const T alpha0 = pend ? uniform(a.scal[SC_ALPHA]) : (T)0;   // pend: x still lacks alpha p of the iteration before k_begin
   Vec<T, V> rr[NQ][R], pp[NQ][R];
   // kPack (regions of more than two rows): the END CELLS of a region's rows - what the strips to the left and right read - are
@@ -876,30 +284,20 @@ __global__ __launch_bounds__(kPersistThreads) void cg_persist1(CgArgs<T> a, Pers
       // the ring: rows below / above (out of range beyond a wall -> 0) and the two neighbouring columns
       // (lane l < R: left neighbour of row l, lane R + l: right neighbour; other lanes and walls read 0)
       const int jb = row_wrap(j0[q] - 1, vb[q]), ja = row_wrap(j0[q] + R, va[q]);
-      if constexpr (SLAB) {                                  // no wrap inside a slab: beyond its edges lies a neighbour's row (or a wall)
-        vb[q] = !(ef[q] & 4u) || (ef[q] & 1u); va[q] = !(ef[q] & 8u) || (ef[q] & 2u);
-        const unsigned hb = (has[q] && vb[q]) ? vT[q] : 0xffffffffu, ha = (has[q] && va[q]) ? vT[q] : 0xffffffffu;
-        const rsrc_t RrH = make_rsrc(a.r - nx, nbytesH), RpH = make_rsrc(a.p[k_begin & 1] - nx, nbytesH);
-        rhb[q] = bld<T, V>(RrH, hb, (unsigned)j0[q] * rowT);            // (the halo-based resources start one row lower)
-        rha[q] = bld<T, V>(RrH, ha, (unsigned)(j0[q] + R + 1) * rowT);
-        pnb[q] = bld<T, V>(RpH, hb, (unsigned)j0[q] * rowT);
-        pna[q] = bld<T, V>(RpH, ha, (unsigned)(j0[q] + R + 1) * rowT);
-        if constexpr (kParkHalos) {                          // parked at once: no register of the entry survives into the loop
-          T* hs = halo_s + (size_t)((wave * NQ + q) * 2) * 64 * V + lane * V;
-          stv<T, V>(hs, pnb[q]);
-          stv<T, V>(hs + 64 * V, pna[q]);
-        }
-      } else {
+      // SLAB: no wrap inside a slab - beyond its edges lies a neighbour's row (or a wall), which r and p carry as halo rows: through
+      // resources that start one row lower
+      if constexpr (SLAB) { vb[q] = !(ef[q] & 4u) || (ef[q] & 1u); va[q] = !(ef[q] & 8u) || (ef[q] & 2u); }
       const unsigned hb = (has[q] && vb[q]) ? vT[q] : 0xffffffffu, ha = (has[q] && va[q]) ? vT[q] : 0xffffffffu;
-      rhb[q] = bld<T, V>(Rr, hb, (unsigned)jb * rowT);
-      rha[q] = bld<T, V>(Rr, ha, (unsigned)ja * rowT);
-      pnb[q] = bld<T, V>(Rp, hb, (unsigned)jb * rowT);
-      pna[q] = bld<T, V>(Rp, ha, (unsigned)ja * rowT);
-      if constexpr (kParkHalos) {
+      const rsrc_t RrN = SLAB ? make_rsrc(a.r - nx, nbytesH) : Rr, RpN = SLAB ? make_rsrc(a.p[k_begin & 1] - nx, nbytesH) : Rp;
+      const int rb = SLAB ? j0[q] : jb, ra = SLAB ? j0[q] + R + 1 : ja;
+      rhb[q] = bld<T, V>(RrN, hb, (unsigned)rb * rowT);
+      rha[q] = bld<T, V>(RrN, ha, (unsigned)ra * rowT);
+      pnb[q] = bld<T, V>(RpN, hb, (unsigned)rb * rowT);
+      pna[q] = bld<T, V>(RpN, ha, (unsigned)ra * rowT);
+      if constexpr (kParkHalos) {                            // parked at once: no register of the entry survives into the loop
         T* hs = halo_s + (size_t)((wave * NQ + q) * 2) * 64 * V + lane * V;
         stv<T, V>(hs, pnb[q]);
         stv<T, V>(hs + 64 * V, pna[q]);
-      }
       }
       int side, er;
       ring_lane(lane, R, side, er);
@@ -961,7 +359,7 @@ __global__ __launch_bounds__(kPersistThreads) void cg_persist1(CgArgs<T> a, Pers
     }
   }
 
-  // ---- coefficient pipeline (as in cg_persist): both passes of an iteration stream the coefficient rows of my regions in
+  // ---- 2 COEFFICIENT PIPELINE (as in cg_persist) and the lambdas of the row loops: both passes of an iteration stream the coefficient rows of my regions in
   // the same order; the loads of row t + D are issued when row t has been consumed, circularly.
   constexpr int coef_regs = ((SYM ? 2 : 4) * (int)sizeof(CT) * V + (RECON ? 0 : (int)sizeof(T) * V)) / 4;   // VGPRs of a row in flight
   constexpr int NT = NQ * R;
@@ -1001,7 +399,7 @@ __global__ __launch_bounds__(kPersistThreads) void cg_persist1(CgArgs<T> a, Pers
   // (behind the publish, in front of the polling: the SIMDs have nothing else to do for a microsecond or two) and kept in
   // registers; U then skips the stencil of those rows.  With the back-and-forth order these are the rows D ended with: their
   // coefficients are still in registers.  Same instructions on the same registers as D's z': bitwise the same values.
-  constexpr int kAhead = (kHier && NQ == 1 && NT == 16 && SYM && RECON && sizeof(T) == 8 && sizeof(CT) == 4) ? PISO_PERSIST1_AHEAD : 0;
+  constexpr int kAhead = (!LOCAL && NQ == 1 && NT == 16 && SYM && RECON && sizeof(T) == 8 && sizeof(CT) == 4) ? PISO_PERSIST1_AHEAD : 0;
   static_assert(kAhead <= Dw || kAhead == 0, "the rows computed ahead are rows whose coefficients D left in registers");
   constexpr bool kShLate = kAhead > 0 && !SLAB && NQ == 1 && SYM;
   // kKeepZ (small regions: a wave's rows are few): z' of D stays in registers until U has used it - U runs no stencil at all (the
@@ -1031,7 +429,7 @@ __global__ __launch_bounds__(kPersistThreads) void cg_persist1(CgArgs<T> a, Pers
   typedef __attribute__((address_space(3))) unsigned char lds_u8;
   unsigned ring_a = (unsigned)(unsigned long)(lds_u8*)ring_s + (unsigned)(wave * NQ * kRingBytes);
   asm volatile("" : "+v"(ring_a));
-  if constexpr (kParkRing) {                                 // the entry's ring columns go to the wave's block at once
+  if constexpr (kRingLds) {                                  // the entry's ring columns go to the wave's block at once
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
       const unsigned rb = ring_a + (unsigned)(q * kRingBytes) + (unsigned)lane * (unsigned)sizeof(T);
@@ -1155,7 +553,7 @@ __global__ __launch_bounds__(kPersistThreads) void cg_persist1(CgArgs<T> a, Pers
       }
     }
   };
-  // ---- z' on the ring, as published by the neighbours (rows below / above, the two neighbouring columns): issued right after
+  // z' on the ring, as published by the neighbours (rows below / above, the two neighbouring columns): issued right after
   // the exchange (every record seen = every perimeter store completed), consumed at the END of U - the row loop hides the trip
   T eZ[NQ];
   Vec<T, V> hbZ[NQ], haZ[NQ];
@@ -1214,10 +612,8 @@ __global__ __launch_bounds__(kPersistThreads) void cg_persist1(CgArgs<T> a, Pers
 
   unsigned epoch = c.epoch0;
   bool healthy = true, first = true;
-  unsigned long long tacc[5] = {0, 0, 0, 0, 0}, tsub[4] = {0, 0, 0, 0}, tlast = (kPersistDiag && c.timing) ? wall_clock64() : 0;
-  auto tick = [&](int slot) __attribute__((always_inline)) {     // diagnostic builds only (-DPISO_PERSIST_DIAG): D / exchange / U clocks
-    if (kPersistDiag && c.timing) { const unsigned long long t = wall_clock64(); tacc[slot] += t - tlast; tlast = t; }
-  };
+  unsigned long long tacc[5] = {0, 0, 0, 0, 0}, tsub[4] = {0, 0, 0, 0};
+  PhaseClock clk((kPersistDiag && c.timing) ? tacc : nullptr);   // diagnostic builds only (-DPISO_PERSIST_DIAG): D / exchange / U clocks
   // the stopping test of iteration k_begin was left to this launch by the previous one (pressure_solve_op.cu.cc:312-335)
   if (!st.done && k > 0 && (k % 5) == 0) {                  // (!done: a launch queued behind a converged one changes nothing)
     const int exceeded = tB[2] > 0;
@@ -1243,7 +639,7 @@ __global__ __launch_bounds__(kPersistThreads) void cg_persist1(CgArgs<T> a, Pers
     } else {
       Rz = (k & 1) ? Rz1 : Rz0;
     }
-    // ---- D(k): p = r + beta p on my cells and on the ring; z' = L p; sums; the perimeter of z' goes out
+    // ---- 3 D(k): p = r + beta p on my cells and on the ring; z' = L p; sums; the perimeter of z' goes out
     T sD[kX1Values] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (has[0]) {
 #pragma unroll
@@ -1253,13 +649,12 @@ __global__ __launch_bounds__(kPersistThreads) void cg_persist1(CgArgs<T> a, Pers
 #pragma unroll
           for (int e = 0; e < V; ++e) pp[q][jj].v[e] = fma(beta, pp[q][jj].v[e], rr[q][jj].v[e]);
         }
-        if constexpr (kParkRing) {
+        if constexpr (kRingLds) {
           const unsigned rb = ring_a + (unsigned)(q * kRingBytes) + (unsigned)lane * (unsigned)sizeof(T);
           const T e_old = *(lds_T*)(unsigned long)rb, r_col = *(lds_T*)(unsigned long)(rb + kRingR);
           *(lds_T*)(unsigned long)rb = fma(beta, e_old, r_col);
         } else {
-        edge[q] = fma(beta, edge[q], eR[q]);
-        if constexpr (kRingLds) *(lds_T*)(unsigned long)(ring_a + (unsigned)(q * kRingBytes) + (unsigned)lane * (unsigned)sizeof(T)) = edge[q];
+          edge[q] = fma(beta, edge[q], eR[q]);
         }
         T* hs = halo_s + (kParkHalos ? (size_t)((wave * NQ + q) * 2) * 64 * V + lane * V : 0);
         if constexpr (kParkHalos) {
@@ -1301,9 +696,11 @@ __global__ __launch_bounds__(kPersistThreads) void cg_persist1(CgArgs<T> a, Pers
         PISO_SB_A2;
       }
     }
+    // ---- 4 EXCHANGE + SCALARS: the eight sums of all workgroups (with z' of U's first rows computed while the records travel), the
+    // stopping test, alpha and beta
     sD[6] = lU[0]; sD[7] = lU[1];
     ++epoch;
-    tick(0);
+    clk.split(0);
     Vec<T, V> zs[kAhead > 0 ? kAhead : 1];
     auto z_ahead = [&]() __attribute__((always_inline)) {
       if constexpr (kAhead > 0) {
@@ -1317,12 +714,11 @@ __global__ __launch_bounds__(kPersistThreads) void cg_persist1(CgArgs<T> a, Pers
         }
       }
     };
-    if constexpr (kHier) healthy = grid_exchange8_hier<T, (SLAB ? kPollDelay2Xg : (kAhead > 0 ? kPollDelay2 : kPollDelay2NoAhead)), SLAB>(c, sD, epoch, smem, hx, hier_s + 2, z_ahead, (kPersistDiag && c.timing) ? tsub : nullptr, sl_off, smem + 2 * kX1Sm);
-    else if constexpr (kLocalAll) healthy = grid_exchange8_local<T>(c, sD, epoch, smem, slot, nslots, hier_s + 2, (kPersistDiag && c.timing) ? tsub : nullptr);
-    else healthy = grid_exchange8<T, LOCAL>(c, sD, epoch, smem, slot, nslots, NoPrefetch(), (kPersistDiag && c.timing) ? tsub : nullptr);
-    tick(1);
+    if constexpr (LOCAL) healthy = grid_exchange8_local<T>(c, sD, epoch, smem, slot, nslots, hier_s + 2, (kPersistDiag && c.timing) ? tsub : nullptr);
+    else healthy = grid_exchange8_hier<T, (SLAB ? kPollDelay2Xg : (kAhead > 0 ? kPollDelay2 : kPollDelay2NoAhead)), SLAB>(c, sD, epoch, smem, hx, hier_s + 2, z_ahead, (kPersistDiag && c.timing) ? tsub : nullptr, sl_off, smem + 2 * kX1Sm);
+    clk.split(1);
     if (!healthy) break;
-    // ---- the stopping test of iteration k, one exchange late but before anything moves (x = x_k): (:312-335)
+    // the stopping test of iteration k, one exchange late but before anything moves (x = x_k): (:312-335)
     if (!first) {
       sumr = sD[6]; cnt_last = sD[7];
       if (k > 0 && (k % 5) == 0) {
@@ -1333,14 +729,14 @@ __global__ __launch_bounds__(kPersistThreads) void cg_persist1(CgArgs<T> a, Pers
       if (st.done) break;
     }
     first = false;
-    // ---- alpha (:301-302) and, by one-step recurrences from the direct sums, what beta of the next iteration needs
+    // alpha (:301-302) and, by one-step recurrences from the direct sums, what beta of the next iteration needs
     vs = uniform(sc_c * sD[0]);
     pz = uniform(sD[2] + vs * sD[0]);
     alpha = uniform((absval(pz) > 0) ? sD[1] / pz : (T)0);
     rz_next = uniform(sD[3] - alpha * (sD[4] + vs * sD[5]));
     sumr = uniform(sumr - alpha * (sD[5] + ncells * vs));
     beta = uniform(-(rz_next + vs * sumr) / pz);             // ... of iteration k + 1 (see above)
-    // ---- U(k): z' again, x += alpha p, r -= alpha (z' + vs) on my cells and on the ring
+    // ---- 5 U(k): z' again, x += alpha p, r -= alpha (z' + vs) on my cells and on the ring
     lU[0] = 0; lU[1] = 0;
     int cnt_wave = 0;                                        // #{|r_{k+1}| >= accuracy} of the whole wave, counted on the scalar unit
     if (has[0]) {
@@ -1418,16 +814,16 @@ __global__ __launch_bounds__(kPersistThreads) void cg_persist1(CgArgs<T> a, Pers
           const bool ok = (side == 0 ? lcol_ok[q] : rcol_ok[q]) && j0[q] + er_unused < a.ny_true;
           if (!ok) vse = 0;
         }
-        if constexpr (kParkRing) {
+        if constexpr (kRingLds) {
           const unsigned rb = ring_a + (unsigned)(q * kRingBytes) + (unsigned)lane * (unsigned)sizeof(T) + kRingR;
           *(lds_T*)(unsigned long)rb = fma(-alpha, eZ[q] + vse, (T) * (lds_T*)(unsigned long)rb);
         } else {
-        eR[q] = fma(-alpha, eZ[q] + vse, eR[q]);
+          eR[q] = fma(-alpha, eZ[q] + vse, eR[q]);
         }
       }
       lU[1] = (lane == 0) ? (T)cnt_wave : (T)0;              // (the exchange adds the lanes of a wave)
     }
-    tick(2);
+    clk.split(2);
   }
   if (kPersistDiag && c.timing && threadIdx.x == 0) {
 #pragma unroll
@@ -1437,18 +833,17 @@ __global__ __launch_bounds__(kPersistThreads) void cg_persist1(CgArgs<T> a, Pers
     c.timing[9 * nslots + slot] = (unsigned long long)(__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & 7);   // the XCD I ran on
     c.timing[10 * nslots + slot] = (unsigned long long)wg;                                                              // the band of regions I own
   }
-  // ---- the last U's sum r and count are only known per workgroup: one more exchange (once per segment)
+  // ---- 6 EXIT.  The last U's sum r and count are only known per workgroup: one more exchange (once per segment)
   T tOut[3] = {rz_next, sumr, cnt_last};
   if (!first && healthy && !st.done) {
     T sX[kX1Values] = {0, 0, 0, 0, 0, 0, lU[0], lU[1]};
     ++epoch;
-    if constexpr (kHier) healthy = grid_exchange8_hier<T, kPollDelay2NoAhead, SLAB>(c, sX, epoch, smem, hx, hier_s + 2, NoPrefetch(), nullptr, sl_off, smem + 2 * kX1Sm);     // (nothing to compute ahead)
-    else if constexpr (kLocalAll) healthy = grid_exchange8_local<T>(c, sX, epoch, smem, slot, nslots, hier_s + 2);
-    else healthy = grid_exchange8<T, LOCAL>(c, sX, epoch, smem, slot, nslots);
+    if constexpr (LOCAL) healthy = grid_exchange8_local<T>(c, sX, epoch, smem, slot, nslots, hier_s + 2);
+    else healthy = grid_exchange8_hier<T, kPollDelay2NoAhead, SLAB>(c, sX, epoch, smem, hx, hier_s + 2, NoPrefetch(), nullptr, sl_off, smem + 2 * kX1Sm);     // (nothing to compute ahead)
     tOut[1] = sX[6]; tOut[2] = sX[7];
   }
 
-  // ---- back to the global-memory state of the two-kernel path (iteration k reads its direction from p[k & 1])
+  // back to the global-memory state of the two-kernel path (iteration k reads its direction from p[k & 1])
   // (the pointers of the exit are read again from the kernarg segment: held in SGPRs across the loop they are spilled, and the
   // reloads of OTHER spilled values land in the row loops)
   struct { T *r, *x, *pk, *partsB, *scal; const T* gB; CgState* state; int nB; } ax;       // (pk: p[k & 1])

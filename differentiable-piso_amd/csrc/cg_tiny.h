@@ -16,7 +16,6 @@
 #pragma once
 #include "cg_kernels.h"
 #include "cg_persist.h"
-#include "cg_persist1.h"
 
 namespace piso {
 
@@ -206,7 +205,7 @@ __global__ __launch_bounds__(kTinyThreads) void cg_tiny(const T* __restrict__ L,
 // LDS, off the dependent chain); the south / north neighbours of the direction are the thread's own registers - for a wave's edge
 // rows: RING COPIES of the neighbouring wave's row, advanced with the owner's arithmetic (see cols_solve) - west / east come from
 // the neighbouring lanes through the DPP wavefront shifts.  LDS traffic per iteration: x read + write, 2 z' row writes + 2 reads
-// per wave and one line of wave sums (cg_tiny: ~90 accesses per thread); ONE barrier per iteration.  The block reduction is the exchange of cg_persist1.h in small: reduce-scatter butterfly of the eight partial sums
+// per wave and one line of wave sums (cg_tiny: ~90 accesses per thread); ONE barrier per iteration.  The block reduction is the exchange of cg_persist.h in small: reduce-scatter butterfly of the eight partial sums
 // inside a wave (lane l ends with value l & 7), one LDS line [8 values][8 waves], ONE barrier, one LDS read per lane and a
 // three-step tree over the waves - every wave computes the same bits.
 // PERX (periodic x) needs nx == 64: the wavefront ROTATES are the wrap-around.

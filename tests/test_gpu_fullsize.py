@@ -63,7 +63,7 @@ def test_persistent_cg_equals_two_kernel_path_2048(walls, piso_option):
 
 @pytest.mark.parametrize("shape", [(2048, 2048), (1024, 256), (512, 512), (256, 256), (512, 256)])
 def test_persistent_cg_is_reproducible_bit_for_bit_from_run_to_run(shape, piso_option):
-    """The exchange adds the workgroups' records of an XCD in the order of their workgroup INDEX (cg_persist1.h: hier_enter), not in
+    """The exchange adds the workgroups' records of an XCD in the order of their workgroup INDEX (cg_persist.h: hier_enter), not in
     the order they happened to arrive at the launch: the same solve on the same input gives the same bits, and - the stopping test of
     the shifted system being as sensitive as it is - the same iteration count.  (By arrival order the 2048^2 benchmark's forward solves
     took 325 - 360 iterations on one input.)  Covers the 16-row instance and the one-region-per-wave instance of the mid-size grids."""

@@ -205,7 +205,7 @@ def test_forward_step_launches_outside_the_solver_iterations():
 def test_unrolled_step_forward_and_reverse_is_reproducible_bit_for_bit(n):
     """Two runs of the benchmark's workload (two unrolled steps forward, the reverse sweep of L = 1/2 |u_2|^2) on the same input give
     the same loss and the same dL/du_0 to the last bit: every reduction on the path adds in a fixed order - the assembly has none, the
-    BiCGStab's partial sums live in fixed slots, the CG's exchange adds an XCD's records by workgroup index (cg_persist1.h: hier_enter),
+    BiCGStab's partial sums live in fixed slots, the CG's exchange adds an XCD's records by workgroup index (cg_persist.h: hier_enter),
     the one-XCD mode by region slot, the glue kernels have no reductions."""
     import os, sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -221,7 +221,7 @@ def test_unrolled_step_forward_and_reverse_is_reproducible_bit_for_bit(n):
             g1, loss1, _ = bench.run_unrolled(P, 2, backward=True)
             its1 = (int(P["ps"].last_iterations), int(P["ps"].last_adjoint_iterations))
             if Nn.cg_last_xcd_map() != m0 or (its1 != its0 and len(m0) > 0):
-                # (the precondition - cg_persist1.h: hier_enter - can only be read back for the LAST solve; a different iteration count of
+                # (the precondition - cg_persist.h: hier_enter - can only be read back for the LAST solve; a different iteration count of
                 # an earlier one on a shared GPU is the same story)
                 pytest.skip("the hardware dealt the workgroups to the XCDs differently between two launches (a GPU somebody else uses as well)")
             assert its1 == its0
