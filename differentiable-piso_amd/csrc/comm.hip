@@ -104,6 +104,34 @@ __global__ __launch_bounds__(kBlock) void peer_exchange_rows(PeerView pv, const 
   for (int i = threadIdx.x; i < nx; i += kBlock) halo[i] = __longlong_as_double((long long)peer_load(row + i));
 }
 
+// ---- peer transport: all-gather of `count` doubles per rank (count * world <= kGatherCells).  Every rank writes its chunk as tagged
+// words {32 payload bits | epoch} into the gather area of EVERY rank's mailbox (its own included), then polls its own area and copies
+// out in rank order.  No flag and no fence: a word that carries the epoch is complete by itself.  The area alternates between two
+// halves by the parity of the gather's own sequence number: gather n + 2 reuses the half of gather n, and a rank starts it only after
+// it finished n + 1, for which every rank had to contribute - which a rank does only after it copied out of n.
+__global__ __launch_bounds__(kBlock) void peer_allgather(PeerView pv, size_t area, const double* __restrict__ src, double* __restrict__ dst, int count,
+                                                         unsigned seq, int* err) {
+  const size_t base = area + (size_t)(seq & 1) * PeerLayout::kGatherParityBytes;
+  const int tid = blockIdx.x * kBlock + threadIdx.x, nt = gridDim.x * kBlock;
+  for (int w = tid; w < 2 * count; w += nt) {
+    const peer_u64 word = peer_tagged(src[w >> 1], w & 1, seq);
+    for (int p = 0; p < pv.world; ++p) peer_store(reinterpret_cast<peer_u64*>(pv.mbox[p] + base) + (size_t)pv.rank * 2 * count + w, word);
+  }
+  const peer_u64* mine = reinterpret_cast<const peer_u64*>(pv.mbox[pv.rank] + base);
+  const int total = count * pv.world;
+  for (int i = tid; i < total; i += nt) {
+    peer_u64 lo = 0, hi = 0;
+    unsigned spins = 0;
+    while (true) {
+      lo = peer_load(mine + 2 * (size_t)i); hi = peer_load(mine + 2 * (size_t)i + 1);
+      if ((unsigned)(lo & 0xffffffffull) == seq && (unsigned)(hi & 0xffffffffull) == seq) break;
+      if (++spins > kPeerSpinLimit) { *err = 1; return; }
+      __builtin_amdgcn_s_sleep(2);
+    }
+    dst[i] = peer_untag(lo, hi);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ host collectives (slab_comm.h)
 // (a communicator is made by piso_comm_create or piso_comm_peer_create[_fd] only: what is not PEER is RCCL and has its ncclComm_t)
 static bool is_peer(const PisoComm* pc) { return pc->transport == TRANSPORT_PEER; }
@@ -123,6 +151,17 @@ int comm_allreduce_i32(PisoComm* pc, int* buf, int count, hipStream_t s) {
   return PISO_OK;
 }
 int comm_allgather_f64(PisoComm* pc, const double* src, double* dst, size_t count, hipStream_t s) {
+  if (is_peer(pc)) {
+    if (count * (size_t)pc->world > (size_t)kGatherCells) { set_error_msg("peer transport: an all-gather carries at most 8192 doubles over all ranks"); return PISO_ERR_INVALID_ARG; }
+    if (count == 0) return PISO_OK;
+    if (pc->world == 1 && opt(OPT_SLAB_FORCE) <= 0) {
+      if (src != dst) PISO_HIP_CHECK(hipMemcpyAsync(dst, src, count * sizeof(double), hipMemcpyDeviceToDevice, s));
+      return PISO_OK;
+    }
+    const int grid = (int)((2 * count + kBlock - 1) / kBlock);
+    peer_allgather<<<grid < 32 ? grid : 32, kBlock, 0, s>>>(make_view(pc, true), PeerLayout::gather_area(pc->row_cap), src, dst, (int)count, ++pc->seq_ga, pc->err);
+    return PISO_OK;
+  }
   PISO_NCCL_CHECK(g_rccl.AllGather(src, dst, count, ncclDouble, pc->comm, s));
   return PISO_OK;
 }
@@ -417,6 +456,17 @@ int piso_comm_exchange(void* comm, void* vec, int dtype, const int* msgs28, piso
   }
   if (dtype < 0 || dtype > 2) { set_error_msg("piso_comm_exchange: dtype must be 0 (float), 1 (double) or 2 (int32)"); return PISO_ERR_INVALID_ARG; }
   return comm_exchange_segments(pc, vec, dtype, m, static_cast<hipStream_t>(stream_));
+}
+// All-gather of `count` doubles per rank in rank order: dst [count * world] on every rank (both transports; peer: count * world <= 8192,
+// and one rank copies unless the option slab_force sends the chunk through its own mailbox).  Queued on the stream.
+int piso_comm_allgather_f64(void* comm, const void* src, void* dst, int count, piso_stream_t stream_) {
+  const piso::OptScope knobs;
+  PisoComm* pc = static_cast<PisoComm*>(comm);
+  if (!pc || !src || !dst || count < 0) { set_error_msg("piso_comm_allgather_f64: invalid argument"); return PISO_ERR_INVALID_ARG; }
+  PISO_TRY(comm_ready(pc, "piso_comm_allgather_f64: the peer communicator is not connected"));
+  PISO_TRY(comm_allgather_f64(pc, static_cast<const double*>(src), static_cast<double*>(dst), (size_t)count, static_cast<hipStream_t>(stream_)));
+  PISO_LAUNCH_CHECK();
+  return PISO_OK;
 }
 // did any wait on a peer give up since the last call?  (agreed over the ranks; synchronises the stream)
 int piso_comm_check(void* comm, piso_stream_t stream_) {

@@ -31,8 +31,12 @@
 // Reductions are two-stage, fixed order (per-block partials, re-added in index order): a solve is reproducible bit for bit.  alpha,
 // beta and the sums stay on the device; the host queues check_every iterations, then reads the state through a pinned word; kernels of
 // iterations queued after convergence see the device flag and return at once, so neither x nor the count depends on the cadence.
-#include "piso_common.h"
+#include <vector>
+
+#include "mg_slab_plan.h"
 #include "options.h"
+#include "piso_common.h"
+#include "slab_comm.h"
 
 namespace piso {
 
@@ -49,6 +53,10 @@ constexpr int kMgMaxLevels = 16;
 constexpr int kMgGrid = 1024;          // grid cap of every kernel that publishes partials (4 workgroups per CU)
 constexpr int kCheckEvery = 4;         // iterations queued between two host looks
 constexpr double kRowSumTol = 1e-9;    // rank_deficient = 1: max|row sum| must stay below this times mean|diag|
+
+// (the host-only plan of mg_slab_plan.h restates the constants that shape a hierarchy)
+static_assert(kMinDim == kPlanMinDim && kTailCells == kPlanTailCells && kTailLds == kPlanTailLds && kTailMaxLevels == kPlanTailMaxLevels &&
+              kMgMaxLevels == kPlanMaxLevels, "mg_slab_plan.h and mg.hip disagree about the hierarchy's constants");
 
 struct MgState { int done, iterations, flags, pad; };
 enum { MG_FLAG_BORDER = 1, MG_FLAG_ZERO_DIAG_ROW = 2, MG_FLAG_NOT_SINGULAR = 4 };
@@ -89,57 +97,6 @@ __device__ __forceinline__ double stencil(const Lv& L, int c, double vs, double 
 __device__ __forceinline__ void ph_pre1(const Lv& L, const double* r, double* z, Walk w) {
   for (int c = w.begin; c < L.n; c += w.step) z[c] = L.dinv[c] * r[c];
 }
-// sweeps 1 and 2 from a zero guess in one stencil pass: z1 = dinv r is pointwise, z2 = z1 + dinv (r - A z1)
-__device__ __forceinline__ void ph_pre2(const Lv& L, const double* r, double* z, Walk w) {
-  for (int c = w.begin; c < L.n; c += w.step) {
-    const int j = c / L.nx, i = c - j * L.nx;
-    const Nb q = neighbours(c, i, j, L.nx, L.ny);
-    const double di = L.dinv[c], rc = r[c], z1 = di * rc;
-    const double az = stencil(L, c, L.dinv[q.s] * r[q.s], L.dinv[q.w] * r[q.w], z1, L.dinv[q.e] * r[q.e], L.dinv[q.n] * r[q.n]);
-    z[c] = z1 + di * (rc - az);
-  }
-}
-// one sweep zout = z' + dinv (r - A z'), z' = zin (+ P e on the present cells where e is given); returns the thread's part of (r, zout)
-__device__ __forceinline__ double ph_jac(const Lv& L, const double* r, const double* zin, double* zout, const double* e, int nxc, Walk w) {
-  double acc = 0;
-  for (int c = w.begin; c < L.n; c += w.step) {
-    const int j = c / L.nx, i = c - j * L.nx;
-    const Nb q = neighbours(c, i, j, L.nx, L.ny);
-    const double di = L.dinv[c], rc = r[c];
-    double vs = zin[q.s], vw = zin[q.w], vc = zin[c], ve = zin[q.e], vn = zin[q.n];
-    if (e) {
-      const int iw = i > 0 ? i - 1 : L.nx - 1, ie = i < L.nx - 1 ? i + 1 : 0;
-      const int js = j > 0 ? j - 1 : L.ny - 1, jn = j < L.ny - 1 ? j + 1 : 0;
-      const int row = (j >> 1) * nxc, col = i >> 1;
-      if (L.dinv[q.s] != 0) vs += e[(js >> 1) * nxc + col];
-      if (L.dinv[q.w] != 0) vw += e[row + (iw >> 1)];
-      if (di != 0) vc += e[row + col];
-      if (L.dinv[q.e] != 0) ve += e[row + (ie >> 1)];
-      if (L.dinv[q.n] != 0) vn += e[(jn >> 1) * nxc + col];
-    }
-    const double zo = di != 0 ? vc + di * (rc - stencil(L, c, vs, vw, vc, ve, vn)) : 0.0;
-    zout[c] = zo;
-    acc += rc * zo;
-  }
-  return acc;
-}
-// residual of the present cells, summed over each 2 x 2 aggregate: rc = P^T (r - A z)
-__device__ __forceinline__ void ph_restrict(const Lv& L, const double* r, const double* z, double* rc, int nxc, int nyc, Walk w) {
-  for (int k = w.begin; k < nxc * nyc; k += w.step) {
-    const int J = k / nxc, I = k - J * nxc;
-    double s = 0;
-    for (int dj = 0; dj < 2; ++dj)
-      for (int di = 0; di < 2; ++di) {
-        const int i = 2 * I + di, j = 2 * J + dj;
-        if (i >= L.nx || j >= L.ny) continue;
-        const int c = j * L.nx + i;
-        if (L.dinv[c] == 0) continue;
-        const Nb q = neighbours(c, i, j, L.nx, L.ny);
-        s += r[c] - stencil(L, c, z[q.s], z[q.w], z[c], z[q.e], z[q.n]);
-      }
-    rc[k] = s;
-  }
-}
 
 // sum over a block of any size up to 1024 threads, the same bits in every thread (lanes by butterfly, then the waves in order)
 __device__ __forceinline__ double mg_block_sum(double v, double* smem /* [16] */) {
@@ -169,46 +126,32 @@ __device__ __forceinline__ double mg_sum_partials(const double* part, int count,
   return mg_block_sum(s, smem);
 }
 
+// ---- the per-cell code that looks at neighbours, for the whole grid (mg_cells.inc; mg_slab.h includes it again for a rank's slab) -----------
+#define MG_N(name) name
+#define MG_GEO_PARAM
+#define MG_NB(c, i, j, nx, ny) neighbours(c, i, j, nx, ny)
+#define MG_JS(j, ny) j > 0 ? j - 1 : ny - 1
+#define MG_JN(j, ny) j < ny - 1 ? j + 1 : 0
+#define MG_EROW(j) (j >> 1)
+#define MG_FIRST_ROW(j) j == 0
+#define MG_LAST_ROW(j, ny) j == ny - 1
+#define MG_DIAG(Lin, idx) Lin[(size_t)idx * 5 + 2]
+#define MG_NCELLS(L) (double)L.n
+#define MG_DIRECTION_HALO_ROWS
+#include "mg_cells.inc"
+#undef MG_N
+#undef MG_GEO_PARAM
+#undef MG_NB
+#undef MG_JS
+#undef MG_JN
+#undef MG_EROW
+#undef MG_FIRST_ROW
+#undef MG_LAST_ROW
+#undef MG_DIAG
+#undef MG_NCELLS
+#undef MG_DIRECTION_HALO_ROWS
+
 // ---- hierarchy ------------------------------------------------------------------------------------------------------------------------
-// level 0: [N][5] -> five arrays + dinv; couplings into absent cells dropped; pattern checks; partials of sum|diag| (ALL rows, as the
-// reference's shift has it), the number of present cells, sum of b over them, max|row sum|
-__global__ __launch_bounds__(kBlock) void mg_setup0(const double* __restrict__ Lin, Lv L, const double* __restrict__ b, double* parts, MgState* st) {
-  __shared__ double smem[16];
-  double sd = 0, np = 0, sb = 0, mr = 0;
-  int flags = 0;
-  const Walk w = grid_walk();
-  for (int c = w.begin; c < L.n; c += w.step) {
-    const int j = c / L.nx, i = c - j * L.nx;
-    const Nb q = neighbours(c, i, j, L.nx, L.ny);
-    double v[5];
-#pragma unroll
-    for (int s = 0; s < 5; ++s) v[s] = Lin[(size_t)c * 5 + s];
-    const bool present = v[2] != 0;
-    // (a NaN there is no pattern: it flows into the solve and comes back as NaN)
-    if ((!L.per_y && ((j == 0 && v[0] != 0 && v[0] == v[0]) || (j == L.ny - 1 && v[4] != 0 && v[4] == v[4]))) ||
-        (!L.per_x && ((i == 0 && v[1] != 0 && v[1] == v[1]) || (i == L.nx - 1 && v[3] != 0 && v[3] == v[3]))))
-      flags |= MG_FLAG_BORDER;
-    if (!present && (v[0] != 0 || v[1] != 0 || v[3] != 0 || v[4] != 0)) flags |= MG_FLAG_ZERO_DIAG_ROW;
-    const int nb[5] = {q.s, q.w, c, q.e, q.n};
-#pragma unroll
-    for (int s = 0; s < 5; ++s)
-      if (s != 2 && (!present || Lin[(size_t)nb[s] * 5 + 2] == 0)) v[s] = 0;
-#pragma unroll
-    for (int s = 0; s < 5; ++s) L.c[s][c] = v[s];
-    L.dinv[c] = present ? kOmega / v[2] : 0.0;
-    sd += fabs(v[2]);
-    if (present) {
-      np += 1.0;
-      if (b) sb += b[c];
-      mr = nanmax(mr, fabs((((v[0] + v[1]) + v[2]) + v[3]) + v[4]));
-    }
-  }
-  sd = mg_block_sum(sd, smem); np = mg_block_sum(np, smem); sb = mg_block_sum(sb, smem); mr = mg_block_max_nan(mr, smem);
-  if (threadIdx.x == 0) {
-    parts[blockIdx.x] = sd; parts[kMgGrid + blockIdx.x] = np; parts[2 * kMgGrid + blockIdx.x] = sb; parts[3 * kMgGrid + blockIdx.x] = mr;
-  }
-  if (flags) atomicOr(&st->flags, flags);
-}
 __global__ __launch_bounds__(kBlock) void mg_setup_fin(const double* parts, int count, double* scal, int rank_deficient, int ncells, MgState* st) {
   __shared__ double smem[16];
   const double sd = mg_sum_partials(parts, count, smem), np = mg_sum_partials(parts + kMgGrid, count, smem);
@@ -222,35 +165,6 @@ __global__ __launch_bounds__(kBlock) void mg_setup_fin(const double* parts, int 
     scal[SC_RZ0] = 0; scal[SC_RZ1] = 0;
     if (rank_deficient && np > 0 && mr > kRowSumTol * (sd / np)) atomicOr(&st->flags, MG_FLAG_NOT_SINGULAR);
     (void)ncells;
-  }
-}
-// A_c = kGalerkin P^T A P, one coarse cell per thread
-__global__ __launch_bounds__(kBlock) void mg_coarsen(Lv F, Lv Cc) {
-  const Walk w = grid_walk();
-  for (int k = w.begin; k < Cc.n; k += w.step) {
-    const int J = k / Cc.nx, I = k - J * Cc.nx;
-    double dg = 0, oS = 0, oW = 0, oE = 0, oN = 0, scale = 0;
-    for (int dj = 0; dj < 2; ++dj)
-      for (int di = 0; di < 2; ++di) {
-        const int i = 2 * I + di, j = 2 * J + dj;
-        if (i >= F.nx || j >= F.ny) continue;
-        const int c = j * F.nx + i;
-        const double cc = F.c[2][c];
-        if (cc == 0) continue;
-        const Nb q = neighbours(c, i, j, F.nx, F.ny);
-        scale += fabs(cc);
-        dg += cc;
-        const double s = F.c[2][q.s] != 0 ? F.c[0][c] : 0.0, ww = F.c[2][q.w] != 0 ? F.c[1][c] : 0.0;
-        const double e = F.c[2][q.e] != 0 ? F.c[3][c] : 0.0, n = F.c[2][q.n] != 0 ? F.c[4][c] : 0.0;
-        if (dj == 1) dg += s; else oS += s;
-        if (di == 1) dg += ww; else oW += ww;
-        if (di == 0 && i + 1 < F.nx) dg += e; else oE += e;
-        if (dj == 0 && j + 1 < F.ny) dg += n; else oN += n;
-      }
-    dg *= kGalerkin; oS *= kGalerkin; oW *= kGalerkin; oE *= kGalerkin; oN *= kGalerkin;
-    if (!(fabs(dg) > kGuard * kGalerkin * scale)) dg = oS = oW = oE = oN = 0;
-    Cc.c[0][k] = oS; Cc.c[1][k] = oW; Cc.c[2][k] = dg; Cc.c[3][k] = oE; Cc.c[4][k] = oN;
-    Cc.dinv[k] = dg != 0 ? kOmega / dg : 0.0;
   }
 }
 __global__ __launch_bounds__(kBlock) void mg_export(Lv L, double* __restrict__ out) {
@@ -352,45 +266,6 @@ __global__ __launch_bounds__(kBlock) void mg_init(Lv L, const double* __restrict
     r[c] = L.dinv[c] != 0 ? b[c] - mean : 0.0;
   }
 }
-// the true residual r = b' - L x
-__global__ __launch_bounds__(kBlock) void mg_residual(Lv L, const double* __restrict__ b, const double* __restrict__ x, double* __restrict__ r, const double* scal,
-                                                      const MgState* st) {
-  if (st->done) return;
-  const double mean = scal[SC_MEAN_B];
-  const Walk w = grid_walk();
-  for (int c = w.begin; c < L.n; c += w.step) {
-    const int j = c / L.nx, i = c - j * L.nx;
-    const Nb q = neighbours(c, i, j, L.nx, L.ny);
-    r[c] = L.dinv[c] != 0 ? (b[c] - mean) - stencil(L, c, x[q.s], x[q.w], x[c], x[q.e], x[q.n]) : 0.0;
-  }
-}
-// p' = z + beta p, q = L p', partials of (p', q); block 0 publishes (r, z) for the update kernel and the next beta
-__global__ __launch_bounds__(kBlock) void mg_direction(Lv L, const double* z, const double* pold, double* pnew, double* q, const double* part_rz, int n_rz,
-                                                       double* scal, int k, int restart, double* part_pq, const MgState* st) {
-  if (st->done) return;
-  __shared__ double smem[16];
-  const double rz = mg_sum_partials(part_rz, n_rz, smem);
-  const double rz_old = scal[SC_RZ0 + ((k + 1) & 1)];
-  const double beta = (restart || rz_old == 0) ? 0.0 : rz / rz_old;
-  if (blockIdx.x == 0 && threadIdx.x == 0) scal[SC_RZ0 + (k & 1)] = rz;
-  double acc = 0;
-  const Walk w = grid_walk();
-  for (int c = w.begin; c < L.n; c += w.step) {
-    const int j = c / L.nx, i = c - j * L.nx;
-    const Nb nb = neighbours(c, i, j, L.nx, L.ny);
-    double ps, pw, pc, pe, pn;
-    if (restart) { ps = z[nb.s]; pw = z[nb.w]; pc = z[c]; pe = z[nb.e]; pn = z[nb.n]; }     // (beta = 0 must not touch an unset p)
-    else {
-      ps = z[nb.s] + beta * pold[nb.s]; pw = z[nb.w] + beta * pold[nb.w]; pc = z[c] + beta * pold[c];
-      pe = z[nb.e] + beta * pold[nb.e]; pn = z[nb.n] + beta * pold[nb.n];
-    }
-    const double qc = stencil(L, c, ps, pw, pc, pe, pn);
-    pnew[c] = pc; q[c] = qc;
-    acc += pc * qc;
-  }
-  acc = mg_block_sum(acc, smem);
-  if (threadIdx.x == 0) part_pq[blockIdx.x] = acc;
-}
 // x += alpha p, r -= alpha q, partials of max|r|
 __global__ __launch_bounds__(kBlock) void mg_update(int n, double* __restrict__ x, double* __restrict__ r, const double* __restrict__ p, const double* __restrict__ q,
                                                     const double* scal, int k, const double* part_pq, int n_pq, double* part_max, const MgState* st) {
@@ -426,15 +301,6 @@ __global__ __launch_bounds__(kBlock) void mg_sum_x(Lv L, const double* __restric
   s = mg_block_sum(s, smem);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
-// the constant mode of the shifted system: mean of x over the present cells := sum(b) / (c n_present^2), c = 0.1 sum|diag| / N
-__global__ __launch_bounds__(kBlock) void mg_finish(Lv L, double* __restrict__ x, const double* part, int count, const double* scal) {
-  __shared__ double smem[16];
-  const double sx = mg_sum_partials(part, count, smem);
-  const double np = scal[SC_NPRESENT], cshift = 0.1 * scal[SC_SUM_DIAG] / (double)L.n;
-  const double add = (np > 0 && cshift != 0) ? scal[SC_MEAN_B] / (cshift * np) - sx / np : 0.0;
-  const Walk w = grid_walk();
-  for (int c = w.begin; c < L.n; c += w.step) x[c] = L.dinv[c] != 0 ? x[c] + add : 0.0;
-}
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
 struct MgPlan {
@@ -448,24 +314,16 @@ static int mg_grid(int n) { return grid_for(n, kBlock, kMgGrid); }
 
 // carves the workspace (the same walk sizes it: piso_mg_workspace_bytes)
 static bool mg_plan(int nx, int ny, int per_x, int per_y, Arena& ar, MgPlan& P) {
-  int l = 0;
-  for (;; ++l) {
+  const MgDims d = mg_dims(nx, ny);                        // (mg_slab_plan.h: the one statement of the hierarchy's shape)
+  for (int l = 0; l < d.nlev; ++l) {
     Lv& L = P.lv[l];
-    L.nx = nx; L.ny = ny; L.n = nx * ny; L.per_x = per_x; L.per_y = per_y;
+    L.nx = d.nx[l]; L.ny = d.ny[l]; L.n = L.nx * L.ny; L.per_x = per_x; L.per_y = per_y;
     for (int s = 0; s < 5; ++s) L.c[s] = ar.take<double>(L.n);
     L.dinv = ar.take<double>(L.n);
     P.r[l] = ar.take<double>(L.n); P.z[l] = ar.take<double>(L.n); P.t[l] = ar.take<double>(L.n);
-    const int nxc = (nx + 1) / 2, nyc = (ny + 1) / 2;
-    if (nxc < kMinDim || nyc < kMinDim || l + 1 == kMgMaxLevels) break;
-    nx = nxc; ny = nyc;
   }
-  P.nlev = l + 1;
-  P.tail_first = -1;
-  for (int f = 0; f < P.nlev; ++f) {
-    int cells = 0;
-    for (int k = f; k < P.nlev; ++k) cells += P.lv[k].n;
-    if (P.lv[f].n <= kTailCells && cells <= kTailLds && P.nlev - f <= kTailMaxLevels) { P.tail_first = f; break; }
-  }
+  P.nlev = d.nlev;
+  P.tail_first = d.tail_first;
   const int n0 = P.lv[0].n;
   P.p[0] = ar.take<double>(n0); P.p[1] = ar.take<double>(n0); P.q = ar.take<double>(n0);
   P.parts = ar.take<double>(4 * kMgGrid);
@@ -534,45 +392,46 @@ static double* mg_first_sweeps(const MgPlan& P, int l, const double* r, int nu, 
   return cur;
 }
 // z = M^-1 r0: returns where z of level 0 is; the last kernel leaves the partials of (r0, z) in P.part_rz (*n_rz of them)
-static double* mg_cycle(const MgPlan& P, const double* r0, int nu, bool use_tail, int* n_rz, hipStream_t stream) {
-  const int end = use_tail ? P.tail_first : P.nlev - 1;      // levels [0, end) have a coarser level and run as kernels of their own
+// (l0: the level r0 lives on - 0, or the first replicated level of a slab solve, which runs levels l0 .. coarsest exactly like this)
+static double* mg_cycle(const MgPlan& P, const double* r0, int nu, bool use_tail, int* n_rz, hipStream_t stream, int l0 = 0) {
+  const int end = use_tail ? P.tail_first : P.nlev - 1;      // levels [l0, end) have a coarser level and run as kernels of their own
   double* zc[kMgMaxLevels];
-  for (int l = 0; l < end; ++l) {
-    const double* r = l == 0 ? r0 : P.r[l];
+  for (int l = l0; l < end; ++l) {
+    const double* r = l == l0 ? r0 : P.r[l];
     zc[l] = mg_first_sweeps(P, l, r, nu, stream);
     mg_restrict<<<mg_grid(P.lv[l + 1].n), kBlock, 0, stream>>>(P.lv[l], r, zc[l], P.r[l + 1], P.lv[l + 1].nx, P.lv[l + 1].ny, P.st);
   }
-  const double* rend = end == 0 ? r0 : P.r[end];
+  const double* rend = end == l0 ? r0 : P.r[end];
   if (use_tail) {
     MgTail T;
     T.nlev = P.nlev - end;
     int off = 0;
     for (int k = 0; k < T.nlev; ++k) { T.lv[k] = P.lv[end + k]; T.off[k] = off; off += T.lv[k].n; }
-    mg_tail<<<1, kTailThreads, 0, stream>>>(T, rend, P.z[end], end == 0 ? P.part_rz : nullptr, nu, P.st);
+    mg_tail<<<1, kTailThreads, 0, stream>>>(T, rend, P.z[end], end == l0 ? P.part_rz : nullptr, nu, P.st);
     zc[end] = P.z[end];
     *n_rz = 1;
   } else {
     double* cur = mg_first_sweeps(P, end, rend, kCoarsestSweeps - 1, stream);
     double* nxt = cur == P.z[end] ? P.t[end] : P.z[end];
     const int g = mg_grid(P.lv[end].n);
-    mg_jacobi<<<g, kBlock, 0, stream>>>(P.lv[end], rend, cur, nxt, nullptr, 0, end == 0 ? P.part_rz : nullptr, P.st);
+    mg_jacobi<<<g, kBlock, 0, stream>>>(P.lv[end], rend, cur, nxt, nullptr, 0, end == l0 ? P.part_rz : nullptr, P.st);
     zc[end] = nxt;
     *n_rz = g;
   }
-  for (int l = end - 1; l >= 0; --l) {
+  for (int l = end - 1; l >= l0; --l) {
     const Lv& L = P.lv[l];
-    const double* r = l == 0 ? r0 : P.r[l];
+    const double* r = l == l0 ? r0 : P.r[l];
     const int g = mg_grid(L.n);
     double* cur = zc[l];
     for (int s = 0; s < nu; ++s) {
       double* nxt = cur == P.z[l] ? P.t[l] : P.z[l];
-      mg_jacobi<<<g, kBlock, 0, stream>>>(L, r, cur, nxt, s == 0 ? zc[l + 1] : nullptr, P.lv[l + 1].nx, (l == 0 && s == nu - 1) ? P.part_rz : nullptr, P.st);
+      mg_jacobi<<<g, kBlock, 0, stream>>>(L, r, cur, nxt, s == 0 ? zc[l + 1] : nullptr, P.lv[l + 1].nx, (l == l0 && s == nu - 1) ? P.part_rz : nullptr, P.st);
       cur = nxt;
     }
     zc[l] = cur;
-    if (l == 0) *n_rz = g;
+    if (l == l0) *n_rz = g;
   }
-  return zc[0];
+  return zc[l0];
 }
 static bool mg_use_tail(const MgPlan& P) { return P.tail_first >= 0 && opt(OPT_MG_TAIL) != 0; }
 
@@ -585,6 +444,8 @@ static int mg_common_args(const char* who, int nx, int ny, const void* a, const 
 }
 
 }  // namespace piso
+
+#include "mg_slab.h"
 
 using namespace piso;
 
@@ -688,6 +549,145 @@ int piso_mg_level_f64(int nx, int ny, int periodic_x, int periodic_y, const doub
   PISO_LAUNCH_CHECK();
   PISO_HIP_CHECK(hipStreamSynchronize(stream));
   return PISO_OK;
+}
+
+// ---- the same solver on y-slabs (mg_slab.h) -----------------------------------------------------------------------------------------------
+size_t piso_mg_slab_workspace_bytes(int nx, int ny_local, int world, int local_ranks) {
+  const piso::OptScope knobs;
+  if (ny_local < 1 || world < 1 || local_ranks < 1) return 0;
+  const MgSlabPlan sp = mg_slab_plan(nx, ny_local * world, world, opt(OPT_MG_SLAB_GATHER_CELLS));
+  if (sp.status) return 0;
+  return mg_slab_g_bytes(local_ranks) + (size_t)local_ranks * mg_slab_rank_bytes(sp);
+}
+
+int piso_mg_slab_plan(int nx, int ny, int world, int gather_cells, int* out, int capacity) {
+  const piso::OptScope knobs;
+  const MgSlabPlan sp = mg_slab_plan(nx, ny, world, gather_cells > 0 ? gather_cells : opt(OPT_MG_SLAB_GATHER_CELLS));
+  if (sp.status) set_error_msg(sp.msg);
+  return out ? mg_slab_plan_record(sp, out, capacity) : 0;
+}
+
+// what the three communicator entry points share: one context, the rank's rows
+static int mg_slab_comm_begin(MgSlab& M, const char* who, void* comm, int nx, int nyl, int px, int py, const double* laplace, const void* a, const void* b,
+                              void* ws, size_t ws_bytes, int sweeps, hipStream_t stream) {
+  PisoComm* pc = static_cast<PisoComm*>(comm);
+  char msg[96];
+  if (!pc || !laplace || !a || !b || !ws) { snprintf(msg, sizeof(msg), "%s: NULL pointer", who); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
+  snprintf(msg, sizeof(msg), "%s: the peer communicator is not connected", who);
+  PISO_TRY(comm_ready(pc, msg));
+  PISO_TRY(mg_slab_begin(M, who, nx, nyl, pc->world, 1, px, py, sweeps, pc, stream));
+  M.R[0].rank = pc->rank; M.R[0].Lin = laplace; M.R[0].b = nullptr;
+  return M.carve(who, ws, ws_bytes);
+}
+// ... and the emulated ones: `slabs` virtual ranks over the full arrays
+static int mg_slab_emulated_begin(MgSlab& M, const char* who, int slabs, int nx, int ny, int px, int py, const double* laplace, const void* a, const void* b,
+                                  void* ws, size_t ws_bytes, int sweeps, hipStream_t stream) {
+  char msg[96];
+  if (!laplace || !a || !b || !ws) { snprintf(msg, sizeof(msg), "%s: NULL pointer", who); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
+  if (slabs < 1 || slabs > kMaxRanks || ny < slabs) { snprintf(msg, sizeof(msg), "%s: needs 1 .. %d slabs", who, kMaxRanks); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
+  if (ny % slabs != 0) {                                      // (the plan's refusal, with the rule)
+    const MgSlabPlan sp = mg_slab_plan(nx, ny, slabs, opt(OPT_MG_SLAB_GATHER_CELLS));
+    set_error_msg(sp.msg);
+    return PISO_ERR_INVALID_ARG;
+  }
+  PISO_TRY(mg_slab_begin(M, who, nx, ny / slabs, slabs, slabs, px, py, sweeps, nullptr, stream));
+  for (int r = 0; r < slabs; ++r) { M.R[r].rank = r; M.R[r].Lin = laplace + (size_t)r * (ny / slabs) * nx * 5; M.R[r].b = nullptr; }
+  return M.carve(who, ws, ws_bytes);
+}
+
+int piso_mg_pcg_solve_slab_f64(void* comm, int nx, int ny_local, int periodic_x, int periodic_y, const double* laplace_local, const double* divergence_local,
+                               double* x_out_local, float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps,
+                               int* iterations_out, void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
+  const piso::OptScope knobs;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const char* who = "piso_mg_pcg_solve_slab";
+  if (max_iterations < 1 || residual_reset < 1) { set_error_msg("piso_mg_pcg_solve_slab: max_iterations and residual_reset must be positive"); return PISO_ERR_INVALID_ARG; }
+  MgSlab M;
+  PISO_TRY(mg_slab_comm_begin(M, who, comm, nx, ny_local, periodic_x, periodic_y, laplace_local, divergence_local, x_out_local, workspace, workspace_bytes, sweeps, stream));
+  M.R[0].b = divergence_local;
+  // a refusal of the set-up is the same on every rank (all-reduced flags); whatever else fails is agreed below
+  PISO_TRY(M.solve(accuracy, max_iterations, rank_deficient ? 1 : 0, residual_reset, sweeps, iterations_out));
+  PISO_HIP_CHECK(hipMemcpyAsync(x_out_local, M.R[0].x, (size_t)nx * ny_local * sizeof(double), hipMemcpyDeviceToDevice, stream));
+  return M.finish(who);
+}
+
+int piso_mg_pcg_solve_slab_emulated_f64(int slabs, int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence, double* x_out,
+                                        float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps, int* iterations_out,
+                                        void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
+  const piso::OptScope knobs;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const char* who = "piso_mg_pcg_solve_slab_emulated";
+  if (max_iterations < 1 || residual_reset < 1) { set_error_msg("piso_mg_pcg_solve_slab_emulated: max_iterations and residual_reset must be positive"); return PISO_ERR_INVALID_ARG; }
+  MgSlab M;
+  PISO_TRY(mg_slab_emulated_begin(M, who, slabs, nx, ny, periodic_x, periodic_y, laplace, divergence, x_out, workspace, workspace_bytes, sweeps, stream));
+  const size_t n = (size_t)nx * (ny / slabs);
+  for (int r = 0; r < slabs; ++r) M.R[r].b = divergence + r * n;
+  PISO_TRY(M.solve(accuracy, max_iterations, rank_deficient ? 1 : 0, residual_reset, sweeps, iterations_out));
+  for (int r = 0; r < slabs; ++r) PISO_HIP_CHECK(hipMemcpyAsync(x_out + r * n, M.R[r].x, n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+  return M.finish(who);
+}
+
+// one cycle: the rank's rows of r go into the outer residual's rows, its rows of z come out
+static int mg_slab_one_cycle(MgSlab& M, const double* const* r_rows, double* const* z_rows, int sweeps, const char* who) {
+  PISO_TRY(M.build(0));
+  const size_t n = (size_t)M.sp.d.nx[0] * M.sp.nyl;
+  for (int q = 0; q < M.nloc(); ++q) PISO_HIP_CHECK(hipMemcpyAsync(M.R[q].ro, r_rows[q], n * sizeof(double), hipMemcpyDeviceToDevice, M.s));
+  PISO_TRY(M.cycle(sweeps));
+  for (int q = 0; q < M.nloc(); ++q) PISO_HIP_CHECK(hipMemcpyAsync(z_rows[q], M.R[q].z_top, n * sizeof(double), hipMemcpyDeviceToDevice, M.s));
+  M.record(sweeps, 0, 1, 0);
+  return M.finish(who);
+}
+
+int piso_mg_vcycle_slab_f64(void* comm, int nx, int ny_local, int periodic_x, int periodic_y, const double* laplace_local, const double* r_local, double* z_local,
+                            int sweeps, void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
+  const piso::OptScope knobs;
+  MgSlab M;
+  const char* who = "piso_mg_vcycle_slab";
+  PISO_TRY(mg_slab_comm_begin(M, who, comm, nx, ny_local, periodic_x, periodic_y, laplace_local, r_local, z_local, workspace, workspace_bytes, sweeps,
+                              static_cast<hipStream_t>(stream_)));
+  return mg_slab_one_cycle(M, &r_local, &z_local, sweeps, who);
+}
+
+int piso_mg_vcycle_slab_emulated_f64(int slabs, int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* r_in, double* z_out, int sweeps,
+                                     void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
+  const piso::OptScope knobs;
+  MgSlab M;
+  const char* who = "piso_mg_vcycle_slab_emulated";
+  PISO_TRY(mg_slab_emulated_begin(M, who, slabs, nx, ny, periodic_x, periodic_y, laplace, r_in, z_out, workspace, workspace_bytes, sweeps, static_cast<hipStream_t>(stream_)));
+  const size_t n = (size_t)nx * (ny / slabs);
+  std::vector<const double*> r(slabs);
+  std::vector<double*> z(slabs);
+  for (int q = 0; q < slabs; ++q) { r[q] = r_in + q * n; z[q] = z_out + q * n; }
+  return mg_slab_one_cycle(M, r.data(), z.data(), sweeps, who);
+}
+
+// a rank's rows of a sharded level, or the whole replicated level, as [nx_out * rows_out][5] (laplace_level_out NULL: sizes only)
+static int mg_slab_level(MgSlab& M, int q, int level, int* nx_out, int* rows_out, double* out, const char* who) {
+  if (level < 0 || level >= M.sp.d.nlev) { *nx_out = 0; *rows_out = 0; set_error_msg("piso_mg_level_slab: no such level"); return PISO_ERR_INVALID_ARG; }
+  *nx_out = M.sp.d.nx[level]; *rows_out = M.sp.rows[level];
+  if (!out) return PISO_OK;
+  PISO_TRY(M.build(0));
+  const Lv& L = M.R[q].lv[level];
+  mg_export<<<mg_grid(L.n), kBlock, 0, M.s>>>(L, out);
+  return M.finish(who);
+}
+int piso_mg_level_slab_f64(void* comm, int nx, int ny_local, int periodic_x, int periodic_y, const double* laplace_local, int level, int* nx_out, int* rows_out,
+                           double* laplace_level_out, void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
+  const piso::OptScope knobs;
+  MgSlab M;
+  const char* who = "piso_mg_level_slab";
+  PISO_TRY(mg_slab_comm_begin(M, who, comm, nx, ny_local, periodic_x, periodic_y, laplace_local, nx_out, rows_out, workspace, workspace_bytes, 1,
+                              static_cast<hipStream_t>(stream_)));
+  return mg_slab_level(M, 0, level, nx_out, rows_out, laplace_level_out, who);
+}
+int piso_mg_level_slab_emulated_f64(int slabs, int rank, int nx, int ny, int periodic_x, int periodic_y, const double* laplace, int level, int* nx_out, int* rows_out,
+                                    double* laplace_level_out, void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
+  const piso::OptScope knobs;
+  MgSlab M;
+  const char* who = "piso_mg_level_slab_emulated";
+  PISO_TRY(mg_slab_emulated_begin(M, who, slabs, nx, ny, periodic_x, periodic_y, laplace, nx_out, rows_out, workspace, workspace_bytes, 1, static_cast<hipStream_t>(stream_)));
+  if (rank < 0 || rank >= slabs) { set_error_msg("piso_mg_level_slab_emulated: no such rank"); return PISO_ERR_INVALID_ARG; }
+  return mg_slab_level(M, rank, level, nx_out, rows_out, laplace_level_out, who);
 }
 
 int piso_mg_last_dispatch(int* out, int capacity) {

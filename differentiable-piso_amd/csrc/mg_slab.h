@@ -1,0 +1,515 @@
+// The multigrid PCG of mg.hip on y-slabs (part of that translation unit: the per-cell code, the whole-grid kernels and mg_cycle are its).
+// The algorithm, its constants, the hierarchy's dimensions, the stopping rule, the constant-mode treatment and the device-side
+// alpha / beta are the one-GPU solver's; only where rows live and how sums are formed differ.  mg_slab_plan.h is the plan:
+//   * levels [0, g) are SHARDED: a rank holds its nyl >> l rows of every array plus one halo row below and one above (zero where the
+//     grid ends without a periodic wrap).  The slab kernels are the per-cell code of mg.hip with GeoSlab: y-neighbours are the rows
+//     below and above in storage, coarse indices are the rank's own (2 x 2 aggregates never straddle a cut);
+//   * level g and everything coarser is REPLICATED: a rank forms its rows of level g from its rows of level g - 1 (the coefficients
+//     once per solve, the restricted residual once per cycle), the rows are all-gathered, and every rank runs levels g .. coarsest
+//     with the whole-grid kernels / mg_tail (mg_cycle from level g).  A rank reads its part of the correction e_g directly;
+//   * g = 0: the cycle is replicated altogether; the outer iteration (x, r, p, q) is always sharded at level 0.
+// What crosses a cut goes through the host collectives of slab_comm.h only (both transports carry it): halo rows by comm_exchange_rows,
+// every global sum from per-rank fixed-order partials by comm_allreduce_f64 (bitwise the same on every rank: every rank takes the same
+// decisions), the rows of level g and the ranks' maxima of |r| by comm_allgather_f64 (the check kernel takes nanmax over them).
+// One driver over a vector of per-rank contexts and a link: the communicator link has one context, the loopback link V virtual ranks
+// on one device whose rows it copies - no mailbox - so that one process can test every cut.
+#pragma once
+
+namespace piso {
+
+constexpr int kMgSlabG = 16;           // doubles of a rank's collective buffer: [0] (r, z), [1] (p, q), [2] max|r|, [3] sum(x), [4 .. 8] set-up
+
+struct MgSlabRank {
+  int rank;
+  const double *Lin, *b;               // the rank's rows of the caller's matrix / right-hand side (b NULL: hierarchy or cycle only)
+  Lv lv[kMgMaxLevels];                 // l < g: the rank's rows (pointers at owned row 0, halo rows at -1 and ny); l >= g: the whole level
+  double *r[kMgMaxLevels], *z[kMgMaxLevels], *t[kMgMaxLevels];
+  Lv chunk;                            // the rank's rows of level g, before the gather
+  double* rchunk;
+  double *ro, *zo;                     // outer r (= r[0] where level 0 is sharded) and, g = 0, the rank's rows of z; both with halo rows
+  double *p[2], *x, *q;                // p, x with halo rows
+  double *parts, *part_rz, *part_pq, *part_max, *scal, *gmax, *g;
+  MgState* st;
+  double* z_top;                       // where the last cycle left the rank's z (halo rows filled)
+};
+
+// ---- slab instances of the per-cell code (mg_cells.inc a second time) ------------------------------------------------------------------------
+struct GeoSlab {
+  int row0, nyg;             // the rank's first global row of this level and the level's global rows
+  int coarse_global;         // the coarser level is replicated: its rows are global rows (else the rank's, with halo rows -1 and L.ny / 2)
+  const double* dg;          // set-up only: the diagonals of the rank's rows of the caller's matrix, with halo rows
+  double ncells;             // cells of the whole grid
+  __device__ __forceinline__ Nb nb(int c, int i, int nx) const {
+    Nb q;
+    q.s = c - nx; q.w = i > 0 ? c - 1 : c + (nx - 1); q.e = i < nx - 1 ? c + 1 : c - (nx - 1); q.n = c + nx;
+    return q;
+  }
+  // coarse row of the rank's fine row j, -1 and L.ny included (periodic y: row -1 of rank 0 is row nyg - 1; without, the halo row's dinv is
+  // zero and nobody reads the index)
+  __device__ __forceinline__ int erow(int j) const { return coarse_global ? ((row0 + j + nyg) % nyg) >> 1 : j >> 1; }
+};
+#define MG_N(name) name##_slab
+#define MG_GEO_PARAM , GeoSlab g
+#define MG_NB(c, i, j, nx, ny) g.nb(c, i, nx)
+#define MG_JS(j, ny) j - 1
+#define MG_JN(j, ny) j + 1
+#define MG_EROW(j) g.erow(j)
+#define MG_FIRST_ROW(j) g.row0 + j == 0
+#define MG_LAST_ROW(j, ny) g.row0 + j == g.nyg - 1
+#define MG_DIAG(Lin, idx) g.dg[idx]
+#define MG_NCELLS(L) g.ncells
+// p' = z + beta p on the rank's two halo rows as well: p never crosses a cut (beta is the same bits on every rank)
+#define MG_DIRECTION_HALO_ROWS                                                                                                  \
+  for (int h = blockIdx.x * blockDim.x + threadIdx.x; h < 2 * L.nx; h += gridDim.x * blockDim.x) {                            \
+    const int ch = h < L.nx ? h - L.nx : L.n + (h - L.nx);                                                                      \
+    pnew[ch] = restart ? z[ch] : z[ch] + beta * pold[ch];                                                                       \
+  }
+#include "mg_cells.inc"
+#undef MG_N
+#undef MG_GEO_PARAM
+#undef MG_NB
+#undef MG_JS
+#undef MG_JN
+#undef MG_EROW
+#undef MG_FIRST_ROW
+#undef MG_LAST_ROW
+#undef MG_DIAG
+#undef MG_NCELLS
+#undef MG_DIRECTION_HALO_ROWS
+
+__global__ __launch_bounds__(kBlock) void mg_slab_diag(const double* __restrict__ Lin, double* __restrict__ dg, int n) {
+  const Walk w = grid_walk();
+  for (int c = w.begin; c < n; c += w.step) dg[c] = Lin[(size_t)c * 5 + 2];
+}
+__global__ __launch_bounds__(kBlock) void mg_pre2_slab(Lv L, const double* r, double* z, const MgState* st, GeoSlab g) {
+  if (st->done) return;
+  ph_pre2_slab(L, r, z, grid_walk(), g);
+}
+__global__ __launch_bounds__(kBlock) void mg_jacobi_slab(Lv L, const double* r, const double* zin, double* zout, const double* e, int nxc, double* part_rz,
+                                                         const MgState* st, GeoSlab g) {
+  if (st->done) return;
+  __shared__ double smem[16];
+  double acc = ph_jac_slab(L, r, zin, zout, e, nxc, grid_walk(), g);
+  if (part_rz) {
+    acc = mg_block_sum(acc, smem);
+    if (threadIdx.x == 0) part_rz[blockIdx.x] = acc;
+  }
+}
+__global__ __launch_bounds__(kBlock) void mg_restrict_slab(Lv L, const double* r, const double* z, double* rc, int nxc, int nyc, const MgState* st, GeoSlab g) {
+  if (st->done) return;
+  ph_restrict_slab(L, r, z, rc, nxc, nyc, grid_walk(), g);
+}
+
+// ---- what the sums need around the collectives ---------------------------------------------------------------------------------------------
+// out[0] = the `count` partials of the previous kernel in index order
+__global__ __launch_bounds__(kBlock) void mg_slab_collapse(const double* part, int count, double* out, const MgState* st) {
+  if (st && st->done) return;
+  __shared__ double smem[16];
+  const double s = mg_sum_partials(part, count, smem);
+  if (threadIdx.x == 0) out[0] = s;
+}
+__global__ __launch_bounds__(kBlock) void mg_slab_collapse_max(const double* part, int count, double* out, const MgState* st) {
+  if (st->done) return;
+  __shared__ double smem[16];
+  double m = 0;
+  for (int b = threadIdx.x; b < count; b += blockDim.x) m = nanmax(m, part[b]);
+  m = mg_block_max_nan(m, smem);
+  if (threadIdx.x == 0) out[0] = m;
+}
+// the set-up partials of mg_setup0 as summable values g[4 .. 8] = sum|diag|, present cells, sum(b), the two pattern flags; g[9] = max|row sum|
+__global__ __launch_bounds__(kBlock) void mg_slab_setup_collapse(const double* parts, int count, const MgState* st, double* g) {
+  __shared__ double smem[16];
+  const double sd = mg_sum_partials(parts, count, smem), np = mg_sum_partials(parts + kMgGrid, count, smem);
+  const double sb = mg_sum_partials(parts + 2 * kMgGrid, count, smem);
+  double mr = 0;
+  for (int b = threadIdx.x; b < count; b += blockDim.x) mr = nanmax(mr, parts[3 * kMgGrid + b]);
+  mr = mg_block_max_nan(mr, smem);
+  if (threadIdx.x == 0) {
+    g[4] = sd; g[5] = np; g[6] = sb;
+    g[7] = (st->flags & MG_FLAG_BORDER) ? 1.0 : 0.0; g[8] = (st->flags & MG_FLAG_ZERO_DIAG_ROW) ? 1.0 : 0.0;
+    g[9] = mr;
+  }
+}
+// ... and back into the layout mg_setup_fin reads, as ONE partial per sum and the ranks' maxima: the same kernel finishes the set-up
+__global__ void mg_slab_setup_spread(const double* g, const double* gmax, int world, double* parts, MgState* st) {
+  if (threadIdx.x != 0) return;
+  for (int r = 0; r < world; ++r) {
+    parts[r] = r == 0 ? g[4] : 0.0; parts[kMgGrid + r] = r == 0 ? g[5] : 0.0; parts[2 * kMgGrid + r] = r == 0 ? g[6] : 0.0;
+    parts[3 * kMgGrid + r] = gmax[r];
+  }
+  st->flags |= (g[7] != 0 ? MG_FLAG_BORDER : 0) | (g[8] != 0 ? MG_FLAG_ZERO_DIAG_ROW : 0);
+}
+// zero the halo rows of up to 12 arrays (pointers at owned row 0 of n = nx * rows cells): where the grid ends no exchange writes them
+struct MgHalos { int count; double* a[12]; };
+__global__ __launch_bounds__(kBlock) void mg_slab_zero_halos(MgHalos h, int nx, int n) {
+  const Walk w = grid_walk();
+  for (int i = w.begin; i < nx; i += w.step)
+    for (int k = 0; k < h.count; ++k) { h.a[k][i - nx] = 0; h.a[k][n + i] = 0; }
+}
+// g = 0: the rank's rows of the replicated z with the rows below and above them (periodic wrap, or zero)
+__global__ __launch_bounds__(kBlock) void mg_slab_take_rows(const double* __restrict__ zfull, double* __restrict__ zloc, int nx, int rows, int row0, int nyg, int per_y,
+                                                            const MgState* st) {
+  if (st->done) return;
+  const Walk w = grid_walk();
+  for (int k = w.begin; k < (rows + 2) * nx; k += w.step) {
+    const int jl = k / nx - 1, i = k - (jl + 1) * nx;
+    int jg = row0 + jl;
+    const bool wrapped = jg < 0 || jg >= nyg;
+    if (wrapped) jg = jg < 0 ? jg + nyg : jg - nyg;
+    zloc[jl * nx + i] = (wrapped && !per_y) ? 0.0 : zfull[(size_t)jg * nx + i];
+  }
+}
+__global__ __launch_bounds__(kBlock) void mg_slab_dot(const double* __restrict__ a, const double* __restrict__ b, int n, double* part, const MgState* st) {
+  if (st->done) return;
+  __shared__ double smem[16];
+  double acc = 0;
+  const Walk w = grid_walk();
+  for (int c = w.begin; c < n; c += w.step) acc += a[c] * b[c];
+  acc = mg_block_sum(acc, smem);
+  if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+// loopback all-reduce: the ranks' buffers lie kMgSlabG apart; sum in rank order, write to all
+__global__ void mg_loop_allreduce(double* base, int world, int count) {
+  const int q = threadIdx.x;
+  if (q >= count) return;
+  double s = 0;
+  for (int r = 0; r < world; ++r) s += base[(size_t)r * kMgSlabG + q];
+  for (int r = 0; r < world; ++r) base[(size_t)r * kMgSlabG + q] = s;
+}
+
+// ---- the link: exchange the halo rows of one array, all-reduce, all-gather -----------------------------------------------------------------
+struct MgLink {
+  PisoComm* pc;              // NULL: loopback over the virtual ranks of R
+  int world;
+  bool periodic_y;
+  hipStream_t s;
+
+  // sel(rank) -> owned row 0 of an array of `rows` rows of nx cells with halo rows
+  template <typename Sel>
+  int exchange(std::vector<MgSlabRank>& R, Sel sel, int nx, int rows, bool ring = false) {
+    const bool per = periodic_y || ring;
+    if (pc) return comm_exchange_rows(pc, per, sel(R[0]), nx, rows, s);
+    for (int r = 0; r < world; ++r) {
+      const int lo = r > 0 ? r - 1 : (per ? world - 1 : -1), hi = r < world - 1 ? r + 1 : (per ? 0 : -1);
+      double* row0 = sel(R[r]);
+      const size_t bytes = (size_t)nx * sizeof(double);
+      if (lo >= 0) PISO_HIP_CHECK(hipMemcpyAsync(row0 - nx, sel(R[lo]) + (size_t)(rows - 1) * nx, bytes, hipMemcpyDeviceToDevice, s));
+      if (hi >= 0) PISO_HIP_CHECK(hipMemcpyAsync(row0 + (size_t)rows * nx, sel(R[hi]), bytes, hipMemcpyDeviceToDevice, s));
+    }
+    return PISO_OK;
+  }
+  int allreduce(std::vector<MgSlabRank>& R, int off, int count) {
+    if (pc) return comm_allreduce_f64(pc, R[0].g + off, count, s);
+    if (world > 1) mg_loop_allreduce<<<1, 64, 0, s>>>(R[0].g + off, world, count);
+    return PISO_OK;
+  }
+  template <typename Src, typename Dst>
+  int allgather(std::vector<MgSlabRank>& R, Src src, Dst dst, size_t count) {
+    if (pc) return comm_allgather_f64(pc, src(R[0]), dst(R[0]), count, s);
+    for (int q = 0; q < world; ++q)
+      for (int r = 0; r < world; ++r)
+        PISO_HIP_CHECK(hipMemcpyAsync(dst(R[q]) + (size_t)r * count, src(R[r]), count * sizeof(double), hipMemcpyDeviceToDevice, s));
+    return PISO_OK;
+  }
+};
+
+// ---- workspace ------------------------------------------------------------------------------------------------------------------------------
+// one rank's share (the same walk sizes it against an arena without memory)
+static bool mg_slab_carve(const MgSlabPlan& sp, int per_x, int per_y, Arena& ar, MgSlabRank& k) {
+  const MgDims& d = sp.d;
+  for (int l = 0; l < d.nlev; ++l) {
+    Lv& L = k.lv[l];
+    const bool sharded = l < sp.g;
+    L.nx = d.nx[l]; L.ny = sp.rows[l]; L.n = L.nx * L.ny; L.per_x = per_x; L.per_y = per_y;
+    const size_t cells = sharded ? (size_t)L.n + 2 * L.nx : (size_t)L.n, off = sharded ? L.nx : 0;
+    for (int s = 0; s < 5; ++s) L.c[s] = ar.take<double>(cells) + off;
+    L.dinv = ar.take<double>(cells) + off;
+    k.r[l] = ar.take<double>(cells) + off; k.z[l] = ar.take<double>(cells) + off; k.t[l] = ar.take<double>(cells) + off;
+  }
+  const int nxg = d.nx[sp.g], rows_g = d.ny[sp.g] / sp.world;      // (ny_g = ny >> g exactly: nyl % 2^g == 0)
+  k.chunk.nx = nxg; k.chunk.ny = rows_g; k.chunk.n = nxg * rows_g; k.chunk.per_x = per_x; k.chunk.per_y = per_y;
+  for (int s = 0; s < 5; ++s) k.chunk.c[s] = ar.take<double>(k.chunk.n);
+  k.chunk.dinv = ar.take<double>(k.chunk.n);
+  k.rchunk = ar.take<double>(k.chunk.n);
+  const int nx = d.nx[0];
+  const size_t n0 = (size_t)nx * sp.nyl, nh0 = n0 + 2 * nx;
+  if (sp.g > 0) { k.ro = k.r[0]; k.zo = nullptr; }
+  else { k.ro = ar.take<double>(nh0) + nx; k.zo = ar.take<double>(nh0) + nx; }
+  k.p[0] = ar.take<double>(nh0) + nx; k.p[1] = ar.take<double>(nh0) + nx; k.x = ar.take<double>(nh0) + nx;
+  k.q = ar.take<double>(n0);
+  k.parts = ar.take<double>(4 * kMgGrid);
+  k.part_rz = ar.take<double>(kMgGrid); k.part_pq = ar.take<double>(kMgGrid); k.part_max = ar.take<double>(kMgGrid);
+  k.scal = ar.take<double>(SC_COUNT_MG);
+  k.gmax = ar.take<double>(kMaxRanks);
+  k.st = ar.take<MgState>(1);
+  return ar.ok();
+}
+static size_t mg_slab_rank_bytes(const MgSlabPlan& sp) {
+  Arena ar(reinterpret_cast<void*>(256), ~(size_t)0);
+  MgSlabRank k;
+  mg_slab_carve(sp, 0, 0, ar, k);
+  return align_up(ar.used, 256);
+}
+static size_t mg_slab_g_bytes(int local_ranks) { return align_up((size_t)local_ranks * kMgSlabG * sizeof(double), 256); }
+
+// ---- the driver ------------------------------------------------------------------------------------------------------------------------------
+struct MgSlab {
+  std::vector<MgSlabRank> R;
+  MgLink link;
+  MgSlabPlan sp;
+  int per_x, per_y;
+  hipStream_t s;
+  bool use_tail;
+
+  int nloc() const { return (int)R.size(); }
+  GeoSlab geo(const MgSlabRank& k, int l) const {
+    GeoSlab g;
+    g.row0 = k.rank * (l == 0 ? sp.nyl : sp.rows[l]); g.nyg = sp.d.ny[l]; g.coarse_global = (l + 1 >= sp.g) ? 1 : 0; g.dg = nullptr; g.ncells = (double)sp.d.nx[0] * sp.d.ny[0];
+    return g;
+  }
+  // the view mg_cycle takes of a rank's replicated levels
+  MgPlan rep(const MgSlabRank& k) const {
+    MgPlan P;
+    P.nlev = sp.d.nlev; P.tail_first = sp.tail_first;
+    for (int l = 0; l < P.nlev; ++l) { P.lv[l] = k.lv[l]; P.r[l] = k.r[l]; P.z[l] = k.z[l]; P.t[l] = k.t[l]; }
+    P.part_rz = k.part_rz; P.st = k.st;
+    return P;
+  }
+
+  // carve `ws` (the g buffers of all local ranks first, contiguous: the loopback all-reduce walks them)
+  int carve(const char* who, void* ws, size_t bytes) {
+    const size_t per_rank = mg_slab_rank_bytes(sp), gb = mg_slab_g_bytes(nloc());
+    char msg[96];
+    if (bytes < gb + per_rank * nloc()) { snprintf(msg, sizeof(msg), "%s: workspace too small", who); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
+    PISO_HIP_CHECK(hipMemsetAsync(ws, 0, gb, s));
+    for (int q = 0; q < nloc(); ++q) {
+      Arena ar(static_cast<char*>(ws) + gb + (size_t)q * per_rank, per_rank);
+      R[q].g = static_cast<double*>(ws) + (size_t)q * kMgSlabG;
+      if (!mg_slab_carve(sp, per_x, per_y, ar, R[q])) { snprintf(msg, sizeof(msg), "%s: workspace too small", who); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
+    }
+    return PISO_OK;
+  }
+
+  // every level from the ranks' rows of the caller's matrix; the same refusals as mg_build, decided on all-reduced flags
+  int build(int rank_deficient) {
+    MgState* pinned = nullptr;
+    PISO_TRY(mg_pinned(&pinned));
+    const int nx = sp.d.nx[0], n0 = nx * sp.nyl, g0 = mg_grid(n0);
+    for (MgSlabRank& k : R) {
+      PISO_HIP_CHECK(hipMemsetAsync(k.st, 0, sizeof(MgState), s));
+      for (int l = 0; l < sp.g; ++l) {
+        MgHalos h{9, {k.lv[l].c[0], k.lv[l].c[1], k.lv[l].c[2], k.lv[l].c[3], k.lv[l].c[4], k.lv[l].dinv, k.r[l], k.z[l], k.t[l]}};
+        mg_slab_zero_halos<<<grid_for(k.lv[l].nx, kBlock, 64), kBlock, 0, s>>>(h, k.lv[l].nx, k.lv[l].n);
+      }
+      MgHalos h{3, {k.p[0], k.p[1], k.x}};
+      if (sp.g == 0) { h.a[3] = k.ro; h.a[4] = k.zo; h.count = 5; }
+      mg_slab_zero_halos<<<grid_for(nx, kBlock, 64), kBlock, 0, s>>>(h, nx, n0);
+      mg_slab_diag<<<g0, kBlock, 0, s>>>(k.Lin, k.p[0], n0);          // (p[0] is free until the first direction)
+    }
+    // (around the ring whatever the border: the whole-grid set-up looks at the wrapped row's diagonal there too)
+    PISO_TRY(link.exchange(R, [](MgSlabRank& k) { return k.p[0]; }, nx, sp.nyl, true));
+    for (MgSlabRank& k : R) {
+      GeoSlab g = geo(k, 0);
+      g.dg = k.p[0];
+      Lv L0 = sp.g > 0 ? k.lv[0] : k.chunk;
+      mg_setup0_slab<<<g0, kBlock, 0, s>>>(k.Lin, L0, k.b, k.parts, k.st, g);
+      mg_slab_setup_collapse<<<1, kBlock, 0, s>>>(k.parts, g0, k.st, k.g);
+    }
+    PISO_TRY(link.allreduce(R, 4, 5));
+    PISO_TRY(link.allgather(R, [](MgSlabRank& k) { return k.g + 9; }, [](MgSlabRank& k) { return k.gmax; }, 1));
+    for (MgSlabRank& k : R) {
+      mg_slab_setup_spread<<<1, 64, 0, s>>>(k.g, k.gmax, sp.world, k.parts, k.st);
+      mg_setup_fin<<<1, kBlock, 0, s>>>(k.parts, sp.world, k.scal, rank_deficient, n0 * sp.world, k.st);
+      MgHalos h{2, {k.p[0], k.p[1]}};                                 // (the diagonals' halo rows: p must start from zero ones)
+      mg_slab_zero_halos<<<grid_for(nx, kBlock, 64), kBlock, 0, s>>>(h, nx, n0);
+    }
+    // the sharded levels: halo rows of the diagonal (coarsening reads the neighbours' presence) and of dinv, once per solve
+    for (int l = 0; l < sp.g; ++l) {
+      PISO_TRY(link.exchange(R, [l](MgSlabRank& k) { return k.lv[l].c[2]; }, sp.d.nx[l], sp.rows[l]));
+      PISO_TRY(link.exchange(R, [l](MgSlabRank& k) { return k.lv[l].dinv; }, sp.d.nx[l], sp.rows[l]));
+      for (MgSlabRank& k : R) {
+        const Lv& Cc = l + 1 < sp.g ? k.lv[l + 1] : k.chunk;
+        mg_coarsen_slab<<<mg_grid(Cc.n), kBlock, 0, s>>>(k.lv[l], Cc, geo(k, l));
+      }
+    }
+    // level g: the ranks' rows, all-gathered
+    for (int a = 0; a < 6; ++a)
+      PISO_TRY(link.allgather(R, [a](MgSlabRank& k) { return a < 5 ? k.chunk.c[a] : k.chunk.dinv; },
+                              [a, this](MgSlabRank& k) { return a < 5 ? k.lv[sp.g].c[a] : k.lv[sp.g].dinv; }, (size_t)R[0].chunk.n));
+    for (MgSlabRank& k : R)
+      for (int l = sp.g; l + 1 < sp.d.nlev; ++l) mg_coarsen<<<mg_grid(k.lv[l + 1].n), kBlock, 0, s>>>(k.lv[l], k.lv[l + 1]);
+    PISO_LAUNCH_CHECK();
+    PISO_HIP_CHECK(hipMemcpyAsync(pinned, R[0].st, sizeof(MgState), hipMemcpyDeviceToHost, s));
+    PISO_HIP_CHECK(hipStreamSynchronize(s));
+    if (pinned->flags & MG_FLAG_BORDER) {
+      set_error_msg("piso_mg: non-zero border entry in a non-periodic direction (the reference stencil reads the neighbouring row there); use the plain CG");
+      return PISO_ERR_UNSUPPORTED_PATTERN;
+    }
+    if (pinned->flags & MG_FLAG_ZERO_DIAG_ROW) {
+      set_error_msg("piso_mg: a row with a zero diagonal has non-zero entries; use the plain CG");
+      return PISO_ERR_UNSUPPORTED_PATTERN;
+    }
+    if (pinned->flags & MG_FLAG_NOT_SINGULAR) {
+      set_error_msg("piso_mg: rank_deficient = 1 but the rows of the matrix do not sum to zero; use the plain CG");
+      return PISO_ERR_UNSUPPORTED_PATTERN;
+    }
+    return PISO_OK;
+  }
+
+  // halo rows of array `sel` of sharded level l
+  template <typename Sel>
+  int halo(int l, Sel sel) { return link.exchange(R, sel, sp.d.nx[l], sp.rows[l]); }
+
+  // z = M^-1 r on every rank's rows: leaves R[q].z_top (halo rows filled) and the rank's part of (r, z) in g[0]
+  int cycle(int nu) {
+    const int G = sp.g, nx = sp.d.nx[0], n0 = nx * sp.nyl;
+    std::vector<std::vector<double*>> zc(nloc(), std::vector<double*>(kMgMaxLevels, nullptr));
+    auto rl = [](MgSlabRank& k, int l) { return l == 0 ? k.ro : k.r[l]; };
+    for (int l = 0; l < G; ++l) {                                       // down the sharded levels
+      const int gl = mg_grid(R[0].lv[l].n);
+      if (nu >= 2) PISO_TRY(halo(l, [&](MgSlabRank& k) { return rl(k, l); }));
+      for (int q = 0; q < nloc(); ++q) {
+        MgSlabRank& k = R[q];
+        zc[q][l] = k.z[l];
+        if (nu >= 2) mg_pre2_slab<<<gl, kBlock, 0, s>>>(k.lv[l], rl(k, l), k.z[l], k.st, geo(k, l));
+        else mg_pre1<<<gl, kBlock, 0, s>>>(k.lv[l], rl(k, l), k.z[l], k.st);
+      }
+      for (int sw = 2; sw < nu; ++sw) {
+        PISO_TRY(halo(l, [&](MgSlabRank& k) { return zc[&k - R.data()][l]; }));
+        for (int q = 0; q < nloc(); ++q) {
+          MgSlabRank& k = R[q];
+          double* nxt = zc[q][l] == k.z[l] ? k.t[l] : k.z[l];
+          mg_jacobi_slab<<<gl, kBlock, 0, s>>>(k.lv[l], rl(k, l), zc[q][l], nxt, nullptr, 0, nullptr, k.st, geo(k, l));
+          zc[q][l] = nxt;
+        }
+      }
+      PISO_TRY(halo(l, [&](MgSlabRank& k) { return zc[&k - R.data()][l]; }));
+      for (int q = 0; q < nloc(); ++q) {
+        MgSlabRank& k = R[q];
+        const Lv& Cc = l + 1 < G ? k.lv[l + 1] : k.chunk;
+        mg_restrict_slab<<<mg_grid(Cc.n), kBlock, 0, s>>>(k.lv[l], rl(k, l), zc[q][l], l + 1 < G ? k.r[l + 1] : k.rchunk, Cc.nx, Cc.ny, k.st, geo(k, l));
+      }
+    }
+    // level g: the ranks' rows of the residual, all-gathered; levels g .. coarsest on every rank, as the one-GPU plan runs them
+    PISO_TRY(link.allgather(R, [G](MgSlabRank& k) { return G > 0 ? k.rchunk : k.ro; }, [G](MgSlabRank& k) { return k.r[G]; }, (size_t)R[0].chunk.n));
+    std::vector<double*> zg(nloc());
+    for (int q = 0; q < nloc(); ++q) {
+      int n_rz = 0;
+      zg[q] = mg_cycle(rep(R[q]), R[q].r[G], nu, use_tail, &n_rz, s, G);
+    }
+    int n_rz = 0;
+    if (G == 0) {
+      n_rz = mg_grid(n0);
+      for (int q = 0; q < nloc(); ++q) {
+        MgSlabRank& k = R[q];
+        mg_slab_take_rows<<<mg_grid(n0 + 2 * nx), kBlock, 0, s>>>(zg[q], k.zo, nx, sp.nyl, k.rank * sp.nyl, sp.d.ny[0], per_y, k.st);
+        mg_slab_dot<<<n_rz, kBlock, 0, s>>>(k.ro, k.zo, n0, k.part_rz, k.st);
+        k.z_top = k.zo;
+      }
+    }
+    for (int l = G - 1; l >= 0; --l) {                                  // up the sharded levels
+      const int gl = mg_grid(R[0].lv[l].n);
+      if (l + 1 < G) PISO_TRY(halo(l + 1, [&](MgSlabRank& k) { return zc[&k - R.data()][l + 1]; }));      // e of a sharded coarser level
+      for (int sw = 0; sw < nu; ++sw) {
+        if (sw > 0) PISO_TRY(halo(l, [&](MgSlabRank& k) { return zc[&k - R.data()][l]; }));               // (sweep 0: filled before the restriction)
+        for (int q = 0; q < nloc(); ++q) {
+          MgSlabRank& k = R[q];
+          double* nxt = zc[q][l] == k.z[l] ? k.t[l] : k.z[l];
+          const double* e = sw == 0 ? (l + 1 < G ? zc[q][l + 1] : zg[q]) : nullptr;
+          mg_jacobi_slab<<<gl, kBlock, 0, s>>>(k.lv[l], rl(k, l), zc[q][l], nxt, e, sp.d.nx[l + 1], (l == 0 && sw == nu - 1) ? k.part_rz : nullptr, k.st, geo(k, l));
+          zc[q][l] = nxt;
+        }
+      }
+      if (l == 0) {
+        n_rz = gl;
+        PISO_TRY(halo(0, [&](MgSlabRank& k) { return zc[&k - R.data()][0]; }));                           // for the direction
+        for (int q = 0; q < nloc(); ++q) R[q].z_top = zc[q][0];
+      }
+    }
+    for (MgSlabRank& k : R) mg_slab_collapse<<<1, kBlock, 0, s>>>(k.part_rz, n_rz, k.g, k.st);
+    PISO_LAUNCH_CHECK();
+    return PISO_OK;
+  }
+
+  int solve(float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps, int* iterations_out) {
+    PISO_TRY(build(rank_deficient));
+    MgState* pinned = nullptr;
+    PISO_TRY(mg_pinned(&pinned));
+    const int nx = sp.d.nx[0], n0 = nx * sp.nyl, g0 = mg_grid(n0);
+    const int check_every = opt(OPT_MG_CHECK_EVERY) > 0 ? opt(OPT_MG_CHECK_EVERY) : kCheckEvery;
+    auto L0 = [&](MgSlabRank& k) { Lv L = sp.g > 0 ? k.lv[0] : k.chunk; L.nx = nx; L.ny = sp.nyl; L.n = n0; return L; };    // (g = 0: the chunk IS the rank's rows of level 0)
+    for (MgSlabRank& k : R) mg_init<<<g0, kBlock, 0, s>>>(L0(k), k.b, k.x, k.ro, k.scal);
+    bool done = false;
+    int iterations = max_iterations;
+    for (int it = 0; it < max_iterations && !done; ++it) {
+      const bool restart = it > 0 && (it + 1) % residual_reset == 0;
+      if (restart) {
+        PISO_TRY(link.exchange(R, [](MgSlabRank& k) { return k.x; }, nx, sp.nyl));
+        for (MgSlabRank& k : R) mg_residual_slab<<<g0, kBlock, 0, s>>>(L0(k), k.b, k.x, k.ro, k.scal, k.st, geo(k, 0));
+      }
+      PISO_TRY(cycle(sweeps));
+      PISO_TRY(link.allreduce(R, 0, 1));
+      for (MgSlabRank& k : R)
+        mg_direction_slab<<<g0, kBlock, 0, s>>>(L0(k), k.z_top, k.p[it & 1], k.p[(it + 1) & 1], k.q, k.g, 1, k.scal, it, (restart || it == 0) ? 1 : 0, k.part_pq, k.st, geo(k, 0));
+      for (MgSlabRank& k : R) mg_slab_collapse<<<1, kBlock, 0, s>>>(k.part_pq, g0, k.g + 1, k.st);
+      PISO_TRY(link.allreduce(R, 1, 1));
+      for (MgSlabRank& k : R) {
+        mg_update<<<g0, kBlock, 0, s>>>(n0, k.x, k.ro, k.p[(it + 1) & 1], k.q, k.scal, it, k.g + 1, 1, k.part_max, k.st);
+        mg_slab_collapse_max<<<1, kBlock, 0, s>>>(k.part_max, g0, k.g + 2, k.st);
+      }
+      PISO_TRY(link.allgather(R, [](MgSlabRank& k) { return k.g + 2; }, [](MgSlabRank& k) { return k.gmax; }, 1));
+      for (MgSlabRank& k : R) mg_check<<<1, kBlock, 0, s>>>(k.gmax, sp.world, accuracy, it + 1, k.st);
+      PISO_LAUNCH_CHECK();
+      if ((it + 1) % check_every == 0 || it + 1 == max_iterations) {
+        PISO_HIP_CHECK(hipMemcpyAsync(pinned, R[0].st, sizeof(MgState), hipMemcpyDeviceToHost, s));
+        PISO_HIP_CHECK(hipStreamSynchronize(s));
+        if (pinned->done) { done = true; iterations = pinned->iterations; }
+      }
+    }
+    if (rank_deficient) {
+      for (MgSlabRank& k : R) {
+        mg_sum_x<<<g0, kBlock, 0, s>>>(L0(k), k.x, k.parts);
+        mg_slab_collapse<<<1, kBlock, 0, s>>>(k.parts, g0, k.g + 3, nullptr);
+      }
+      PISO_TRY(link.allreduce(R, 3, 1));
+      for (MgSlabRank& k : R) mg_finish_slab<<<g0, kBlock, 0, s>>>(L0(k), k.x, k.g + 3, 1, k.scal, geo(k, 0));
+      PISO_LAUNCH_CHECK();
+    }
+    if (iterations_out) *iterations_out = iterations;
+    int recomputed = 0;
+    for (int k = 1; k < iterations; ++k) recomputed += (k + 1) % residual_reset == 0;
+    record(sweeps, iterations, iterations, recomputed);
+    return PISO_OK;
+  }
+
+  void record(int sweeps, int iterations, int cycles, int recomputed) const {
+    int* d = tl_mg_dispatch;
+    d[MD_LEVELS] = sp.d.nlev; d[MD_TAIL_FIRST] = use_tail ? sp.tail_first : -1; d[MD_SWEEPS] = sweeps; d[MD_ITERATIONS] = iterations;
+    d[MD_CYCLES] = cycles; d[MD_RESIDUAL_RECOMPUTATIONS] = recomputed;
+    tl_mg_dispatch_n = MD_COUNT;
+  }
+
+  // copy rank-local results out and make every rank return the same status
+  int finish(const char* who) {
+    PISO_LAUNCH_CHECK();
+    if (link.pc) return comm_agree(link.pc, who, s, opt(OPT_SLAB_FORCE) > 0);
+    PISO_HIP_CHECK(hipStreamSynchronize(s));
+    return PISO_OK;
+  }
+};
+
+// the plan of a call: refusals are the plan's, with its message
+static int mg_slab_begin(MgSlab& M, const char* who, int nx, int nyl, int world, int local_ranks, int per_x, int per_y, int sweeps, PisoComm* pc, hipStream_t s) {
+  char msg[320];
+  if (sweeps < 1 || sweeps > 8) { snprintf(msg, sizeof(msg), "%s: sweeps must be 1 .. 8", who); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
+  if (nyl < 1 || world < 1 || world > kMaxRanks) { snprintf(msg, sizeof(msg), "%s: needs 1 .. %d ranks with at least one row each", who, kMaxRanks); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
+  M.sp = mg_slab_plan(nx, nyl * world, world, opt(OPT_MG_SLAB_GATHER_CELLS));
+  if (M.sp.status) { snprintf(msg, sizeof(msg), "%s: %s", who, M.sp.msg); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
+  M.per_x = per_x ? 1 : 0; M.per_y = per_y ? 1 : 0; M.s = s;
+  M.link = MgLink{pc, world, per_y != 0, s};
+  M.use_tail = M.sp.tail_first >= 0 && opt(OPT_MG_TAIL) != 0;
+  M.R.resize(local_ranks);
+  return PISO_OK;
+}
+
+}  // namespace piso

@@ -36,6 +36,7 @@ enum Opt {
   OPT_SLAB_HOP_TICKS,      // measurements only: the persistent slab kernel's cross-GPU records leave this many 10 ns ticks late (an emulated link latency)
   OPT_MG_TAIL,             // 0: the multigrid cycle (mg.hip) runs its coarse levels as launches of their own instead of inside one workgroup (the same arithmetic per cell)
   OPT_MG_CHECK_EVERY,      // multigrid PCG: iterations queued between two host looks (default 4; result and count do not depend on it)
+  OPT_MG_SLAB_GATHER_CELLS, // slab multigrid: the gather limit where positive and below kGatherCells = 8192 (mg_slab_plan.h); it moves the first replicated level, which tests use to shard levels of small grids.  A different limit is a different plan: sums are grouped by other ranks' rows (round-off only)
   OPT_COUNT
 };
 

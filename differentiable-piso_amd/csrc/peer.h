@@ -13,6 +13,7 @@
 //     peer (it needs that peer's contribution to finish the current one), so two slots suffice.
 // All accesses to a mailbox are system-scope atomics (sc0 sc1): they bypass the non-coherent cache levels on both sides.
 #pragma once
+#include "mg_slab_plan.h"
 #include "piso_common.h"
 
 namespace piso {
@@ -38,7 +39,12 @@ struct PeerLayout {
   // side 0: the row BELOW my slab (written by my lower neighbour), side 1: the row ABOVE it (written by my upper neighbour)
   static constexpr size_t ex_row(int parity, int side, size_t row_cap) { return kRows + ((size_t)parity * 2 + side) * row_cap * 8; }   // host-level halo exchange
   static constexpr size_t z_row(int parity, int side, size_t row_cap) { return kRows + (4 + (size_t)parity * 2 + side) * row_cap * 8; }   // persistent kernel: z' halo rows
-  static size_t bytes(size_t row_cap) { return align_up(kRows + 8 * row_cap * 8, 4096); }
+  // the all-gather's area, APPENDED behind everything above (no earlier offset moves): two parities of kGatherCells doubles, each
+  // double as two tagged words {32 payload bits | 32-bit epoch} - a word that carries the expected epoch is complete by itself, so
+  // there is no flag.  Source r's chunk of `count` doubles starts at word 2 r count of the parity's half.
+  static size_t gather_area(size_t row_cap) { return align_up(kRows + 8 * row_cap * 8, 4096); }
+  static constexpr size_t kGatherParityBytes = (size_t)kGatherCells * 2 * 8;
+  static size_t bytes(size_t row_cap) { return gather_area(row_cap) + 2 * kGatherParityBytes; }
 };
 
 // what a kernel needs to talk to the other ranks (passed by value)

@@ -22,6 +22,7 @@ struct PisoComm {
   size_t vmm_bytes = 0;
   unsigned seq_pp = 0;                // ping-pong tags (piso_comm_pingpong)
   unsigned seq_ar = 0, seq_ex = 0;    // sequence numbers of the host-level collectives (advance identically on every rank)
+  unsigned seq_ga = 0;                // epochs of the peer all-gather: a sequence of its own, so two consecutive gathers never share a slot
   unsigned launches = 0;              // persistent slab launches so far: the high half of their exchange tags
   int* err = nullptr;                 // device flag: a wait on a peer gave up
   int persist_fallbacks = 0;          // solves restarted on the two-kernel iteration after a persistent segment failed
@@ -40,7 +41,10 @@ inline PeerView make_view(const PisoComm* pc, bool periodic_y) {
 }
 
 // The host collectives (comm.hip): each is the only place that chooses a transport for its job, and queues it on stream `s`.
-//   * in-place sum of `count` doubles over the ranks (one rank: nothing); of ints, and the all-gather of doubles: RCCL only;
+//   * in-place sum of `count` doubles over the ranks (one rank: nothing); of ints: RCCL only;
+//   * the all-gather of `count` doubles per rank, in rank order.  Peer transport: count * world <= kGatherCells, every rank writes its
+//     chunk as tagged words into every rank's gather area (its own included), polls its own and copies out; one rank: a copy, unless
+//     the option slab_force sends it through the mailbox;
 //   * the halo rows -1 and ny of a slab vector whose owned rows start at `row0` (nx doubles a row; neighbours by periodic_y);
 //   * the four halo messages of a globally indexed vector {to upper, to lower, from lower, from upper}, always around the ring.
 //     RCCL: grouped send / recv of the segments, straight from / into the vector (no staging).  Sends and receives between one pair

@@ -67,6 +67,22 @@ lib.piso_mg_vcycle_f64.argtypes = [_i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, 
 lib.piso_mg_vcycle_f64.restype = _i
 lib.piso_mg_level_f64.argtypes = [_i, _i, _i, _i, _vp, _i, _ip, _ip, _vp, _vp, _sz, _vp]
 lib.piso_mg_level_f64.restype = _i
+lib.piso_mg_slab_workspace_bytes.argtypes = [_i, _i, _i, _i]
+lib.piso_mg_slab_workspace_bytes.restype = _sz
+lib.piso_mg_slab_plan.argtypes = [_i, _i, _i, _i, _ip, _i]
+lib.piso_mg_slab_plan.restype = _i
+lib.piso_mg_pcg_solve_slab_f64.argtypes = [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i, _i, _i, _i, _ip, _vp, _sz, _vp]
+lib.piso_mg_pcg_solve_slab_f64.restype = _i
+lib.piso_mg_vcycle_slab_f64.argtypes = [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]
+lib.piso_mg_vcycle_slab_f64.restype = _i
+lib.piso_mg_level_slab_f64.argtypes = [_vp, _i, _i, _i, _i, _vp, _i, _ip, _ip, _vp, _vp, _sz, _vp]
+lib.piso_mg_level_slab_f64.restype = _i
+lib.piso_mg_pcg_solve_slab_emulated_f64.argtypes = [_i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i, _i, _i, _i, _ip, _vp, _sz, _vp]
+lib.piso_mg_pcg_solve_slab_emulated_f64.restype = _i
+lib.piso_mg_vcycle_slab_emulated_f64.argtypes = [_i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]
+lib.piso_mg_vcycle_slab_emulated_f64.restype = _i
+lib.piso_mg_level_slab_emulated_f64.argtypes = [_i, _i, _i, _i, _i, _i, _vp, _i, _ip, _ip, _vp, _vp, _sz, _vp]
+lib.piso_mg_level_slab_emulated_f64.restype = _i
 lib.piso_mg_last_dispatch.argtypes = [_ip, _i]
 lib.piso_mg_last_dispatch.restype = _i
 lib.piso_cg_fixed_iterations_f64.argtypes = [_i, _i, _i, _i, _vp, _vp, _vp, _i, _i, C.POINTER(C.c_float), _vp, _sz, _vp]
@@ -158,6 +174,8 @@ for _n in ("piso_multi_bicgstab_ilu_slab_local_f32", "piso_multi_bicgstab_ilu_sl
     getattr(lib, _n).restype = _i
 lib.piso_comm_exchange.argtypes = [_vp, _vp, _i, _ip, _vp]
 lib.piso_comm_exchange.restype = _i
+lib.piso_comm_allgather_f64.argtypes = [_vp, _vp, _vp, _i, _vp]
+lib.piso_comm_allgather_f64.restype = _i
 lib.piso_comm_check.argtypes = [_vp, _vp]
 lib.piso_comm_check.restype = _i
 lib.piso_cg_slab_workspace_bytes.argtypes = [_i, _i, _i]
@@ -277,6 +295,18 @@ def conv_last_dispatch():
 
 
 MG_DISPATCH_FIELDS = ("levels", "tail_first", "sweeps", "iterations", "cycles", "residual_recomputations")
+
+
+def mg_slab_plan(nx, ny, world, gather_cells=0):
+    """The pure plan of a slab multigrid solve (csrc/mg_slab_plan.h) as a dict: levels [(nx, ny)], g (first replicated level), tail_first,
+    rows (held per rank and level).  gather_cells 0: the option mg_slab_gather_cells / 8192.  A refused shape raises PisoNativeError."""
+    buf = (C.c_int * 64)()
+    n = lib.piso_mg_slab_plan(int(nx), int(ny), int(world), int(gather_cells), buf, 64)
+    if buf[0] != 0:
+        raise PisoNativeError("piso_mg_slab_plan refused %d x %d on %d ranks: %s" % (nx, ny, world, lib.piso_last_error_string().decode()))
+    lv = [(buf[6 + 3 * l], buf[7 + 3 * l]) for l in range(buf[1])]
+    assert n == 6 + 3 * buf[1]
+    return {"levels": lv, "g": buf[2], "tail_first": buf[3], "nyl": buf[4], "world": buf[5], "rows": [buf[8 + 3 * l] for l in range(buf[1])]}
 
 
 def mg_last_dispatch():

@@ -648,7 +648,11 @@ class PisoPressureSolverMultigrid(PisoPressureSolverCudaCustom):
     grids; the two solvers agree to the tolerance they are run at, not bit for bit, and `max_iterations` counts multigrid
     iterations here (a few dozen suffice).  Measured faster than the plain solver from 256 x 256 cells up (3x at 256^2, 25 - 77x at
     2048^2; DESIGN.md 3.7 has the table); not measured on smaller grids, where the plain solver's one-workgroup kernels have no
-    launch or host round trip per iteration and are the better choice.  fp64, one GPU: cast_to_double=False and a slab communicator are refused.
+    launch or host round trip per iteration and are the better choice.  fp64 only: cast_to_double=False is refused.
+    With a distributed.SlabCommunicator of more than one rank in `slab_comm` the solve is cut into y-slabs like the plain solver's (csrc/mg_slab.h:
+    fine levels sharded with halo rows, the levels of at most 8192 cells replicated; ny / ranks must be divisible by 2^g, g the first replicated
+    level, else the call is refused and names the plain solver); with `.sharded` L holds the rank's rows and the result stays on them.  Anything
+    else in `slab_comm` is refused.
     The fluid cells must be CONNECTED: a pocket of fluid enclosed by solid cells is not detected, and the solve then runs to `max_iterations`
     without converging (as the plain solver does).  Grids whose hierarchy stops after 0 or 1 coarsenings (a dimension below 8 or 16 cells
     next to a long one) are preconditioned poorly: ~200 iterations instead of tens.
@@ -667,11 +671,24 @@ class PisoPressureSolverMultigrid(PisoPressureSolverCudaCustom):
         self.smoothing_sweeps = int(smoothing_sweeps)
 
     def _cg(self, nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset):
-        if self.slab_comm is not None:
-            raise N.PisoNativeError("PisoPressureSolverMultigrid runs on one GPU: sharded / slab-decomposed solves need "
-                                    "PisoPressureSolverCudaCustom")
+        from .distributed import SlabCommunicator, mg_solve_slab, mg_solve_slab_local
+        if self.slab_comm is not None and not isinstance(self.slab_comm, SlabCommunicator):
+            raise N.PisoNativeError("PisoPressureSolverMultigrid cuts a solve into y-slabs over a distributed.SlabCommunicator only; anything else "
+                                    "in slab_comm is refused (one GPU: leave it None; other decompositions need PisoPressureSolverCudaCustom)")
         if not self.cast_to_double or L.dtype != torch.float64:
             raise N.PisoNativeError("PisoPressureSolverMultigrid is fp64 only; use PisoPressureSolverCudaCustom for float32")
+        # (option slab_force: a communicator of ONE rank still runs the slab solve - a ring of one, tests)
+        if self.slab_comm is not None and (self.slab_comm.world > 1 or N.get_option("slab_force") > 0):
+            if self.slab_comm.sharded:       # slab-decomposed STEP: L holds the rank's owned rows, div its stored rows; the result stays there
+                sh = self.slab_comm.step_sharding
+                d_loc = sh.owned_cells(div.reshape(-1).to(torch.float64)).reshape(-1).contiguous()
+                x_loc, it = mg_solve_slab_local(self.slab_comm, nx, sh.nyl, per_x, per_y, L, d_loc, accuracy, max_iterations, rank_deficient,
+                                                residual_reset, self.smoothing_sweeps)
+                x = torch.zeros(sh.n_cells, dtype=x_loc.dtype, device=x_loc.device)
+                sh.owned_cells(x).copy_(x_loc.view(sh.nyl, nx))
+                return x, it
+            return mg_solve_slab(self.slab_comm, nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset,
+                                 self.smoothing_sweeps)
         return mg_solve_native(nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset, self.smoothing_sweeps)
 
     @staticmethod

@@ -351,6 +351,37 @@ int piso_mg_vcycle_f64(int nx, int ny, int periodic_x, int periodic_y, const dou
                        int sweeps, void* workspace, size_t workspace_bytes, piso_stream_t stream);
 int piso_mg_level_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, int level, int* nx_out, int* ny_out,
                       double* laplace_level_out, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+/* The same solver on y-slabs (csrc/mg_slab.h, csrc/mg_slab_plan.h): every rank owns ny_local = ny / world contiguous rows and passes its
+ * rows of laplace / divergence / x, otherwise the arguments of piso_mg_pcg_solve_f64.  Levels 0 .. g - 1 are sharded (a rank's rows
+ * plus one halo row below and above), level g - the first of at most 8192 cells, or of at most "mg_slab_gather_cells" cells where that
+ * option is positive and smaller - and everything coarser is replicated: the ranks' rows of level g are all-gathered and every rank
+ * runs the coarse levels itself.  Refused with PISO_ERR_INVALID_ARG before any launch: ny_local not divisible by 2^g, no level within
+ * the limit (the message states the rule and names the plain solver), a workspace below piso_mg_slab_workspace_bytes(nx, ny_local,
+ * world, 1).  Halo rows, sums and gathers go through the communicator's collectives (either transport); every sum is formed from
+ * per-rank fixed-order partials, so every rank takes the same decisions, reports the same count and the same status.  Against the
+ * one-GPU solver the hierarchy and a cycle are bit for bit the same, a solve differs by the grouping of its dot products only.
+ * The *_emulated entries run `slabs` virtual ranks on one device over the full arrays (their rows are copied, no communicator): the test
+ * harness of every cut; their workspace is piso_mg_slab_workspace_bytes(nx, ny / slabs, slabs, slabs).
+ * piso_mg_level_slab_f64: a rank's rows of a sharded level, or the whole replicated level, as [nx_out * rows_out][5].
+ * piso_mg_slab_plan: the pure plan as a flat int record {status (0 accepted), levels, g, tail_first, rows per rank of level 0, ranks,
+ * then nx, ny, rows held per rank for every level}; gather_cells <= 0: the option / 8192; returns the number of fields (6 when refused,
+ * with the reason in piso_last_error_string). */
+size_t piso_mg_slab_workspace_bytes(int nx, int ny_local, int world, int local_ranks);
+int piso_mg_slab_plan(int nx, int ny, int world, int gather_cells, int* out, int capacity);
+int piso_mg_pcg_solve_slab_f64(void* comm, int nx, int ny_local, int periodic_x, int periodic_y, const double* laplace_local,
+                               const double* divergence_local, double* x_out_local, float accuracy, int max_iterations, int rank_deficient,
+                               int residual_reset, int sweeps, int* iterations_out, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+int piso_mg_vcycle_slab_f64(void* comm, int nx, int ny_local, int periodic_x, int periodic_y, const double* laplace_local, const double* r_local,
+                            double* z_local, int sweeps, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+int piso_mg_level_slab_f64(void* comm, int nx, int ny_local, int periodic_x, int periodic_y, const double* laplace_local, int level, int* nx_out,
+                           int* rows_out, double* laplace_level_out, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+int piso_mg_pcg_solve_slab_emulated_f64(int slabs, int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence,
+                                        double* x_out, float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps,
+                                        int* iterations_out, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+int piso_mg_vcycle_slab_emulated_f64(int slabs, int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* r_in, double* z_out,
+                                     int sweeps, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+int piso_mg_level_slab_emulated_f64(int slabs, int rank, int nx, int ny, int periodic_x, int periodic_y, const double* laplace, int level, int* nx_out,
+                                    int* rows_out, double* laplace_level_out, void* workspace, size_t workspace_bytes, piso_stream_t stream);
 /* What the calling thread's last piso_mg_pcg_solve_f64 / piso_mg_vcycle_f64 ran; returns the number of fields (6):
  *    0 levels         levels of the hierarchy
  *    1 tail_first     first level that ran inside the one-workgroup tail kernel (-1: none)
@@ -460,6 +491,10 @@ int piso_comm_stats(void* comm, long long* out6);
  * piso_comm_check: has a wait on a peer given up (agreed over the ranks; peer transport - RCCL has no bounded waits)? */
 int piso_comm_exchange(void* comm, void* vec, int dtype, const int* msgs28, piso_stream_t stream);
 int piso_comm_check(void* comm, piso_stream_t stream);
+/* All-gather of `count` doubles per rank, in rank order: dst holds count * world doubles on every rank (queued on the stream).  Peer
+ * transport: a host-launched mailbox kernel, count * world <= 8192 (more: PISO_ERR_INVALID_ARG); one rank copies, unless the option
+ * "slab_force" sends the chunk through its own mailbox.  The bits arrive unchanged (NaN payloads, -0.0, infinities). */
+int piso_comm_allgather_f64(void* comm, const void* src, void* dst, int count, piso_stream_t stream);
 /* Slab-decomposed ILU(0)-BiCGStab (either transport): same arguments as piso_multi_bicgstab_ilu_*, all arrays FULL on every rank
  * (the assembly is cheap and replicated); the rank works on the face rows of its ny / world cell rows, which must be whole
  * preconditioner bands (ny / world a multiple of the band height: then the banded ILU(0) is the single-GPU one and the iterates

@@ -7,7 +7,8 @@ labels) and prints a class per kernel:
   B  the opcode histogram and the resource notes (VGPRs, SGPRs, both spill counts, scratch, LDS, kernarg size) are identical:
      the same instructions in another order
   C  anything else, with the counts that differ
-Exit status: 0 if no kernel is of class C, 1 if one is, 2 if the two trees do not define the same kernels."""
+Exit status: 0 if no kernel is of class C, 1 if one is, 2 if the two trees do not define the same kernels (the kernels of both are
+still classified, and the resource notes of those only tree B has are listed)."""
 import collections, os, re, subprocess, sys, tempfile
 
 from isa_loop import mix
@@ -64,9 +65,10 @@ def main():
         if sorted(ka) != sorted(kb):
             print("%s: the kernel symbols differ: only in A %s, only in B %s" % (f, sorted(set(ka) - set(kb)), sorted(set(kb) - set(ka))))
             status = 2
-            continue
+            for name in sorted(set(kb) - set(ka)):         # what a new kernel takes: the resource notes of its metadata
+                print("new  %s  %s  %s" % (f, name, ", ".join("%s %d" % (k[1:], kb[name][1][k]) for k in NOTES)))
         count = collections.Counter()
-        for name in sorted(ka):
+        for name in sorted(set(ka) & set(kb)):             # (kernels of one tree only were listed above: the rest is still compared)
             (la, na), (lb, nb) = ka[name], kb[name]
             ha, hb = mix(la), mix(lb)
             cls = "A" if la == lb else ("B" if ha == hb and na == nb else "C")
@@ -78,7 +80,7 @@ def main():
                 status = max(status, 1)
                 print("     notes: " + (", ".join("%s %d -> %d" % (k[1:], na[k], nb[k]) for k in NOTES if na[k] != nb[k]) or "equal"))
                 print("     opcodes: " + (", ".join("%s %d -> %d" % (k, ha[k], hb[k]) for k in sorted(set(ha) | set(hb)) if ha[k] != hb[k]) or "equal"))
-        print("%s: %d kernels (%d cg_persist1), class A %d, B %d, C %d" % (f, len(ka), sum("cg_persist1" in k for k in ka), count["A"], count["B"], count["C"]))
+        print("%s: %d kernels (%d cg_persist1), class A %d, B %d, C %d" % (f, len(set(ka) & set(kb)), sum("cg_persist1" in k for k in ka), count["A"], count["B"], count["C"]))
     raise SystemExit(status)
 
 
