@@ -31,6 +31,8 @@
 // Reductions are two-stage, fixed order (per-block partials, re-added in index order): a solve is reproducible bit for bit.  alpha,
 // beta and the sums stay on the device; the host queues check_every iterations, then reads the state through a pinned word; kernels of
 // iterations queued after convergence see the device flag and return at once, so neither x nor the count depends on the cadence.
+//
+// Opt-in: the same iteration around a float32 cycle (mg_f32.h, piso_mg_*_c32_f64); this file's kernels are its fp64 outer iteration.
 #include <vector>
 
 #include "mg_slab_plan.h"
@@ -82,19 +84,30 @@ __device__ __forceinline__ Nb neighbours(int c, int i, int j, int nx, int ny) {
   q.n = j < ny - 1 ? c + nx : c - (ny - 1) * nx;
   return q;
 }
-// summation order of the reference stencil: S, W, C, E, N
-__device__ __forceinline__ double stencil(const Lv& L, int c, double vs, double vw, double vc, double ve, double vn) {
-  double t = L.c[0][c] * vs;
-  t += L.c[1][c] * vw;
-  t += L.c[2][c] * vc;
-  t += L.c[3][c] * ve;
-  t += L.c[4][c] * vn;
+// summation order of the reference stencil: S, W, C, E, N (T: double, or float in the float32 cycle of mg_f32.h)
+// `cf(s)` is the cell's coefficient s: read from the level's arrays (stencil), or from the registers of a four-cell thread (mg_f32.h)
+template <typename T, typename CF>
+__device__ __forceinline__ T stencil_sum(CF cf, T vs, T vw, T vc, T ve, T vn) {
+  T t = cf(0) * vs;
+  t += cf(1) * vw;
+  t += cf(2) * vc;
+  t += cf(3) * ve;
+  t += cf(4) * vn;
   return t;
 }
+template <typename LV, typename T>
+__device__ __forceinline__ T stencil(const LV& L, int c, T vs, T vw, T vc, T ve, T vn) {
+  return stencil_sum<T>([&](int s) { return L.c[s][c]; }, vs, vw, vc, ve, vn);
+}
+// what a cell becomes from its stencil sum `az`: the second of two sweeps from zero, a sweep, a term of the restricted residual
+template <typename T> __device__ __forceinline__ T pre2_out(T di, T rc, T z1, T az) { return z1 + di * (rc - az); }
+template <typename T> __device__ __forceinline__ T jac_out(T di, T rc, T vc, T az) { return vc + di * (rc - az); }
+template <typename T> __device__ __forceinline__ T restrict_term(T rc, T az) { return rc - az; }
 
 // ---- the per-cell passes, shared by the per-level kernels (grid_walk) and the one-workgroup tail (block_walk) -------------------------
 // first sweep from a zero guess
-__device__ __forceinline__ void ph_pre1(const Lv& L, const double* r, double* z, Walk w) {
+template <typename LV, typename T>
+__device__ __forceinline__ void ph_pre1(const LV& L, const T* r, T* z, Walk w) {
   for (int c = w.begin; c < L.n; c += w.step) z[c] = L.dinv[c] * r[c];
 }
 
@@ -128,6 +141,14 @@ __device__ __forceinline__ double mg_sum_partials(const double* part, int count,
 
 // ---- the per-cell code that looks at neighbours, for the whole grid (mg_cells.inc; mg_slab.h includes it again for a rank's slab) -----------
 #define MG_N(name) name
+#define MG_REAL double
+#define MG_LV Lv
+#define MG_RDOT_PARAM
+#define MG_RDOT_ARG(rd)
+#define MG_RDOT(rc, zo, c) rc * zo
+#define MG_R32_PARAM
+#define MG_R32_STORE(c, v)
+#define MG_WHOLE_GRID
 #define MG_GEO_PARAM
 #define MG_NB(c, i, j, nx, ny) neighbours(c, i, j, nx, ny)
 #define MG_JS(j, ny) j > 0 ? j - 1 : ny - 1
@@ -139,17 +160,7 @@ __device__ __forceinline__ double mg_sum_partials(const double* part, int count,
 #define MG_NCELLS(L) (double)L.n
 #define MG_DIRECTION_HALO_ROWS
 #include "mg_cells.inc"
-#undef MG_N
-#undef MG_GEO_PARAM
-#undef MG_NB
-#undef MG_JS
-#undef MG_JN
-#undef MG_EROW
-#undef MG_FIRST_ROW
-#undef MG_LAST_ROW
-#undef MG_DIAG
-#undef MG_NCELLS
-#undef MG_DIRECTION_HALO_ROWS
+#include "mg_cells_undef.inc"
 
 // ---- hierarchy ------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void mg_setup_fin(const double* parts, int count, double* scal, int rank_deficient, int ncells, MgState* st) {
@@ -167,94 +178,7 @@ __global__ __launch_bounds__(kBlock) void mg_setup_fin(const double* parts, int 
     (void)ncells;
   }
 }
-__global__ __launch_bounds__(kBlock) void mg_export(Lv L, double* __restrict__ out) {
-  const Walk w = grid_walk();
-  for (int c = w.begin; c < L.n; c += w.step)
-    for (int s = 0; s < 5; ++s) out[(size_t)c * 5 + s] = L.c[s][c];
-}
-
-// ---- per-level cycle kernels -----------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void mg_pre1(Lv L, const double* r, double* z, const MgState* st) {
-  if (st->done) return;
-  ph_pre1(L, r, z, grid_walk());
-}
-__global__ __launch_bounds__(kBlock) void mg_pre2(Lv L, const double* r, double* z, const MgState* st) {
-  if (st->done) return;
-  ph_pre2(L, r, z, grid_walk());
-}
-__global__ __launch_bounds__(kBlock) void mg_jacobi(Lv L, const double* r, const double* zin, double* zout, const double* e, int nxc, double* part_rz,
-                                                    const MgState* st) {
-  if (st->done) return;
-  __shared__ double smem[16];
-  double acc = ph_jac(L, r, zin, zout, e, nxc, grid_walk());
-  if (part_rz) {
-    acc = mg_block_sum(acc, smem);
-    if (threadIdx.x == 0) part_rz[blockIdx.x] = acc;
-  }
-}
-__global__ __launch_bounds__(kBlock) void mg_restrict(Lv L, const double* r, const double* z, double* rc, int nxc, int nyc, const MgState* st) {
-  if (st->done) return;
-  ph_restrict(L, r, z, rc, nxc, nyc, grid_walk());
-}
-
-// ---- the coarse tail: levels [0, nlev) of `T` inside one workgroup ----------------------------------------------------------------------
-struct MgTail {
-  int nlev;
-  Lv lv[kTailMaxLevels];
-  int off[kTailMaxLevels];
-};
-// nu sweeps from a zero guess into `dst` (scratch `tmp`)
-__device__ __forceinline__ void tail_first_sweeps(const Lv& L, const double* r, double* dst, double* tmp, int nu, Walk w) {
-  const int rest = nu >= 2 ? nu - 2 : 0;
-  double* cur = (rest & 1) ? tmp : dst;
-  if (nu >= 2) ph_pre2(L, r, cur, w); else ph_pre1(L, r, cur, w);
-  __syncthreads();
-  for (int s = 0; s < rest; ++s) {
-    double* nxt = cur == dst ? tmp : dst;
-    ph_jac(L, r, cur, nxt, nullptr, 0, w);
-    __syncthreads();
-    cur = nxt;
-  }
-}
-__global__ __launch_bounds__(kTailThreads) void mg_tail(MgTail T, const double* r_in, double* z_out, double* part_rz, int nu, const MgState* st) {
-  if (st->done) return;
-  __shared__ double rbuf[kTailLds], zbuf[kTailLds], tbuf[kTailCells];
-  __shared__ double smem[16];
-  const Walk w = block_walk();
-  for (int c = w.begin; c < T.lv[0].n; c += w.step) rbuf[c] = r_in[c];
-  __syncthreads();
-  const int last = T.nlev - 1;
-  for (int l = 0; l < last; ++l) {                                      // down
-    const Lv& L = T.lv[l];
-    tail_first_sweeps(L, rbuf + T.off[l], zbuf + T.off[l], tbuf, nu, w);
-    ph_restrict(L, rbuf + T.off[l], zbuf + T.off[l], rbuf + T.off[l + 1], T.lv[l + 1].nx, T.lv[l + 1].ny, w);
-    __syncthreads();
-  }
-  tail_first_sweeps(T.lv[last], rbuf + T.off[last], zbuf + T.off[last], tbuf, kCoarsestSweeps, w);
-  double acc = 0;
-  for (int l = last - 1; l >= 0; --l) {                                  // up
-    const Lv& L = T.lv[l];
-    double *cur = zbuf + T.off[l], *nxt = tbuf;
-    for (int s = 0; s < nu; ++s) {
-      acc = ph_jac(L, rbuf + T.off[l], cur, nxt, s == 0 ? zbuf + T.off[l + 1] : nullptr, T.lv[l + 1].nx, w);
-      __syncthreads();
-      double* t = cur; cur = nxt; nxt = t;
-    }
-    if (cur != zbuf + T.off[l]) {                                       // odd nu: the result sits in the scratch the next level needs
-      for (int c = w.begin; c < L.n; c += w.step) zbuf[T.off[l] + c] = tbuf[c];
-      __syncthreads();
-    }
-  }
-  if (last == 0) {                                                       // (a one-level tail: the sum was never formed)
-    acc = 0;
-    for (int c = w.begin; c < T.lv[0].n; c += w.step) acc += rbuf[c] * zbuf[c];
-  }
-  for (int c = w.begin; c < T.lv[0].n; c += w.step) z_out[c] = zbuf[c];
-  if (part_rz) {
-    acc = mg_block_sum(acc, smem);
-    if (threadIdx.x == 0) part_rz[0] = acc;
-  }
-}
+// (mg_export, the per-level cycle kernels mg_pre1 / mg_pre2 / mg_jacobi / mg_restrict and the one-workgroup tail mg_tail: mg_cells.inc, MG_WHOLE_GRID)
 
 // ---- outer iteration ------------------------------------------------------------------------------------------------------------------
 // r = b' on the present cells (b' = b - mean over the present cells where rank deficient), 0 elsewhere; x = 0
@@ -335,7 +259,7 @@ static bool mg_plan(int nx, int ny, int per_x, int per_y, Arena& ar, MgPlan& P) 
 static bool mg_dims_ok(int nx, int ny) { return nx >= kMinDim && ny >= kMinDim && (long long)nx * ny <= (1ll << 30); }
 
 // which shape the calling thread's last solve / cycle had (piso_mg_last_dispatch)
-enum { MD_LEVELS = 0, MD_TAIL_FIRST, MD_SWEEPS, MD_ITERATIONS, MD_CYCLES, MD_RESIDUAL_RECOMPUTATIONS, MD_COUNT };
+enum { MD_LEVELS = 0, MD_TAIL_FIRST, MD_SWEEPS, MD_ITERATIONS, MD_CYCLES, MD_RESIDUAL_RECOMPUTATIONS, MD_CYCLE_ELEM, MD_VEC_MASK, MD_COUNT };
 static thread_local int tl_mg_dispatch[MD_COUNT];
 static thread_local int tl_mg_dispatch_n = 0;
 
@@ -351,17 +275,19 @@ static int mg_pinned(MgState** out) {
   return PISO_OK;
 }
 
-// builds every level from the caller's matrix and refuses what the solver does not solve (one host look, as the plain CG's set-up has)
-static int mg_build(const MgPlan& P, const double* laplace, const double* b, int rank_deficient, hipStream_t stream) {
+// builds every level from the caller's matrix and refuses what the solver does not solve (one host look, as the plain CG's set-up has):
+// level 0 and the sums (begin), the coarser levels (the caller's), the look (end)
+static int mg_build_begin(const Lv& L0, const double* laplace, const double* b, int rank_deficient, double* parts, double* scal, MgState* st, hipStream_t stream) {
+  PISO_HIP_CHECK(hipMemsetAsync(st, 0, sizeof(MgState), stream));
+  const int g0 = mg_grid(L0.n);
+  mg_setup0<<<g0, kBlock, 0, stream>>>(laplace, L0, b, parts, st);
+  mg_setup_fin<<<1, kBlock, 0, stream>>>(parts, g0, scal, rank_deficient, L0.n, st);
+  return PISO_OK;
+}
+static int mg_build_end(const MgState* st, hipStream_t stream) {
   MgState* pinned = nullptr;
   if (int rc = mg_pinned(&pinned)) return rc;
-  PISO_HIP_CHECK(hipMemsetAsync(P.st, 0, sizeof(MgState), stream));
-  const int g0 = mg_grid(P.lv[0].n);
-  mg_setup0<<<g0, kBlock, 0, stream>>>(laplace, P.lv[0], b, P.parts, P.st);
-  mg_setup_fin<<<1, kBlock, 0, stream>>>(P.parts, g0, P.scal, rank_deficient, P.lv[0].n, P.st);
-  for (int l = 0; l + 1 < P.nlev; ++l) mg_coarsen<<<mg_grid(P.lv[l + 1].n), kBlock, 0, stream>>>(P.lv[l], P.lv[l + 1]);
-  PISO_LAUNCH_CHECK();
-  PISO_HIP_CHECK(hipMemcpyAsync(pinned, P.st, sizeof(MgState), hipMemcpyDeviceToHost, stream));
+  PISO_HIP_CHECK(hipMemcpyAsync(pinned, st, sizeof(MgState), hipMemcpyDeviceToHost, stream));
   PISO_HIP_CHECK(hipStreamSynchronize(stream));
   if (pinned->flags & MG_FLAG_BORDER) {
     set_error_msg("piso_mg: non-zero border entry in a non-periodic direction (the reference stencil reads the neighbouring row there); use the plain CG");
@@ -376,6 +302,12 @@ static int mg_build(const MgPlan& P, const double* laplace, const double* b, int
     return PISO_ERR_UNSUPPORTED_PATTERN;
   }
   return PISO_OK;
+}
+static int mg_build(const MgPlan& P, const double* laplace, const double* b, int rank_deficient, hipStream_t stream) {
+  PISO_TRY(mg_build_begin(P.lv[0], laplace, b, rank_deficient, P.parts, P.scal, P.st, stream));
+  for (int l = 0; l + 1 < P.nlev; ++l) mg_coarsen<<<mg_grid(P.lv[l + 1].n), kBlock, 0, stream>>>(P.lv[l], P.lv[l + 1]);
+  PISO_LAUNCH_CHECK();
+  return mg_build_end(P.st, stream);
 }
 
 // nu sweeps from a zero guess on level l; returns where the result is
@@ -446,6 +378,7 @@ static int mg_common_args(const char* who, int nx, int ny, const void* a, const 
 }  // namespace piso
 
 #include "mg_slab.h"
+#include "mg_f32.h"
 
 using namespace piso;
 
@@ -506,7 +439,7 @@ int piso_mg_pcg_solve_f64(int nx, int ny, int periodic_x, int periodic_y, const 
   for (int k = 1; k < iterations; ++k) recomputed += (k + 1) % residual_reset == 0;
   int* d = tl_mg_dispatch;
   d[MD_LEVELS] = P.nlev; d[MD_TAIL_FIRST] = use_tail ? P.tail_first : -1; d[MD_SWEEPS] = sweeps; d[MD_ITERATIONS] = iterations;
-  d[MD_CYCLES] = iterations; d[MD_RESIDUAL_RECOMPUTATIONS] = recomputed;
+  d[MD_CYCLES] = iterations; d[MD_RESIDUAL_RECOMPUTATIONS] = recomputed; d[MD_CYCLE_ELEM] = 8; d[MD_VEC_MASK] = 0;
   tl_mg_dispatch_n = MD_COUNT;
   return PISO_OK;
 }
@@ -528,7 +461,7 @@ int piso_mg_vcycle_f64(int nx, int ny, int periodic_x, int periodic_y, const dou
   PISO_HIP_CHECK(hipStreamSynchronize(stream));
   int* d = tl_mg_dispatch;
   d[MD_LEVELS] = P.nlev; d[MD_TAIL_FIRST] = use_tail ? P.tail_first : -1; d[MD_SWEEPS] = sweeps; d[MD_ITERATIONS] = 0; d[MD_CYCLES] = 1;
-  d[MD_RESIDUAL_RECOMPUTATIONS] = 0;
+  d[MD_RESIDUAL_RECOMPUTATIONS] = 0; d[MD_CYCLE_ELEM] = 8; d[MD_VEC_MASK] = 0;
   tl_mg_dispatch_n = MD_COUNT;
   return PISO_OK;
 }
@@ -546,6 +479,112 @@ int piso_mg_level_f64(int nx, int ny, int periodic_x, int periodic_y, const doub
   if (!laplace_level_out) return PISO_OK;                     // (sizes only)
   if (int rc = mg_build(P, laplace, nullptr, 0, stream)) return rc;
   mg_export<<<mg_grid(P.lv[level].n), kBlock, 0, stream>>>(P.lv[level], laplace_level_out);
+  PISO_LAUNCH_CHECK();
+  PISO_HIP_CHECK(hipStreamSynchronize(stream));
+  return PISO_OK;
+}
+
+// ---- the float32 cycle under the same fp64 PCG (mg_f32.h) ----------------------------------------------------------------------------------
+size_t piso_mg_workspace_bytes_cycle(int nx, int ny, int cycle_elem_size) {
+  if (cycle_elem_size == 8) return piso_mg_workspace_bytes(nx, ny);
+  if (cycle_elem_size != 4 || !mg_dims_ok(nx, ny)) return 0;
+  Arena ar(reinterpret_cast<void*>(256), ~(size_t)0);
+  MgPlanF P;
+  mg_plan_f32(nx, ny, 0, 0, ar, P);
+  return ar.used;
+}
+
+static void mg_record_f32(const MgRunF& R, int iterations, int cycles, int recomputed) {
+  int* d = tl_mg_dispatch;
+  d[MD_LEVELS] = R.P.nlev; d[MD_TAIL_FIRST] = R.use_tail ? R.P.tail_first : -1; d[MD_SWEEPS] = R.nu; d[MD_ITERATIONS] = iterations;
+  d[MD_CYCLES] = cycles; d[MD_RESIDUAL_RECOMPUTATIONS] = recomputed; d[MD_CYCLE_ELEM] = 4; d[MD_VEC_MASK] = R.vec_mask;
+  tl_mg_dispatch_n = MD_COUNT;
+}
+
+int piso_mg_pcg_solve_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence, double* x_out,
+                              float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps, int* iterations_out,
+                              void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
+  const piso::OptScope knobs;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (int rc = mg_common_args("piso_mg_pcg_solve", nx, ny, laplace, divergence, x_out, workspace, sweeps)) return rc;
+  if (max_iterations < 1 || residual_reset < 1) { set_error_msg("piso_mg_pcg_solve: max_iterations and residual_reset must be positive"); return PISO_ERR_INVALID_ARG; }
+  Arena ar(workspace, workspace_bytes);
+  MgPlanF P;
+  if (!mg_plan_f32(nx, ny, periodic_x ? 1 : 0, periodic_y ? 1 : 0, ar, P)) { set_error_msg("piso_mg_pcg_solve: workspace too small"); return PISO_ERR_INVALID_ARG; }
+  if (int rc = mg_build_f32(P, laplace, divergence, rank_deficient ? 1 : 0, stream)) return rc;
+  MgState* pinned = nullptr;
+  if (int rc = mg_pinned(&pinned)) return rc;
+  const Lv& L0 = P.L0;
+  const int n = L0.n, g0 = mg_grid(n);
+  MgRunF R{P, sweeps, P.tail_first >= 0 && opt(OPT_MG_TAIL) != 0, opt(OPT_MG_F32_VEC) != 0, stream};
+  const int check_every = opt(OPT_MG_CHECK_EVERY) > 0 ? opt(OPT_MG_CHECK_EVERY) : kCheckEvery;
+  double* r = P.r64;
+  float* r32 = P.r[0];
+  mg_init_f32<<<g0, kBlock, 0, stream>>>(L0, divergence, x_out, r, P.scal, r32);
+  bool done = false;
+  int iterations = max_iterations;
+  for (int k = 0; k < max_iterations && !done; ++k) {
+    const bool restart = k > 0 && (k + 1) % residual_reset == 0;
+    if (restart) mg_residual_f32<<<g0, kBlock, 0, stream>>>(L0, divergence, x_out, r, P.scal, P.st, r32);
+    int n_rz = 0;
+    const float* z = R.cycle(r32, r, &n_rz);
+    mg_direction_f32<<<g0, kBlock, 0, stream>>>(L0, z, P.p[k & 1], P.p[(k + 1) & 1], P.q, P.part_rz, n_rz, P.scal, k, (restart || k == 0) ? 1 : 0, P.part_pq, P.st);
+    mg_update_f32<<<g0, kBlock, 0, stream>>>(n, x_out, r, P.p[(k + 1) & 1], P.q, P.scal, k, P.part_pq, g0, P.part_max, P.st, r32);
+    mg_check<<<1, kBlock, 0, stream>>>(P.part_max, g0, accuracy, k + 1, P.st);
+    PISO_LAUNCH_CHECK();
+    if ((k + 1) % check_every == 0 || k + 1 == max_iterations) {
+      PISO_HIP_CHECK(hipMemcpyAsync(pinned, P.st, sizeof(MgState), hipMemcpyDeviceToHost, stream));
+      PISO_HIP_CHECK(hipStreamSynchronize(stream));
+      if (pinned->done) { done = true; iterations = pinned->iterations; }
+    }
+  }
+  if (rank_deficient) {
+    mg_sum_x<<<g0, kBlock, 0, stream>>>(L0, x_out, P.parts);
+    mg_finish<<<g0, kBlock, 0, stream>>>(L0, x_out, P.parts, g0, P.scal);
+    PISO_LAUNCH_CHECK();
+  }
+  PISO_HIP_CHECK(hipStreamSynchronize(stream));
+  if (iterations_out) *iterations_out = iterations;
+  int recomputed = 0;
+  for (int k = 1; k < iterations; ++k) recomputed += (k + 1) % residual_reset == 0;
+  mg_record_f32(R, iterations, iterations, recomputed);
+  return PISO_OK;
+}
+
+int piso_mg_vcycle_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* r_in, double* z_out, int sweeps,
+                           void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
+  const piso::OptScope knobs;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (int rc = mg_common_args("piso_mg_vcycle", nx, ny, laplace, r_in, z_out, workspace, sweeps)) return rc;
+  Arena ar(workspace, workspace_bytes);
+  MgPlanF P;
+  if (!mg_plan_f32(nx, ny, periodic_x ? 1 : 0, periodic_y ? 1 : 0, ar, P)) { set_error_msg("piso_mg_vcycle: workspace too small"); return PISO_ERR_INVALID_ARG; }
+  if (int rc = mg_build_f32(P, laplace, nullptr, 0, stream)) return rc;
+  MgRunF R{P, sweeps, P.tail_first >= 0 && opt(OPT_MG_TAIL) != 0, opt(OPT_MG_F32_VEC) != 0, stream};
+  const int n = P.L0.n;
+  mg_cast_f32<<<mg_grid(n), kBlock, 0, stream>>>(n, r_in, P.r[0]);
+  int n_rz = 0;
+  const float* z = R.cycle(P.r[0], nullptr, &n_rz);
+  mg_widen_f32<<<mg_grid(n), kBlock, 0, stream>>>(n, z, z_out);
+  PISO_LAUNCH_CHECK();
+  PISO_HIP_CHECK(hipStreamSynchronize(stream));
+  mg_record_f32(R, 0, 1, 0);
+  return PISO_OK;
+}
+
+int piso_mg_level_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, int level, int* nx_out, int* ny_out,
+                          double* laplace_level_out, void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
+  const piso::OptScope knobs;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (int rc = mg_common_args("piso_mg_level", nx, ny, laplace, nx_out, ny_out, workspace, 1)) return rc;
+  Arena ar(workspace, workspace_bytes);
+  MgPlanF P;
+  if (!mg_plan_f32(nx, ny, periodic_x ? 1 : 0, periodic_y ? 1 : 0, ar, P)) { set_error_msg("piso_mg_level: workspace too small"); return PISO_ERR_INVALID_ARG; }
+  if (level < 0 || level >= P.nlev) { *nx_out = 0; *ny_out = 0; set_error_msg("piso_mg_level: no such level"); return PISO_ERR_INVALID_ARG; }
+  *nx_out = P.lv[level].nx; *ny_out = P.lv[level].ny;
+  if (!laplace_level_out) return PISO_OK;                     // (sizes only)
+  if (int rc = mg_build_f32(P, laplace, nullptr, 0, stream)) return rc;
+  mg_export_f32<<<mg_grid(P.lv[level].n), kBlock, 0, stream>>>(P.lv[level], laplace_level_out);
   PISO_LAUNCH_CHECK();
   PISO_HIP_CHECK(hipStreamSynchronize(stream));
   return PISO_OK;

@@ -49,6 +49,13 @@ struct GeoSlab {
   __device__ __forceinline__ int erow(int j) const { return coarse_global ? ((row0 + j + nyg) % nyg) >> 1 : j >> 1; }
 };
 #define MG_N(name) name##_slab
+#define MG_REAL double
+#define MG_LV Lv
+#define MG_RDOT_PARAM
+#define MG_RDOT_ARG(rd)
+#define MG_RDOT(rc, zo, c) rc * zo
+#define MG_R32_PARAM
+#define MG_R32_STORE(c, v)
 #define MG_GEO_PARAM , GeoSlab g
 #define MG_NB(c, i, j, nx, ny) g.nb(c, i, nx)
 #define MG_JS(j, ny) j - 1
@@ -65,17 +72,7 @@ struct GeoSlab {
     pnew[ch] = restart ? z[ch] : z[ch] + beta * pold[ch];                                                                       \
   }
 #include "mg_cells.inc"
-#undef MG_N
-#undef MG_GEO_PARAM
-#undef MG_NB
-#undef MG_JS
-#undef MG_JN
-#undef MG_EROW
-#undef MG_FIRST_ROW
-#undef MG_LAST_ROW
-#undef MG_DIAG
-#undef MG_NCELLS
-#undef MG_DIRECTION_HALO_ROWS
+#include "mg_cells_undef.inc"
 
 __global__ __launch_bounds__(kBlock) void mg_slab_diag(const double* __restrict__ Lin, double* __restrict__ dg, int n) {
   const Walk w = grid_walk();
@@ -485,7 +482,7 @@ struct MgSlab {
   void record(int sweeps, int iterations, int cycles, int recomputed) const {
     int* d = tl_mg_dispatch;
     d[MD_LEVELS] = sp.d.nlev; d[MD_TAIL_FIRST] = use_tail ? sp.tail_first : -1; d[MD_SWEEPS] = sweeps; d[MD_ITERATIONS] = iterations;
-    d[MD_CYCLES] = cycles; d[MD_RESIDUAL_RECOMPUTATIONS] = recomputed;
+    d[MD_CYCLES] = cycles; d[MD_RESIDUAL_RECOMPUTATIONS] = recomputed; d[MD_CYCLE_ELEM] = 8; d[MD_VEC_MASK] = 0;
     tl_mg_dispatch_n = MD_COUNT;
   }
 

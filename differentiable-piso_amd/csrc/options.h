@@ -4,8 +4,9 @@
 // switch a check / a measurement aid on and off.  Bitwise the same result: cg_no_compact, cg_no_recon, cg_no_sym, cg_nt, the bicg_* knobs and
 // conv_lds, mg_tail and mg_check_every (same operations in the same order; tests/test_gpu_conv_dispatch.py holds conv_lds to it, non-finite inputs included).  Equal to round-off only - they change which workgroup or block owns which cells, so the partial
 // sums of the dot products are grouped differently: cg_persist, cg_persist_r, cg_persist_half, cg_persist_nq, cg_xcd_local, cg_pad, cg_tiny,
-// cg_rpw, cg_maxblocks (tests/test_gpu_cg_dispatch.py holds both groups to their word).  Stores and loads are atomic; a call works on a
-// snapshot (OptScope).
+// cg_rpw, cg_maxblocks (tests/test_gpu_cg_dispatch.py holds both groups to their word).  mg_f32_vec belongs to the second group: the
+// cycle's z is bitwise the same, the partials of (r, z) are grouped by other threads (tests/test_gpu_mg_f32.py).  Stores and loads are
+// atomic; a call works on a snapshot (OptScope).
 #pragma once
 
 namespace piso {
@@ -37,6 +38,7 @@ enum Opt {
   OPT_MG_TAIL,             // 0: the multigrid cycle (mg.hip) runs its coarse levels as launches of their own instead of inside one workgroup (the same arithmetic per cell)
   OPT_MG_CHECK_EVERY,      // multigrid PCG: iterations queued between two host looks (default 4; result and count do not depend on it)
   OPT_MG_SLAB_GATHER_CELLS, // slab multigrid: the gather limit where positive and below kGatherCells = 8192 (mg_slab_plan.h); it moves the first replicated level, which tests use to shard levels of small grids.  A different limit is a different plan: sums are grouped by other ranks' rows (round-off only)
+  OPT_MG_F32_VEC,          // 0: the float32 multigrid cycle (mg_f32.h) runs its one-cell-per-thread kernels on every level instead of the four-cell kernels where nx % 4 == 0 (the same z, bit for bit; the (r, z) partials are grouped by other threads: solves equal to round-off)
   OPT_COUNT
 };
 

@@ -67,6 +67,14 @@ lib.piso_mg_vcycle_f64.argtypes = [_i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, 
 lib.piso_mg_vcycle_f64.restype = _i
 lib.piso_mg_level_f64.argtypes = [_i, _i, _i, _i, _vp, _i, _ip, _ip, _vp, _vp, _sz, _vp]
 lib.piso_mg_level_f64.restype = _i
+lib.piso_mg_workspace_bytes_cycle.argtypes = [_i, _i, _i]
+lib.piso_mg_workspace_bytes_cycle.restype = _sz
+lib.piso_mg_pcg_solve_c32_f64.argtypes = lib.piso_mg_pcg_solve_f64.argtypes
+lib.piso_mg_pcg_solve_c32_f64.restype = _i
+lib.piso_mg_vcycle_c32_f64.argtypes = lib.piso_mg_vcycle_f64.argtypes
+lib.piso_mg_vcycle_c32_f64.restype = _i
+lib.piso_mg_level_c32_f64.argtypes = lib.piso_mg_level_f64.argtypes
+lib.piso_mg_level_c32_f64.restype = _i
 lib.piso_mg_slab_workspace_bytes.argtypes = [_i, _i, _i, _i]
 lib.piso_mg_slab_workspace_bytes.restype = _sz
 lib.piso_mg_slab_plan.argtypes = [_i, _i, _i, _i, _ip, _i]
@@ -294,7 +302,7 @@ def conv_last_dispatch():
     return _last_dispatch(lib.piso_conv_last_dispatch, "piso_conv_last_dispatch", CONV_DISPATCH_FIELDS)
 
 
-MG_DISPATCH_FIELDS = ("levels", "tail_first", "sweeps", "iterations", "cycles", "residual_recomputations")
+MG_DISPATCH_FIELDS = ("levels", "tail_first", "sweeps", "iterations", "cycles", "residual_recomputations", "cycle_elem", "vec_mask")
 
 
 def mg_slab_plan(nx, ny, world, gather_cells=0):

@@ -595,49 +595,62 @@ class PisoPressureSolverCudaCustom(PoissonSolver):
 PisoPressureSolverHip = PisoPressureSolverCudaCustom
 
 
-def mg_workspace(nx, ny, device):
-    nbytes = N.lib.piso_mg_workspace_bytes(nx, ny)
+def _mg_cycle_elem(cycle_dtype):
+    """8 / 4 for the two precisions of the multigrid cycle; anything else is refused."""
+    if cycle_dtype == torch.float64:
+        return 8
+    if cycle_dtype == torch.float32:
+        return 4
+    raise ValueError("cycle_dtype must be torch.float64 or torch.float32 (got %r)" % (cycle_dtype,))
+
+
+def mg_workspace(nx, ny, device, cycle_dtype=torch.float64):
+    elem = _mg_cycle_elem(cycle_dtype)
+    nbytes = N.lib.piso_mg_workspace_bytes(nx, ny) if elem == 8 else N.lib.piso_mg_workspace_bytes_cycle(nx, ny, elem)
     if nbytes == 0:
         raise N.PisoNativeError("the multigrid pressure solver needs at least 4 cells in each dimension (got %d x %d); "
                                 "use PisoPressureSolverCudaCustom" % (ny, nx))
     return N.workspace(nbytes, device, "mg")
 
 
-def mg_solve_native(nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset, sweeps=2):
-    """-> (x, iterations): multigrid-preconditioned CG on the system cg_solve_native solves (csrc/mg.hip; fp64)."""
+def mg_solve_native(nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset, sweeps=2, cycle_dtype=torch.float64):
+    """-> (x, iterations): multigrid-preconditioned CG on the system cg_solve_native solves (csrc/mg.hip; fp64).  cycle_dtype=torch.float32:
+    the same fp64 iteration around a float32 V-cycle (csrc/mg_f32.h)."""
     if L.dtype != torch.float64:
         raise N.PisoNativeError("the multigrid pressure solver is fp64 only; use the plain CG (cg_solve_native) for float32")
+    fn = N.lib.piso_mg_pcg_solve_f64 if _mg_cycle_elem(cycle_dtype) == 8 else N.lib.piso_mg_pcg_solve_c32_f64
     div = div.reshape(-1).to(torch.float64).contiguous()
     x = torch.empty_like(div)
-    ws = mg_workspace(nx, ny, div.device)
+    ws = mg_workspace(nx, ny, div.device, cycle_dtype)
     it = C.c_int(0)
-    st = N.lib.piso_mg_pcg_solve_f64(nx, ny, int(per_x), int(per_y), N.ptr(L), N.ptr(div), N.ptr(x), C.c_float(accuracy), int(max_iterations),
-                                     int(bool(rank_deficient)), int(residual_reset), int(sweeps), C.byref(it), N.ptr(ws), C.c_size_t(ws.numel()),
-                                     N.stream_ptr())
+    st = fn(nx, ny, int(per_x), int(per_y), N.ptr(L), N.ptr(div), N.ptr(x), C.c_float(accuracy), int(max_iterations),
+            int(bool(rank_deficient)), int(residual_reset), int(sweeps), C.byref(it), N.ptr(ws), C.c_size_t(ws.numel()), N.stream_ptr())
     N.check(st, "piso_mg_pcg_solve")
     return x, it.value
 
 
-def mg_vcycle_native(nx, ny, per_x, per_y, L, r, sweeps=2):
-    """z = M^-1 r: one V-cycle of the multigrid preconditioner (tests, measurements)."""
+def mg_vcycle_native(nx, ny, per_x, per_y, L, r, sweeps=2, cycle_dtype=torch.float64):
+    """z = M^-1 r: one V-cycle of the multigrid preconditioner (tests, measurements); float64 in and out in either precision of the cycle."""
+    fn = N.lib.piso_mg_vcycle_f64 if _mg_cycle_elem(cycle_dtype) == 8 else N.lib.piso_mg_vcycle_c32_f64
     r = r.reshape(-1).to(torch.float64).contiguous()
     z = torch.empty_like(r)
-    ws = mg_workspace(nx, ny, r.device)
-    N.check(N.lib.piso_mg_vcycle_f64(nx, ny, int(per_x), int(per_y), N.ptr(L), N.ptr(r), N.ptr(z), int(sweeps), N.ptr(ws), C.c_size_t(ws.numel()),
-                                     N.stream_ptr()), "piso_mg_vcycle")
+    ws = mg_workspace(nx, ny, r.device, cycle_dtype)
+    N.check(fn(nx, ny, int(per_x), int(per_y), N.ptr(L), N.ptr(r), N.ptr(z), int(sweeps), N.ptr(ws), C.c_size_t(ws.numel()), N.stream_ptr()),
+            "piso_mg_vcycle")
     return z
 
 
-def mg_level_native(nx, ny, per_x, per_y, L, level):
-    """-> (A_level [nyl * nxl, 5], nxl, nyl), or None past the coarsest level (tests)."""
-    ws = mg_workspace(nx, ny, L.device)
+def mg_level_native(nx, ny, per_x, per_y, L, level, cycle_dtype=torch.float64):
+    """-> (A_level [nyl * nxl, 5], nxl, nyl), or None past the coarsest level (tests); the float32 cycle's entries come widened to float64."""
+    fn = N.lib.piso_mg_level_f64 if _mg_cycle_elem(cycle_dtype) == 8 else N.lib.piso_mg_level_c32_f64
+    ws = mg_workspace(nx, ny, L.device, cycle_dtype)
     nxl, nyl = C.c_int(0), C.c_int(0)
-    if N.lib.piso_mg_level_f64(nx, ny, int(per_x), int(per_y), N.ptr(L), int(level), C.byref(nxl), C.byref(nyl), None, N.ptr(ws),
-                               C.c_size_t(ws.numel()), N.stream_ptr()) != 0:
+    if fn(nx, ny, int(per_x), int(per_y), N.ptr(L), int(level), C.byref(nxl), C.byref(nyl), None, N.ptr(ws), C.c_size_t(ws.numel()),
+          N.stream_ptr()) != 0:
         return None
     out = torch.empty((nxl.value * nyl.value, 5), dtype=torch.float64, device=L.device)
-    N.check(N.lib.piso_mg_level_f64(nx, ny, int(per_x), int(per_y), N.ptr(L), int(level), C.byref(nxl), C.byref(nyl), N.ptr(out), N.ptr(ws),
-                                    C.c_size_t(ws.numel()), N.stream_ptr()), "piso_mg_level")
+    N.check(fn(nx, ny, int(per_x), int(per_y), N.ptr(L), int(level), C.byref(nxl), C.byref(nyl), N.ptr(out), N.ptr(ws), C.c_size_t(ws.numel()),
+               N.stream_ptr()), "piso_mg_level")
     return out, nxl.value, nyl.value
 
 
@@ -649,6 +662,10 @@ class PisoPressureSolverMultigrid(PisoPressureSolverCudaCustom):
     iterations here (a few dozen suffice).  Measured faster than the plain solver from 256 x 256 cells up (3x at 256^2, 25 - 77x at
     2048^2; DESIGN.md 3.7 has the table); not measured on smaller grids, where the plain solver's one-workgroup kernels have no
     launch or host round trip per iteration and are the better choice.  fp64 only: cast_to_double=False is refused.
+    cycle_dtype=torch.float32 (opt-in) keeps that fp64 iteration - x, r, p, q, the operator, every sum, the stopping rule - and runs the
+    V-cycle, hierarchy included, in float32 (csrc/mg_f32.h): the same counts or a few more iterations (DESIGN.md 3.7 has both tables), r is
+    not scaled, so a residual beyond float32's range never converges and tolerances below ~1e-30 are outside that mode.  It is one-GPU only:
+    with a communicator that would cut the solve it is refused.
     With a distributed.SlabCommunicator of more than one rank in `slab_comm` the solve is cut into y-slabs like the plain solver's (csrc/mg_slab.h:
     fine levels sharded with halo rows, the levels of at most 8192 cells replicated; ny / ranks must be divisible by 2^g, g the first replicated
     level, else the call is refused and names the plain solver); with `.sharded` L holds the rank's rows and the result stays on them.  Anything
@@ -660,15 +677,17 @@ class PisoPressureSolverMultigrid(PisoPressureSolverCudaCustom):
     solver."""
 
     def __init__(self, dx, accuracy=1e-5, max_iterations=2000, residual_reset=10, randomized_restarts=0, cast_to_double=True,
-                 smoothing_sweeps=2):
+                 smoothing_sweeps=2, cycle_dtype=torch.float64):
         if not cast_to_double:
             raise ValueError("PisoPressureSolverMultigrid is fp64 only (cast_to_double=True); use PisoPressureSolverCudaCustom for float32")
         if not 1 <= int(smoothing_sweeps) <= 8:
             raise ValueError("smoothing_sweeps must be 1 .. 8")
+        _mg_cycle_elem(cycle_dtype)
         PisoPressureSolverCudaCustom.__init__(self, dx, accuracy=accuracy, max_iterations=max_iterations, residual_reset=residual_reset,
                                               randomized_restarts=randomized_restarts, cast_to_double=True)
         self.name = "HIP multigrid-preconditioned Conjugate Gradient"
         self.smoothing_sweeps = int(smoothing_sweeps)
+        self.cycle_dtype = cycle_dtype
 
     def _cg(self, nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset):
         from .distributed import SlabCommunicator, mg_solve_slab, mg_solve_slab_local
@@ -679,6 +698,9 @@ class PisoPressureSolverMultigrid(PisoPressureSolverCudaCustom):
             raise N.PisoNativeError("PisoPressureSolverMultigrid is fp64 only; use PisoPressureSolverCudaCustom for float32")
         # (option slab_force: a communicator of ONE rank still runs the slab solve - a ring of one, tests)
         if self.slab_comm is not None and (self.slab_comm.world > 1 or N.get_option("slab_force") > 0):
+            if self.cycle_dtype != torch.float64:
+                raise N.PisoNativeError("PisoPressureSolverMultigrid: the float32 cycle runs on one GPU only; a solve cut into y-slabs needs "
+                                        "cycle_dtype=torch.float64")
             if self.slab_comm.sharded:       # slab-decomposed STEP: L holds the rank's owned rows, div its stored rows; the result stays there
                 sh = self.slab_comm.step_sharding
                 d_loc = sh.owned_cells(div.reshape(-1).to(torch.float64)).reshape(-1).contiguous()
@@ -689,9 +711,10 @@ class PisoPressureSolverMultigrid(PisoPressureSolverCudaCustom):
                 return x, it
             return mg_solve_slab(self.slab_comm, nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset,
                                  self.smoothing_sweeps)
-        return mg_solve_native(nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset, self.smoothing_sweeps)
+        return mg_solve_native(nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset, self.smoothing_sweeps,
+                               self.cycle_dtype)
 
     @staticmethod
     def last_dispatch():
-        """levels, tail_first, sweeps, iterations, cycles, residual_recomputations of this thread's last multigrid solve."""
+        """levels, tail_first, sweeps, iterations, cycles, residual_recomputations, cycle_elem, vec_mask of this thread's last multigrid solve."""
         return N.mg_last_dispatch()

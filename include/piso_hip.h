@@ -351,6 +351,26 @@ int piso_mg_vcycle_f64(int nx, int ny, int periodic_x, int periodic_y, const dou
                        int sweeps, void* workspace, size_t workspace_bytes, piso_stream_t stream);
 int piso_mg_level_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, int level, int* nx_out, int* ny_out,
                       double* laplace_level_out, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+/* The float32 cycle (csrc/mg_f32.h; opt-in): the same PCG in float64 - x, r, p, q, the level-0 operator of q = L p and of the residual
+ * recomputation, alpha, beta, every sum, the stopping rule, the constant mode - around a V-cycle whose hierarchy and vectors are stored and
+ * computed in float32.  Level 0 is fl32 of the fp64 set-up's arrays, level l + 1 is fl32(1/2 P^T A_l P) accumulated in double from the
+ * float32 entries of level l and rounded once, the Jacobi weight is fl32(0.8 / (double)diag32); the cycle reads fl32(r) and returns a
+ * float32 z, which the direction kernel widens; the (r, z) partials are accumulated in double from the double r and the float z.  r is
+ * not scaled: a residual beyond float32's range turns Inf / NaN in the cycle and never counts as converged, and an accuracy below about
+ * 1e-30 is outside this mode.  Iteration counts are those of the fp64 cycle or a few more.  The entries take the arguments
+ * of their fp64 namesakes, refuse what they refuse with the same status (the pattern checks run on the double matrix), want a workspace
+ * of piso_mg_workspace_bytes_cycle(nx, ny, 4) bytes (cycle_elem_size 8: piso_mg_workspace_bytes; anything else: 0) and are bitwise
+ * reproducible.  piso_mg_vcycle_c32_f64 casts r_in and widens z_out; piso_mg_level_c32_f64 returns the float32 entries widened.
+ * Option "mg_f32_vec" 0 runs the one-cell-per-thread kernels on every level instead of the four-cell kernels (levels with nx % 4 == 0
+ * above the tail): the same z bit for bit, a solve equal to round-off (the (r, z) partials are grouped by other threads). */
+size_t piso_mg_workspace_bytes_cycle(int nx, int ny, int cycle_elem_size);
+int piso_mg_pcg_solve_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence,
+                              double* x_out, float accuracy, int max_iterations, int rank_deficient, int residual_reset,
+                              int sweeps, int* iterations_out, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+int piso_mg_vcycle_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* r_in, double* z_out,
+                           int sweeps, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+int piso_mg_level_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, int level, int* nx_out, int* ny_out,
+                          double* laplace_level_out, void* workspace, size_t workspace_bytes, piso_stream_t stream);
 /* The same solver on y-slabs (csrc/mg_slab.h, csrc/mg_slab_plan.h): every rank owns ny_local = ny / world contiguous rows and passes its
  * rows of laplace / divergence / x, otherwise the arguments of piso_mg_pcg_solve_f64.  Levels 0 .. g - 1 are sharded (a rank's rows
  * plus one halo row below and above), level g - the first of at most 8192 cells, or of at most "mg_slab_gather_cells" cells where that
@@ -382,13 +402,15 @@ int piso_mg_vcycle_slab_emulated_f64(int slabs, int nx, int ny, int periodic_x, 
                                      int sweeps, void* workspace, size_t workspace_bytes, piso_stream_t stream);
 int piso_mg_level_slab_emulated_f64(int slabs, int rank, int nx, int ny, int periodic_x, int periodic_y, const double* laplace, int level, int* nx_out,
                                     int* rows_out, double* laplace_level_out, void* workspace, size_t workspace_bytes, piso_stream_t stream);
-/* What the calling thread's last piso_mg_pcg_solve_f64 / piso_mg_vcycle_f64 ran; returns the number of fields (6):
+/* What the calling thread's last multigrid solve / cycle ran (fp64, float32 cycle or slab); returns the number of fields (8):
  *    0 levels         levels of the hierarchy
  *    1 tail_first     first level that ran inside the one-workgroup tail kernel (-1: none)
  *    2 sweeps
  *    3 iterations     0 after piso_mg_vcycle_f64
  *    4 cycles         V-cycles that contributed to the result
- *    5 residual_recomputations */
+ *    5 residual_recomputations
+ *    6 cycle_elem     bytes of a value of the cycle: 8, or 4 after a piso_mg_*_c32_f64 entry
+ *    7 vec_mask       bit l set where level l ran the four-cell float32 kernels (0 for the fp64 and the slab paths) */
 int piso_mg_last_dispatch(int* out, int capacity);
 
 /* ---------------------------------------------------------------------------------------------------------------
