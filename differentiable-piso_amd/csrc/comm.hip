@@ -132,6 +132,31 @@ __global__ __launch_bounds__(kBlock) void peer_allgather(PeerView pv, size_t are
   }
 }
 
+// ... and of `count` floats per rank: a float is one tagged word {payload | epoch}; source r's chunk starts at word r count of the
+// parity's half.  The same epochs and halves as peer_allgather (one sequence over both).
+__global__ __launch_bounds__(kBlock) void peer_allgather_f32(PeerView pv, size_t area, const float* __restrict__ src, float* __restrict__ dst, int count,
+                                                             unsigned seq, int* err) {
+  const size_t base = area + (size_t)(seq & 1) * PeerLayout::kGatherParityBytes;
+  const int tid = blockIdx.x * kBlock + threadIdx.x, nt = gridDim.x * kBlock;
+  for (int w = tid; w < count; w += nt) {
+    const peer_u64 word = ((peer_u64)__float_as_uint(src[w]) << 32) | seq;
+    for (int p = 0; p < pv.world; ++p) peer_store(reinterpret_cast<peer_u64*>(pv.mbox[p] + base) + (size_t)pv.rank * count + w, word);
+  }
+  const peer_u64* mine = reinterpret_cast<const peer_u64*>(pv.mbox[pv.rank] + base);
+  const int total = count * pv.world;
+  for (int i = tid; i < total; i += nt) {
+    peer_u64 word = 0;
+    unsigned spins = 0;
+    while (true) {
+      word = peer_load(mine + (size_t)i);
+      if ((unsigned)(word & 0xffffffffull) == seq) break;
+      if (++spins > kPeerSpinLimit) { *err = 1; return; }
+      __builtin_amdgcn_s_sleep(2);
+    }
+    dst[i] = __uint_as_float((unsigned)(word >> 32));
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ host collectives (slab_comm.h)
 // (a communicator is made by piso_comm_create or piso_comm_peer_create[_fd] only: what is not PEER is RCCL and has its ncclComm_t)
 static bool is_peer(const PisoComm* pc) { return pc->transport == TRANSPORT_PEER; }
@@ -180,6 +205,43 @@ int comm_exchange_rows(PisoComm* pc, bool periodic_y, double* row0, int nx, int 
   if (lo >= 0) PISO_NCCL_CHECK(g_rccl.Recv(below, nx, dt, lo, pc->comm, s));      // lower's top row -> my lower halo
   if (lo >= 0) PISO_NCCL_CHECK(g_rccl.Send(row0, nx, dt, lo, pc->comm, s));       // my bottom row -> lower's upper halo
   if (hi >= 0) PISO_NCCL_CHECK(g_rccl.Recv(above, nx, dt, hi, pc->comm, s));      // upper's bottom row -> my upper halo
+  PISO_NCCL_CHECK(g_rccl.GroupEnd());
+  return PISO_OK;
+}
+
+int comm_allgather_f32(PisoComm* pc, const float* src, float* dst, size_t count, hipStream_t s) {
+  if (is_peer(pc)) {
+    if (count * (size_t)pc->world > (size_t)kGatherCells) { set_error_msg("peer transport: an all-gather carries at most 8192 floats over all ranks"); return PISO_ERR_INVALID_ARG; }
+    if (count == 0) return PISO_OK;
+    if (pc->world == 1 && opt(OPT_SLAB_FORCE) <= 0) {
+      if (src != dst) PISO_HIP_CHECK(hipMemcpyAsync(dst, src, count * sizeof(float), hipMemcpyDeviceToDevice, s));
+      return PISO_OK;
+    }
+    const int grid = (int)((count + kBlock - 1) / kBlock);
+    peer_allgather_f32<<<grid < 32 ? grid : 32, kBlock, 0, s>>>(make_view(pc, true), PeerLayout::gather_area(pc->row_cap), src, dst, (int)count, ++pc->seq_ga, pc->err);
+    return PISO_OK;
+  }
+  PISO_NCCL_CHECK(g_rccl.AllGather(src, dst, count, ncclFloat, pc->comm, s));
+  return PISO_OK;
+}
+int comm_exchange_rows_f32(PisoComm* pc, bool periodic_y, float* row0, int nx, int ny, hipStream_t s) {
+  float *top = row0 + (size_t)(ny - 1) * nx, *below = row0 - nx, *above = row0 + (size_t)ny * nx;
+  const PeerView pv = make_view(pc, periodic_y);
+  if (is_peer(pc)) {
+    if (nx > (int)pc->row_cap) { set_error_msg("peer transport: row longer than the mailbox rows"); return PISO_ERR_INVALID_ARG; }
+    // the four messages of a row exchange, as element offsets from the halo row below: {to upper, to lower, from lower, from upper}.
+    // The floats travel as their 32 bits (the int instance: int -> double -> int is exact, so every bit pattern arrives unchanged)
+    const HaloMsg up{1, {ny * nx, 0, 0}, {nx, 0, 0}}, down{1, {nx, 0, 0}, {nx, 0, 0}}, from_lo{1, {0, 0, 0}, {nx, 0, 0}}, from_hi{1, {(ny + 1) * nx, 0, 0}, {nx, 0, 0}};
+    peer_exchange_segments<int><<<2, 256, 0, s>>>(pv, reinterpret_cast<int*>(below), up, down, from_lo, from_hi, ++pc->seq_ex, pc->err);
+    return PISO_OK;
+  }
+  const int lo = pv.lower, hi = pv.upper;                  // (the UPWARD transfer first, then the DOWNWARD one: slab_comm.h)
+  constexpr ncclDataType_t dt = ncclFloat;
+  PISO_NCCL_CHECK(g_rccl.GroupStart());
+  if (hi >= 0) PISO_NCCL_CHECK(g_rccl.Send(top, nx, dt, hi, pc->comm, s));
+  if (lo >= 0) PISO_NCCL_CHECK(g_rccl.Recv(below, nx, dt, lo, pc->comm, s));
+  if (lo >= 0) PISO_NCCL_CHECK(g_rccl.Send(row0, nx, dt, lo, pc->comm, s));
+  if (hi >= 0) PISO_NCCL_CHECK(g_rccl.Recv(above, nx, dt, hi, pc->comm, s));
   PISO_NCCL_CHECK(g_rccl.GroupEnd());
   return PISO_OK;
 }
@@ -465,6 +527,16 @@ int piso_comm_allgather_f64(void* comm, const void* src, void* dst, int count, p
   if (!pc || !src || !dst || count < 0) { set_error_msg("piso_comm_allgather_f64: invalid argument"); return PISO_ERR_INVALID_ARG; }
   PISO_TRY(comm_ready(pc, "piso_comm_allgather_f64: the peer communicator is not connected"));
   PISO_TRY(comm_allgather_f64(pc, static_cast<const double*>(src), static_cast<double*>(dst), (size_t)count, static_cast<hipStream_t>(stream_)));
+  PISO_LAUNCH_CHECK();
+  return PISO_OK;
+}
+// ... and of `count` floats per rank (the float rows of the float32 multigrid cycle; peer: count * world <= 8192)
+int piso_comm_allgather_f32(void* comm, const void* src, void* dst, int count, piso_stream_t stream_) {
+  const piso::OptScope knobs;
+  PisoComm* pc = static_cast<PisoComm*>(comm);
+  if (!pc || !src || !dst || count < 0) { set_error_msg("piso_comm_allgather_f32: invalid argument"); return PISO_ERR_INVALID_ARG; }
+  PISO_TRY(comm_ready(pc, "piso_comm_allgather_f32: the peer communicator is not connected"));
+  PISO_TRY(comm_allgather_f32(pc, static_cast<const float*>(src), static_cast<float*>(dst), (size_t)count, static_cast<hipStream_t>(stream_)));
   PISO_LAUNCH_CHECK();
   return PISO_OK;
 }

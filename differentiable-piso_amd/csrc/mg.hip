@@ -35,6 +35,7 @@
 // Opt-in: the same iteration around a float32 cycle (mg_f32.h, piso_mg_*_c32_f64); this file's kernels are its fp64 outer iteration.
 #include <vector>
 
+#include "mg_slab_carve.h"
 #include "mg_slab_plan.h"
 #include "options.h"
 #include "piso_common.h"
@@ -52,7 +53,6 @@ constexpr int kTailLds = 6144;         // cells of all tail levels together (r a
 constexpr int kTailThreads = 1024;
 constexpr int kTailMaxLevels = 8;
 constexpr int kMgMaxLevels = 16;
-constexpr int kMgGrid = 1024;          // grid cap of every kernel that publishes partials (4 workgroups per CU)
 constexpr int kCheckEvery = 4;         // iterations queued between two host looks
 constexpr double kRowSumTol = 1e-9;    // rank_deficient = 1: max|row sum| must stay below this times mean|diag|
 
@@ -60,15 +60,9 @@ constexpr double kRowSumTol = 1e-9;    // rank_deficient = 1: max|row sum| must 
 static_assert(kMinDim == kPlanMinDim && kTailCells == kPlanTailCells && kTailLds == kPlanTailLds && kTailMaxLevels == kPlanTailMaxLevels &&
               kMgMaxLevels == kPlanMaxLevels, "mg_slab_plan.h and mg.hip disagree about the hierarchy's constants");
 
-struct MgState { int done, iterations, flags, pad; };
+// (MgState, the SC_* slots of `scal`, the level structs Lv / LvF and kMgGrid: mg_slab_carve.h, host code a driver can walk)
 enum { MG_FLAG_BORDER = 1, MG_FLAG_ZERO_DIAG_ROW = 2, MG_FLAG_NOT_SINGULAR = 4 };
-enum { SC_RZ0 = 0, SC_RZ1, SC_SUM_DIAG, SC_NPRESENT, SC_MEAN_B, SC_COUNT_MG = 8 };
-
-struct Lv {
-  int nx, ny, n, per_x, per_y;
-  double* c[5];        // S, W, C, E, N
-  double* dinv;        // kOmega / diag, 0 on absent cells
-};
+static_assert(kPlanMaxRanks == kMaxRanks, "mg_slab_carve.h and peer.h disagree about the ranks of a node");
 
 struct Walk { int begin, step; };
 __device__ __forceinline__ Walk grid_walk() { return Walk{(int)(blockIdx.x * blockDim.x + threadIdx.x), (int)(gridDim.x * blockDim.x)}; }
@@ -379,6 +373,137 @@ static int mg_common_args(const char* who, int nx, int ny, const void* a, const 
 
 #include "mg_slab.h"
 #include "mg_f32.h"
+#include "mg_slab_f32.h"
+
+namespace piso {
+
+// ---- the slab entry points, once over the type of the cycle's values (mg_slab.h, mg_slab_f32.h) ------------------------------------------------
+// what the three communicator entry points share: one context, the rank's rows
+template <typename C>
+static int mg_slab_comm_begin(MgSlabT<C>& M, const char* who, void* comm, int nx, int nyl, int px, int py, const double* laplace, const void* a, const void* b,
+                              void* ws, size_t ws_bytes, int sweeps, hipStream_t stream) {
+  PisoComm* pc = static_cast<PisoComm*>(comm);
+  char msg[96];
+  if (!pc || !laplace || !a || !b || !ws) { snprintf(msg, sizeof(msg), "%s: NULL pointer", who); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
+  snprintf(msg, sizeof(msg), "%s: the peer communicator is not connected", who);
+  PISO_TRY(comm_ready(pc, msg));
+  PISO_TRY(mg_slab_begin(M, who, nx, nyl, pc->world, 1, px, py, sweeps, pc, stream));
+  M.R[0].rank = pc->rank; M.R[0].Lin = laplace; M.R[0].b = nullptr;
+  return M.carve(who, ws, ws_bytes);
+}
+// ... and the emulated ones: `slabs` virtual ranks over the full arrays
+template <typename C>
+static int mg_slab_emulated_begin(MgSlabT<C>& M, const char* who, int slabs, int nx, int ny, int px, int py, const double* laplace, const void* a, const void* b,
+                                  void* ws, size_t ws_bytes, int sweeps, hipStream_t stream) {
+  char msg[96];
+  if (!laplace || !a || !b || !ws) { snprintf(msg, sizeof(msg), "%s: NULL pointer", who); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
+  if (slabs < 1 || slabs > kMaxRanks || ny < slabs) { snprintf(msg, sizeof(msg), "%s: needs 1 .. %d slabs", who, kMaxRanks); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
+  if (ny % slabs != 0) {                                      // (the plan's refusal, with the rule)
+    const MgSlabPlan sp = mg_slab_plan(nx, ny, slabs, opt(OPT_MG_SLAB_GATHER_CELLS));
+    set_error_msg(sp.msg);
+    return PISO_ERR_INVALID_ARG;
+  }
+  PISO_TRY(mg_slab_begin(M, who, nx, ny / slabs, slabs, slabs, px, py, sweeps, nullptr, stream));
+  for (int r = 0; r < slabs; ++r) { M.R[r].rank = r; M.R[r].Lin = laplace + (size_t)r * (ny / slabs) * nx * 5; M.R[r].b = nullptr; }
+  return M.carve(who, ws, ws_bytes);
+}
+
+template <typename C>
+static int mg_slab_solve_comm(const char* who, void* comm, int nx, int ny_local, int periodic_x, int periodic_y, const double* laplace_local, const double* divergence_local,
+                              double* x_out_local, float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps,
+                              int* iterations_out, void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
+  const OptScope knobs;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  char msg[128];
+  if (max_iterations < 1 || residual_reset < 1) { snprintf(msg, sizeof(msg), "%s: max_iterations and residual_reset must be positive", who); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
+  MgSlabT<C> M;
+  PISO_TRY(mg_slab_comm_begin(M, who, comm, nx, ny_local, periodic_x, periodic_y, laplace_local, divergence_local, x_out_local, workspace, workspace_bytes, sweeps, stream));
+  M.R[0].b = divergence_local;
+  // a refusal of the set-up is the same on every rank (all-reduced flags); whatever else fails is agreed below
+  PISO_TRY(M.solve(accuracy, max_iterations, rank_deficient ? 1 : 0, residual_reset, sweeps, iterations_out));
+  PISO_HIP_CHECK(hipMemcpyAsync(x_out_local, M.R[0].x, (size_t)nx * ny_local * sizeof(double), hipMemcpyDeviceToDevice, stream));
+  return M.finish(who);
+}
+template <typename C>
+static int mg_slab_solve_emulated(const char* who, int slabs, int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence, double* x_out,
+                                  float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps, int* iterations_out,
+                                  void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
+  const OptScope knobs;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  char msg[128];
+  if (max_iterations < 1 || residual_reset < 1) { snprintf(msg, sizeof(msg), "%s: max_iterations and residual_reset must be positive", who); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
+  MgSlabT<C> M;
+  PISO_TRY(mg_slab_emulated_begin(M, who, slabs, nx, ny, periodic_x, periodic_y, laplace, divergence, x_out, workspace, workspace_bytes, sweeps, stream));
+  const size_t n = (size_t)nx * (ny / slabs);
+  for (int r = 0; r < slabs; ++r) M.R[r].b = divergence + r * n;
+  PISO_TRY(M.solve(accuracy, max_iterations, rank_deficient ? 1 : 0, residual_reset, sweeps, iterations_out));
+  for (int r = 0; r < slabs; ++r) PISO_HIP_CHECK(hipMemcpyAsync(x_out + r * n, M.R[r].x, n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+  return M.finish(who);
+}
+
+// one cycle: the rank's rows of r go into the outer residual's rows, its rows of z come out
+template <typename C>
+static int mg_slab_one_cycle(MgSlabT<C>& M, const double* const* r_rows, double* const* z_rows, int sweeps, const char* who) {
+  PISO_TRY(M.build(0));
+  const size_t n = (size_t)M.sp.d.nx[0] * M.sp.nyl;
+  for (int q = 0; q < M.nloc(); ++q) PISO_TRY(MgSlabOps<C>::load_r(M.R[q], r_rows[q], n, M.s));
+  PISO_TRY(M.cycle(sweeps));
+  for (int q = 0; q < M.nloc(); ++q) PISO_TRY(MgSlabOps<C>::store_z(M.R[q], z_rows[q], n, M.s));
+  M.record(sweeps, 0, 1, 0);
+  return M.finish(who);
+}
+template <typename C>
+static int mg_slab_vcycle_comm(const char* who, void* comm, int nx, int ny_local, int periodic_x, int periodic_y, const double* laplace_local, const double* r_local,
+                               double* z_local, int sweeps, void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
+  const OptScope knobs;
+  MgSlabT<C> M;
+  PISO_TRY(mg_slab_comm_begin(M, who, comm, nx, ny_local, periodic_x, periodic_y, laplace_local, r_local, z_local, workspace, workspace_bytes, sweeps,
+                              static_cast<hipStream_t>(stream_)));
+  return mg_slab_one_cycle(M, &r_local, &z_local, sweeps, who);
+}
+template <typename C>
+static int mg_slab_vcycle_emulated(const char* who, int slabs, int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* r_in, double* z_out,
+                                   int sweeps, void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
+  const OptScope knobs;
+  MgSlabT<C> M;
+  PISO_TRY(mg_slab_emulated_begin(M, who, slabs, nx, ny, periodic_x, periodic_y, laplace, r_in, z_out, workspace, workspace_bytes, sweeps, static_cast<hipStream_t>(stream_)));
+  const size_t n = (size_t)nx * (ny / slabs);
+  std::vector<const double*> r(slabs);
+  std::vector<double*> z(slabs);
+  for (int q = 0; q < slabs; ++q) { r[q] = r_in + q * n; z[q] = z_out + q * n; }
+  return mg_slab_one_cycle(M, r.data(), z.data(), sweeps, who);
+}
+
+// a rank's rows of a sharded level, or the whole replicated level, as [nx_out * rows_out][5] (laplace_level_out NULL: sizes only)
+template <typename C>
+static int mg_slab_level(MgSlabT<C>& M, int q, int level, int* nx_out, int* rows_out, double* out, const char* who) {
+  if (level < 0 || level >= M.sp.d.nlev) { *nx_out = 0; *rows_out = 0; set_error_msg("piso_mg_level_slab: no such level"); return PISO_ERR_INVALID_ARG; }
+  *nx_out = M.sp.d.nx[level]; *rows_out = M.sp.rows[level];
+  if (!out) return PISO_OK;
+  PISO_TRY(M.build(0));
+  MgSlabOps<C>::export_level(M.R[q].lv[level], out, M.s);
+  return M.finish(who);
+}
+template <typename C>
+static int mg_slab_level_comm(const char* who, void* comm, int nx, int ny_local, int periodic_x, int periodic_y, const double* laplace_local, int level, int* nx_out,
+                              int* rows_out, double* laplace_level_out, void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
+  const OptScope knobs;
+  MgSlabT<C> M;
+  PISO_TRY(mg_slab_comm_begin(M, who, comm, nx, ny_local, periodic_x, periodic_y, laplace_local, nx_out, rows_out, workspace, workspace_bytes, 1,
+                              static_cast<hipStream_t>(stream_)));
+  return mg_slab_level(M, 0, level, nx_out, rows_out, laplace_level_out, who);
+}
+template <typename C>
+static int mg_slab_level_emulated(const char* who, int slabs, int rank, int nx, int ny, int periodic_x, int periodic_y, const double* laplace, int level, int* nx_out,
+                                  int* rows_out, double* laplace_level_out, void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
+  const OptScope knobs;
+  MgSlabT<C> M;
+  PISO_TRY(mg_slab_emulated_begin(M, who, slabs, nx, ny, periodic_x, periodic_y, laplace, nx_out, rows_out, workspace, workspace_bytes, 1, static_cast<hipStream_t>(stream_)));
+  if (rank < 0 || rank >= slabs) { set_error_msg("piso_mg_level_slab_emulated: no such rank"); return PISO_ERR_INVALID_ARG; }
+  return mg_slab_level(M, rank, level, nx_out, rows_out, laplace_level_out, who);
+}
+
+}  // namespace piso
 
 using namespace piso;
 
@@ -590,13 +715,16 @@ int piso_mg_level_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const 
   return PISO_OK;
 }
 
-// ---- the same solver on y-slabs (mg_slab.h) -----------------------------------------------------------------------------------------------
-size_t piso_mg_slab_workspace_bytes(int nx, int ny_local, int world, int local_ranks) {
+// ---- the same solver on y-slabs (mg_slab.h; the float32 cycle on them: mg_slab_f32.h) ---------------------------------------------------------
+size_t piso_mg_slab_workspace_bytes_cycle(int nx, int ny_local, int world, int local_ranks, int cycle_elem_size) {
   const piso::OptScope knobs;
-  if (ny_local < 1 || world < 1 || local_ranks < 1) return 0;
+  if (ny_local < 1 || world < 1 || local_ranks < 1 || (cycle_elem_size != 4 && cycle_elem_size != 8)) return 0;
   const MgSlabPlan sp = mg_slab_plan(nx, ny_local * world, world, opt(OPT_MG_SLAB_GATHER_CELLS));
-  if (sp.status) return 0;
-  return mg_slab_g_bytes(local_ranks) + (size_t)local_ranks * mg_slab_rank_bytes(sp);
+  if (sp.status || (cycle_elem_size == 4 && sp.g == 0)) return 0;
+  return mg_slab_g_bytes(local_ranks) + (size_t)local_ranks * (cycle_elem_size == 8 ? mg_slab_rank_bytes<double>(sp) : mg_slab_rank_bytes<float>(sp));
+}
+size_t piso_mg_slab_workspace_bytes(int nx, int ny_local, int world, int local_ranks) {
+  return piso_mg_slab_workspace_bytes_cycle(nx, ny_local, world, local_ranks, 8);
 }
 
 int piso_mg_slab_plan(int nx, int ny, int world, int gather_cells, int* out, int capacity) {
@@ -606,128 +734,43 @@ int piso_mg_slab_plan(int nx, int ny, int world, int gather_cells, int* out, int
   return out ? mg_slab_plan_record(sp, out, capacity) : 0;
 }
 
-// what the three communicator entry points share: one context, the rank's rows
-static int mg_slab_comm_begin(MgSlab& M, const char* who, void* comm, int nx, int nyl, int px, int py, const double* laplace, const void* a, const void* b,
-                              void* ws, size_t ws_bytes, int sweeps, hipStream_t stream) {
-  PisoComm* pc = static_cast<PisoComm*>(comm);
-  char msg[96];
-  if (!pc || !laplace || !a || !b || !ws) { snprintf(msg, sizeof(msg), "%s: NULL pointer", who); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
-  snprintf(msg, sizeof(msg), "%s: the peer communicator is not connected", who);
-  PISO_TRY(comm_ready(pc, msg));
-  PISO_TRY(mg_slab_begin(M, who, nx, nyl, pc->world, 1, px, py, sweeps, pc, stream));
-  M.R[0].rank = pc->rank; M.R[0].Lin = laplace; M.R[0].b = nullptr;
-  return M.carve(who, ws, ws_bytes);
-}
-// ... and the emulated ones: `slabs` virtual ranks over the full arrays
-static int mg_slab_emulated_begin(MgSlab& M, const char* who, int slabs, int nx, int ny, int px, int py, const double* laplace, const void* a, const void* b,
-                                  void* ws, size_t ws_bytes, int sweeps, hipStream_t stream) {
-  char msg[96];
-  if (!laplace || !a || !b || !ws) { snprintf(msg, sizeof(msg), "%s: NULL pointer", who); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
-  if (slabs < 1 || slabs > kMaxRanks || ny < slabs) { snprintf(msg, sizeof(msg), "%s: needs 1 .. %d slabs", who, kMaxRanks); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
-  if (ny % slabs != 0) {                                      // (the plan's refusal, with the rule)
-    const MgSlabPlan sp = mg_slab_plan(nx, ny, slabs, opt(OPT_MG_SLAB_GATHER_CELLS));
-    set_error_msg(sp.msg);
-    return PISO_ERR_INVALID_ARG;
+// the six entries, once per type of the cycle's values
+#define PISO_MG_SLAB_ENTRIES(SUFFIX, C)                                                                                                                          \
+  int piso_mg_pcg_solve_slab##SUFFIX(void* comm, int nx, int ny_local, int periodic_x, int periodic_y, const double* laplace_local, const double* divergence_local, \
+                                     double* x_out_local, float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps,                \
+                                     int* iterations_out, void* workspace, size_t workspace_bytes, piso_stream_t stream) {                                       \
+    return mg_slab_solve_comm<C>("piso_mg_pcg_solve_slab", comm, nx, ny_local, periodic_x, periodic_y, laplace_local, divergence_local, x_out_local, accuracy,   \
+                                 max_iterations, rank_deficient, residual_reset, sweeps, iterations_out, workspace, workspace_bytes, stream);                    \
+  }                                                                                                                                                              \
+  int piso_mg_pcg_solve_slab_emulated##SUFFIX(int slabs, int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence,        \
+                                              double* x_out, float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps,             \
+                                              int* iterations_out, void* workspace, size_t workspace_bytes, piso_stream_t stream) {                              \
+    return mg_slab_solve_emulated<C>("piso_mg_pcg_solve_slab_emulated", slabs, nx, ny, periodic_x, periodic_y, laplace, divergence, x_out, accuracy,             \
+                                     max_iterations, rank_deficient, residual_reset, sweeps, iterations_out, workspace, workspace_bytes, stream);                \
+  }                                                                                                                                                              \
+  int piso_mg_vcycle_slab##SUFFIX(void* comm, int nx, int ny_local, int periodic_x, int periodic_y, const double* laplace_local, const double* r_local,          \
+                                  double* z_local, int sweeps, void* workspace, size_t workspace_bytes, piso_stream_t stream) {                                  \
+    return mg_slab_vcycle_comm<C>("piso_mg_vcycle_slab", comm, nx, ny_local, periodic_x, periodic_y, laplace_local, r_local, z_local, sweeps, workspace,         \
+                                  workspace_bytes, stream);                                                                                                      \
+  }                                                                                                                                                              \
+  int piso_mg_vcycle_slab_emulated##SUFFIX(int slabs, int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* r_in, double* z_out,  \
+                                           int sweeps, void* workspace, size_t workspace_bytes, piso_stream_t stream) {                                          \
+    return mg_slab_vcycle_emulated<C>("piso_mg_vcycle_slab_emulated", slabs, nx, ny, periodic_x, periodic_y, laplace, r_in, z_out, sweeps, workspace,            \
+                                      workspace_bytes, stream);                                                                                                  \
+  }                                                                                                                                                              \
+  int piso_mg_level_slab##SUFFIX(void* comm, int nx, int ny_local, int periodic_x, int periodic_y, const double* laplace_local, int level, int* nx_out,          \
+                                 int* rows_out, double* laplace_level_out, void* workspace, size_t workspace_bytes, piso_stream_t stream) {                      \
+    return mg_slab_level_comm<C>("piso_mg_level_slab", comm, nx, ny_local, periodic_x, periodic_y, laplace_local, level, nx_out, rows_out, laplace_level_out,    \
+                                 workspace, workspace_bytes, stream);                                                                                            \
+  }                                                                                                                                                              \
+  int piso_mg_level_slab_emulated##SUFFIX(int slabs, int rank, int nx, int ny, int periodic_x, int periodic_y, const double* laplace, int level, int* nx_out,    \
+                                          int* rows_out, double* laplace_level_out, void* workspace, size_t workspace_bytes, piso_stream_t stream) {             \
+    return mg_slab_level_emulated<C>("piso_mg_level_slab_emulated", slabs, rank, nx, ny, periodic_x, periodic_y, laplace, level, nx_out, rows_out,               \
+                                     laplace_level_out, workspace, workspace_bytes, stream);                                                                     \
   }
-  PISO_TRY(mg_slab_begin(M, who, nx, ny / slabs, slabs, slabs, px, py, sweeps, nullptr, stream));
-  for (int r = 0; r < slabs; ++r) { M.R[r].rank = r; M.R[r].Lin = laplace + (size_t)r * (ny / slabs) * nx * 5; M.R[r].b = nullptr; }
-  return M.carve(who, ws, ws_bytes);
-}
-
-int piso_mg_pcg_solve_slab_f64(void* comm, int nx, int ny_local, int periodic_x, int periodic_y, const double* laplace_local, const double* divergence_local,
-                               double* x_out_local, float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps,
-                               int* iterations_out, void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
-  const piso::OptScope knobs;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const char* who = "piso_mg_pcg_solve_slab";
-  if (max_iterations < 1 || residual_reset < 1) { set_error_msg("piso_mg_pcg_solve_slab: max_iterations and residual_reset must be positive"); return PISO_ERR_INVALID_ARG; }
-  MgSlab M;
-  PISO_TRY(mg_slab_comm_begin(M, who, comm, nx, ny_local, periodic_x, periodic_y, laplace_local, divergence_local, x_out_local, workspace, workspace_bytes, sweeps, stream));
-  M.R[0].b = divergence_local;
-  // a refusal of the set-up is the same on every rank (all-reduced flags); whatever else fails is agreed below
-  PISO_TRY(M.solve(accuracy, max_iterations, rank_deficient ? 1 : 0, residual_reset, sweeps, iterations_out));
-  PISO_HIP_CHECK(hipMemcpyAsync(x_out_local, M.R[0].x, (size_t)nx * ny_local * sizeof(double), hipMemcpyDeviceToDevice, stream));
-  return M.finish(who);
-}
-
-int piso_mg_pcg_solve_slab_emulated_f64(int slabs, int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence, double* x_out,
-                                        float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps, int* iterations_out,
-                                        void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
-  const piso::OptScope knobs;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const char* who = "piso_mg_pcg_solve_slab_emulated";
-  if (max_iterations < 1 || residual_reset < 1) { set_error_msg("piso_mg_pcg_solve_slab_emulated: max_iterations and residual_reset must be positive"); return PISO_ERR_INVALID_ARG; }
-  MgSlab M;
-  PISO_TRY(mg_slab_emulated_begin(M, who, slabs, nx, ny, periodic_x, periodic_y, laplace, divergence, x_out, workspace, workspace_bytes, sweeps, stream));
-  const size_t n = (size_t)nx * (ny / slabs);
-  for (int r = 0; r < slabs; ++r) M.R[r].b = divergence + r * n;
-  PISO_TRY(M.solve(accuracy, max_iterations, rank_deficient ? 1 : 0, residual_reset, sweeps, iterations_out));
-  for (int r = 0; r < slabs; ++r) PISO_HIP_CHECK(hipMemcpyAsync(x_out + r * n, M.R[r].x, n * sizeof(double), hipMemcpyDeviceToDevice, stream));
-  return M.finish(who);
-}
-
-// one cycle: the rank's rows of r go into the outer residual's rows, its rows of z come out
-static int mg_slab_one_cycle(MgSlab& M, const double* const* r_rows, double* const* z_rows, int sweeps, const char* who) {
-  PISO_TRY(M.build(0));
-  const size_t n = (size_t)M.sp.d.nx[0] * M.sp.nyl;
-  for (int q = 0; q < M.nloc(); ++q) PISO_HIP_CHECK(hipMemcpyAsync(M.R[q].ro, r_rows[q], n * sizeof(double), hipMemcpyDeviceToDevice, M.s));
-  PISO_TRY(M.cycle(sweeps));
-  for (int q = 0; q < M.nloc(); ++q) PISO_HIP_CHECK(hipMemcpyAsync(z_rows[q], M.R[q].z_top, n * sizeof(double), hipMemcpyDeviceToDevice, M.s));
-  M.record(sweeps, 0, 1, 0);
-  return M.finish(who);
-}
-
-int piso_mg_vcycle_slab_f64(void* comm, int nx, int ny_local, int periodic_x, int periodic_y, const double* laplace_local, const double* r_local, double* z_local,
-                            int sweeps, void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
-  const piso::OptScope knobs;
-  MgSlab M;
-  const char* who = "piso_mg_vcycle_slab";
-  PISO_TRY(mg_slab_comm_begin(M, who, comm, nx, ny_local, periodic_x, periodic_y, laplace_local, r_local, z_local, workspace, workspace_bytes, sweeps,
-                              static_cast<hipStream_t>(stream_)));
-  return mg_slab_one_cycle(M, &r_local, &z_local, sweeps, who);
-}
-
-int piso_mg_vcycle_slab_emulated_f64(int slabs, int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* r_in, double* z_out, int sweeps,
-                                     void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
-  const piso::OptScope knobs;
-  MgSlab M;
-  const char* who = "piso_mg_vcycle_slab_emulated";
-  PISO_TRY(mg_slab_emulated_begin(M, who, slabs, nx, ny, periodic_x, periodic_y, laplace, r_in, z_out, workspace, workspace_bytes, sweeps, static_cast<hipStream_t>(stream_)));
-  const size_t n = (size_t)nx * (ny / slabs);
-  std::vector<const double*> r(slabs);
-  std::vector<double*> z(slabs);
-  for (int q = 0; q < slabs; ++q) { r[q] = r_in + q * n; z[q] = z_out + q * n; }
-  return mg_slab_one_cycle(M, r.data(), z.data(), sweeps, who);
-}
-
-// a rank's rows of a sharded level, or the whole replicated level, as [nx_out * rows_out][5] (laplace_level_out NULL: sizes only)
-static int mg_slab_level(MgSlab& M, int q, int level, int* nx_out, int* rows_out, double* out, const char* who) {
-  if (level < 0 || level >= M.sp.d.nlev) { *nx_out = 0; *rows_out = 0; set_error_msg("piso_mg_level_slab: no such level"); return PISO_ERR_INVALID_ARG; }
-  *nx_out = M.sp.d.nx[level]; *rows_out = M.sp.rows[level];
-  if (!out) return PISO_OK;
-  PISO_TRY(M.build(0));
-  const Lv& L = M.R[q].lv[level];
-  mg_export<<<mg_grid(L.n), kBlock, 0, M.s>>>(L, out);
-  return M.finish(who);
-}
-int piso_mg_level_slab_f64(void* comm, int nx, int ny_local, int periodic_x, int periodic_y, const double* laplace_local, int level, int* nx_out, int* rows_out,
-                           double* laplace_level_out, void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
-  const piso::OptScope knobs;
-  MgSlab M;
-  const char* who = "piso_mg_level_slab";
-  PISO_TRY(mg_slab_comm_begin(M, who, comm, nx, ny_local, periodic_x, periodic_y, laplace_local, nx_out, rows_out, workspace, workspace_bytes, 1,
-                              static_cast<hipStream_t>(stream_)));
-  return mg_slab_level(M, 0, level, nx_out, rows_out, laplace_level_out, who);
-}
-int piso_mg_level_slab_emulated_f64(int slabs, int rank, int nx, int ny, int periodic_x, int periodic_y, const double* laplace, int level, int* nx_out, int* rows_out,
-                                    double* laplace_level_out, void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
-  const piso::OptScope knobs;
-  MgSlab M;
-  const char* who = "piso_mg_level_slab_emulated";
-  PISO_TRY(mg_slab_emulated_begin(M, who, slabs, nx, ny, periodic_x, periodic_y, laplace, nx_out, rows_out, workspace, workspace_bytes, 1, static_cast<hipStream_t>(stream_)));
-  if (rank < 0 || rank >= slabs) { set_error_msg("piso_mg_level_slab_emulated: no such rank"); return PISO_ERR_INVALID_ARG; }
-  return mg_slab_level(M, rank, level, nx_out, rows_out, laplace_level_out, who);
-}
+PISO_MG_SLAB_ENTRIES(_f64, double)
+PISO_MG_SLAB_ENTRIES(_c32_f64, float)
+#undef PISO_MG_SLAB_ENTRIES
 
 int piso_mg_last_dispatch(int* out, int capacity) {
   const int n = tl_mg_dispatch_n < capacity ? tl_mg_dispatch_n : capacity;

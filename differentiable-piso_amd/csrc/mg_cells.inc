@@ -1,5 +1,5 @@
 // The per-cell code of the multigrid that looks at a cell's NEIGHBOURS or at the coarse rows above it - the single statement of that
-// arithmetic, included three times by mg.hip:
+// arithmetic, included four times by mg.hip:
 //   * for the WHOLE grid (wrap arithmetic on both axes; the macros expand to the expressions this code has always had, token for token),
 //   * for a rank's SLAB of a sharded level (mg_slab.h, GeoSlab g): the arrays hold the rank's rows plus one halo row below (row -1) and
 //     one above (row L.ny), so the y-neighbours are the rows below and above in storage - no wrap; only the coarse row of a REPLICATED
@@ -7,6 +7,8 @@
 //   * for the float32 cycle (mg_f32.h): the whole grid's geometry with MG_REAL float, MG_LV LvF; MG_CYCLE_F32 leaves out what only the
 //     fp64 outer iteration needs (set-up of level 0, constant mode); mg_residual and mg_direction become the mixed instantiations that
 //     emit fl32(r) (MG_R32_PARAM / MG_R32_STORE) and read a float z; the (r, z) partial multiplies the DOUBLE r (MG_RDOT*).
+//   * for the float32 cycle on a rank's slab (mg_slab_f32.h): MG_REAL float with GeoSlab - the scalar slab kernels' passes, the coarsening and
+//     the mixed residual / direction of a sharded level.
 // MG_REAL / MG_LV: the type of the cycle's values and of its level struct (double / Lv in the first two inclusions, token for token what
 // the code had).  MG_WHOLE_GRID adds the export, the per-level cycle kernels and the one-workgroup tail.
 // MG_N(name) names a function; MG_GEO_PARAM is the slab's trailing parameter; MG_NB the neighbours; MG_JS / MG_JN / MG_EROW the fine rows

@@ -20,12 +20,6 @@
 
 namespace piso {
 
-struct LvF {
-  int nx, ny, n, per_x, per_y;
-  float* c[5];         // S, W, C, E, N
-  float* dinv;         // fl32(kOmega / diag), 0 on absent cells
-};
-
 #define MG_N(name) name##_f32
 #define MG_REAL float
 #define MG_LV LvF
@@ -126,134 +120,15 @@ __device__ __forceinline__ Quad quad_at(int row, int iq, int nx, int ny) {
   return q;
 }
 
-// sweeps 1 and 2 from a zero guess (ph_pre2)
-__global__ __launch_bounds__(kBlock) void mg_pre2_f32x4(LvF L, const float* r, float* z, const MgState* st) {
-  if (st->done) return;
-  const int nxq = L.nx >> 2, nq = nxq * L.ny;
-  for (int base = blockIdx.x * blockDim.x; base < nq; base += gridDim.x * blockDim.x) {      // (uniform trip count per wave: the lanes exchange values)
-    const int qd = base + (int)threadIdx.x;
-    const bool act = qd < nq;
-    const int qq = act ? qd : nq - 1;                                                           // an idle lane redoes the last quad and stores nothing
-    const int row = qq / nxq;
-    const Quad q = quad_at(row, qq - row * nxq, L.nx, L.ny);
-    float cf[5][4], di[4], rc[4], z1[4], zs[4], zn[4], a[4], b[4], out[4];
-#pragma unroll
-    for (int s = 0; s < 5; ++s) ld4(L.c[s] + q.c0, cf[s]);
-    ld4(L.dinv + q.c0, di); ld4(r + q.c0, rc);
-    ld4(L.dinv + q.cs, a); ld4(r + q.cs, b);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) zs[k] = a[k] * b[k];
-    ld4(L.dinv + q.cn, a); ld4(r + q.cn, b);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { zn[k] = a[k] * b[k]; z1[k] = di[k] * rc[k]; }
-    float zw = __shfl_up(z1[3], 1, kWave), ze = __shfl_down(z1[0], 1, kWave);
-    if (!q.lane_w) zw = L.dinv[q.cw] * r[q.cw];
-    if (!q.lane_e) ze = L.dinv[q.ce] * r[q.ce];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float vw = k > 0 ? z1[k > 0 ? k - 1 : 0] : zw, ve = k < 3 ? z1[k < 3 ? k + 1 : 3] : ze;
-      const float az = stencil_sum<float>([&](int s) { return cf[s][k]; }, zs[k], vw, z1[k], ve, zn[k]);
-      out[k] = pre2_out(di[k], rc[k], z1[k], az);
-    }
-    if (act) st4(z + q.c0, out);
-  }
-}
-
-// one sweep (ph_jac); HAS_E: the coarse correction is added first; RZ: the block's part of (rd, zout) in double
-template <bool HAS_E, bool RZ>
-__global__ __launch_bounds__(kBlock) void mg_jacobi_f32x4(LvF L, const float* r, const float* zin, float* zout, const float* e, int nxc, double* part_rz,
-                                                          const MgState* st, const double* rd) {
-  if (st->done) return;
-  __shared__ double smem[16];
-  const int nxq = L.nx >> 2, nq = nxq * L.ny;
-  double acc = 0;
-  for (int base = blockIdx.x * blockDim.x; base < nq; base += gridDim.x * blockDim.x) {
-    const int qd = base + (int)threadIdx.x;
-    const bool act = qd < nq;
-    const int qq = act ? qd : nq - 1;
-    const int row = qq / nxq;
-    const Quad q = quad_at(row, qq - row * nxq, L.nx, L.ny);
-    float cf[5][4], di[4], rc[4], vc[4], vs[4], vn[4], zo[4];
-#pragma unroll
-    for (int s = 0; s < 5; ++s) ld4(L.c[s] + q.c0, cf[s]);
-    ld4(L.dinv + q.c0, di); ld4(r + q.c0, rc);
-    ld4(zin + q.c0, vc); ld4(zin + q.cs, vs); ld4(zin + q.cn, vn);
-    float vw = 0, ve = 0;
-    if (HAS_E) {
-      const int js = q.j > 0 ? q.j - 1 : L.ny - 1, jn = q.j < L.ny - 1 ? q.j + 1 : 0;
-      const int col = q.i0 >> 1;                                                                // (even: the two coarse cells above the quad are one 8-byte load)
-      const float2 ec = *reinterpret_cast<const float2*>(e + (q.j >> 1) * nxc + col);
-      const float2 es = *reinterpret_cast<const float2*>(e + (js >> 1) * nxc + col);
-      const float2 en = *reinterpret_cast<const float2*>(e + (jn >> 1) * nxc + col);
-      float ds[4], dn[4];
-      ld4(L.dinv + q.cs, ds); ld4(L.dinv + q.cn, dn);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (ds[k] != 0) vs[k] += k < 2 ? es.x : es.y;
-        if (di[k] != 0) vc[k] += k < 2 ? ec.x : ec.y;
-        if (dn[k] != 0) vn[k] += k < 2 ? en.x : en.y;
-      }
-    }
-    vw = __shfl_up(vc[3], 1, kWave); ve = __shfl_down(vc[0], 1, kWave);
-    if (!q.lane_w) {
-      vw = zin[q.cw];
-      if (HAS_E) { const int iw = q.i0 > 0 ? q.i0 - 1 : L.nx - 1; if (L.dinv[q.cw] != 0) vw += e[(q.j >> 1) * nxc + (iw >> 1)]; }
-    }
-    if (!q.lane_e) {
-      ve = zin[q.ce];
-      if (HAS_E) { const int ie = q.i0 + 4 < L.nx ? q.i0 + 4 : 0; if (L.dinv[q.ce] != 0) ve += e[(q.j >> 1) * nxc + (ie >> 1)]; }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float w = k > 0 ? vc[k > 0 ? k - 1 : 0] : vw, ee = k < 3 ? vc[k < 3 ? k + 1 : 3] : ve;
-      zo[k] = di[k] != 0 ? jac_out(di[k], rc[k], vc[k], stencil_sum<float>([&](int s) { return cf[s][k]; }, vs[k], w, vc[k], ee, vn[k])) : 0.0f;
-    }
-    if (act) {
-      st4(zout + q.c0, zo);
-      if (RZ) {
-        const double2 r01 = *reinterpret_cast<const double2*>(rd + q.c0), r23 = *reinterpret_cast<const double2*>(rd + q.c0 + 2);
-        acc += r01.x * (double)zo[0]; acc += r01.y * (double)zo[1]; acc += r23.x * (double)zo[2]; acc += r23.y * (double)zo[3];
-      }
-    }
-  }
-  if (RZ) {
-    acc = mg_block_sum(acc, smem);
-    if (threadIdx.x == 0) part_rz[blockIdx.x] = acc;
-  }
-}
-
-// rc = P^T (r - A z) on the present cells (ph_restrict): a thread owns four columns of the fine rows 2J, 2J + 1 = two coarse cells
-__global__ __launch_bounds__(kBlock) void mg_restrict_f32x4(LvF L, const float* r, const float* z, float* rcoarse, int nxc, int nyc, const MgState* st) {
-  if (st->done) return;
-  const int nxq = L.nx >> 2, nq = nxq * nyc;
-  for (int base = blockIdx.x * blockDim.x; base < nq; base += gridDim.x * blockDim.x) {
-    const int qd = base + (int)threadIdx.x;
-    const bool act = qd < nq;
-    const int qq = act ? qd : nq - 1;
-    const int J = qq / nxq, iq = qq - J * nxq;
-    float s[2] = {0.0f, 0.0f};
-#pragma unroll
-    for (int dj = 0; dj < 2; ++dj) {
-      const bool have = 2 * J + dj < L.ny;                                                      // (odd ny: the last coarse row has one fine row)
-      const Quad q = quad_at(have ? 2 * J + dj : 2 * J, iq, L.nx, L.ny);                        // (every lane takes part in the exchange)
-      float cf[5][4], di[4], rc[4], zc[4], zs[4], zn[4];
-#pragma unroll
-      for (int t = 0; t < 5; ++t) ld4(L.c[t] + q.c0, cf[t]);
-      ld4(L.dinv + q.c0, di); ld4(r + q.c0, rc);
-      ld4(z + q.c0, zc); ld4(z + q.cs, zs); ld4(z + q.cn, zn);
-      float zw = __shfl_up(zc[3], 1, kWave), ze = __shfl_down(zc[0], 1, kWave);
-      if (!q.lane_w) zw = z[q.cw];
-      if (!q.lane_e) ze = z[q.ce];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float w = k > 0 ? zc[k > 0 ? k - 1 : 0] : zw, ee = k < 3 ? zc[k < 3 ? k + 1 : 3] : ze;
-        const float term = restrict_term(rc[k], stencil_sum<float>([&](int t) { return cf[t][k]; }, zs[k], w, zc[k], ee, zn[k]));
-        if (have && di[k] != 0) s[k >> 1] += term;
-      }
-    }
-    if (act) *reinterpret_cast<float2*>(rcoarse + J * nxc + (iq << 1)) = make_float2(s[0], s[1]);
-  }
-}
+// (mg_pre2_f32x4, mg_jacobi_f32x4<HAS_E, RZ>, mg_restrict_f32x4: mg_quads.inc, whole grid; mg_slab_f32.h includes it again for a rank's slab)
+#define MG_N(stem) stem##_f32x4
+#define MG_GEO_PARAM
+#define MG_QUAD_AT(row, iq, nx, ny) quad_at(row, iq, nx, ny)
+#define MG_JS(j, ny) j > 0 ? j - 1 : ny - 1
+#define MG_JN(j, ny) j < ny - 1 ? j + 1 : 0
+#define MG_EROW(j) (j >> 1)
+#include "mg_quads.inc"
+#include "mg_cells_undef.inc"
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------------
 struct MgPlanF {
@@ -332,12 +207,13 @@ struct MgRunF {
     return cur;
   }
   // z = M^-1 r0 (mg_cycle of mg.hip in float32); rd: the outer residual in double - the partials of (rd, z) are left in P.part_rz
-  float* cycle(const float* r0, const double* rd, int* n_rz) {
+  // (l0: the level r0 lives on - 0, or the first replicated level of a slab solve, as mg_cycle has it)
+  float* cycle(const float* r0, const double* rd, int* n_rz, int l0 = 0) {
     const int end = use_tail ? P.tail_first : P.nlev - 1;
     float* zc[kMgMaxLevels];
     vec_mask = 0;
-    for (int l = 0; l < end; ++l) {
-      const float* r = l == 0 ? r0 : P.r[l];
+    for (int l = l0; l < end; ++l) {
+      const float* r = l == l0 ? r0 : P.r[l];
       const bool x4 = quads(l);
       if (x4) vec_mask |= 1 << l;
       zc[l] = first_sweeps(l, x4, r, nu);
@@ -345,8 +221,8 @@ struct MgRunF {
       if (x4) mg_restrict_f32x4<<<mg_grid((P.lv[l].nx >> 2) * C.ny), kBlock, 0, stream>>>(P.lv[l], r, zc[l], P.r[l + 1], C.nx, C.ny, P.st);
       else mg_restrict_f32<<<mg_grid(C.n), kBlock, 0, stream>>>(P.lv[l], r, zc[l], P.r[l + 1], C.nx, C.ny, P.st);
     }
-    const float* rend = end == 0 ? r0 : P.r[end];
-    const double* rd_end = end == 0 ? rd : nullptr;
+    const float* rend = end == l0 ? r0 : P.r[end];
+    const double* rd_end = end == l0 ? rd : nullptr;
     if (use_tail) {
       MgTail_f32 T;
       T.nlev = P.nlev - end;
@@ -361,19 +237,19 @@ struct MgRunF {
       *n_rz = jacobi(end, false, rend, cur, nxt, nullptr, rd_end);
       zc[end] = nxt;
     }
-    for (int l = end - 1; l >= 0; --l) {
-      const float* r = l == 0 ? r0 : P.r[l];
+    for (int l = end - 1; l >= l0; --l) {
+      const float* r = l == l0 ? r0 : P.r[l];
       const bool x4 = quads(l);
       float* cur = zc[l];
       for (int s = 0; s < nu; ++s) {
         float* nxt = cur == P.z[l] ? P.t[l] : P.z[l];
-        const int g = jacobi(l, x4, r, cur, nxt, s == 0 ? zc[l + 1] : nullptr, (l == 0 && s == nu - 1) ? rd : nullptr);
-        if (l == 0) *n_rz = g;
+        const int g = jacobi(l, x4, r, cur, nxt, s == 0 ? zc[l + 1] : nullptr, (l == l0 && s == nu - 1) ? rd : nullptr);
+        if (l == l0) *n_rz = g;
         cur = nxt;
       }
       zc[l] = cur;
     }
-    return zc[0];
+    return zc[l0];
   }
 };
 

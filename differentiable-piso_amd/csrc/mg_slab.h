@@ -12,26 +12,15 @@
 // every global sum from per-rank fixed-order partials by comm_allreduce_f64 (bitwise the same on every rank: every rank takes the same
 // decisions), the rows of level g and the ranks' maxima of |r| by comm_allgather_f64 (the check kernel takes nanmax over them).
 // One driver over a vector of per-rank contexts and a link: the communicator link has one context, the loopback link V virtual ranks
-// on one device whose rows it copies - no mailbox - so that one process can test every cut.
+// on one device whose rows it copies - no mailbox - so that one process can test every cut.  The driver is ONE text over the type C of the
+// cycle's values, MgSlabT<C>, with its launches in MgSlabOps<C>: MgSlab = MgSlabT<double> is this solver, MgSlabT<float> runs the float32
+// cycle of mg_f32.h on the same plan under the same fp64 outer iteration (mg_slab_f32.h).
 #pragma once
 
 namespace piso {
 
-constexpr int kMgSlabG = 16;           // doubles of a rank's collective buffer: [0] (r, z), [1] (p, q), [2] max|r|, [3] sum(x), [4 .. 8] set-up
-
-struct MgSlabRank {
-  int rank;
-  const double *Lin, *b;               // the rank's rows of the caller's matrix / right-hand side (b NULL: hierarchy or cycle only)
-  Lv lv[kMgMaxLevels];                 // l < g: the rank's rows (pointers at owned row 0, halo rows at -1 and ny); l >= g: the whole level
-  double *r[kMgMaxLevels], *z[kMgMaxLevels], *t[kMgMaxLevels];
-  Lv chunk;                            // the rank's rows of level g, before the gather
-  double* rchunk;
-  double *ro, *zo;                     // outer r (= r[0] where level 0 is sharded) and, g = 0, the rank's rows of z; both with halo rows
-  double *p[2], *x, *q;                // p, x with halo rows
-  double *parts, *part_rz, *part_pq, *part_max, *scal, *gmax, *g;
-  MgState* st;
-  double* z_top;                       // where the last cycle left the rank's z (halo rows filled)
-};
+// (MgSlabRankT<C>, what a rank holds, and mg_slab_carve, its workspace: mg_slab_carve.h - host code a driver can walk)
+typedef MgSlabRankT<double> MgSlabRank;
 
 // ---- slab instances of the per-cell code (mg_cells.inc a second time) ------------------------------------------------------------------------
 struct GeoSlab {
@@ -174,7 +163,12 @@ __global__ void mg_loop_allreduce(double* base, int world, int count) {
   for (int r = 0; r < world; ++r) base[(size_t)r * kMgSlabG + q] = s;
 }
 
-// ---- the link: exchange the halo rows of one array, all-reduce, all-gather -----------------------------------------------------------------
+
+// ---- the link: exchange the halo rows of one array, all-reduce, all-gather (T: double, or the float rows of the float32 cycle) ---------------
+inline int comm_rows(PisoComm* pc, bool per, double* row0, int nx, int rows, hipStream_t s) { return comm_exchange_rows(pc, per, row0, nx, rows, s); }
+inline int comm_rows(PisoComm* pc, bool per, float* row0, int nx, int rows, hipStream_t s) { return comm_exchange_rows_f32(pc, per, row0, nx, rows, s); }
+inline int comm_gather(PisoComm* pc, const double* src, double* dst, size_t count, hipStream_t s) { return comm_allgather_f64(pc, src, dst, count, s); }
+inline int comm_gather(PisoComm* pc, const float* src, float* dst, size_t count, hipStream_t s) { return comm_allgather_f32(pc, src, dst, count, s); }
 struct MgLink {
   PisoComm* pc;              // NULL: loopback over the virtual ranks of R
   int world;
@@ -182,100 +176,130 @@ struct MgLink {
   hipStream_t s;
 
   // sel(rank) -> owned row 0 of an array of `rows` rows of nx cells with halo rows
-  template <typename Sel>
-  int exchange(std::vector<MgSlabRank>& R, Sel sel, int nx, int rows, bool ring = false) {
+  template <typename RK, typename Sel>
+  int exchange(std::vector<RK>& R, Sel sel, int nx, int rows, bool ring = false) {
     const bool per = periodic_y || ring;
-    if (pc) return comm_exchange_rows(pc, per, sel(R[0]), nx, rows, s);
+    if (pc) return comm_rows(pc, per, sel(R[0]), nx, rows, s);
     for (int r = 0; r < world; ++r) {
       const int lo = r > 0 ? r - 1 : (per ? world - 1 : -1), hi = r < world - 1 ? r + 1 : (per ? 0 : -1);
-      double* row0 = sel(R[r]);
-      const size_t bytes = (size_t)nx * sizeof(double);
+      auto* row0 = sel(R[r]);
+      const size_t bytes = (size_t)nx * sizeof(*row0);
       if (lo >= 0) PISO_HIP_CHECK(hipMemcpyAsync(row0 - nx, sel(R[lo]) + (size_t)(rows - 1) * nx, bytes, hipMemcpyDeviceToDevice, s));
       if (hi >= 0) PISO_HIP_CHECK(hipMemcpyAsync(row0 + (size_t)rows * nx, sel(R[hi]), bytes, hipMemcpyDeviceToDevice, s));
     }
     return PISO_OK;
   }
-  int allreduce(std::vector<MgSlabRank>& R, int off, int count) {
+  template <typename RK>
+  int allreduce(std::vector<RK>& R, int off, int count) {
     if (pc) return comm_allreduce_f64(pc, R[0].g + off, count, s);
     if (world > 1) mg_loop_allreduce<<<1, 64, 0, s>>>(R[0].g + off, world, count);
     return PISO_OK;
   }
-  template <typename Src, typename Dst>
-  int allgather(std::vector<MgSlabRank>& R, Src src, Dst dst, size_t count) {
-    if (pc) return comm_allgather_f64(pc, src(R[0]), dst(R[0]), count, s);
+  template <typename RK, typename Src, typename Dst>
+  int allgather(std::vector<RK>& R, Src src, Dst dst, size_t count) {
+    if (pc) return comm_gather(pc, src(R[0]), dst(R[0]), count, s);
     for (int q = 0; q < world; ++q)
       for (int r = 0; r < world; ++r)
-        PISO_HIP_CHECK(hipMemcpyAsync(dst(R[q]) + (size_t)r * count, src(R[r]), count * sizeof(double), hipMemcpyDeviceToDevice, s));
+        PISO_HIP_CHECK(hipMemcpyAsync(dst(R[q]) + (size_t)r * count, src(R[r]), count * sizeof(*src(R[r])), hipMemcpyDeviceToDevice, s));
     return PISO_OK;
   }
 };
 
 // ---- workspace ------------------------------------------------------------------------------------------------------------------------------
-// one rank's share (the same walk sizes it against an arena without memory)
-static bool mg_slab_carve(const MgSlabPlan& sp, int per_x, int per_y, Arena& ar, MgSlabRank& k) {
-  const MgDims& d = sp.d;
-  for (int l = 0; l < d.nlev; ++l) {
-    Lv& L = k.lv[l];
-    const bool sharded = l < sp.g;
-    L.nx = d.nx[l]; L.ny = sp.rows[l]; L.n = L.nx * L.ny; L.per_x = per_x; L.per_y = per_y;
-    const size_t cells = sharded ? (size_t)L.n + 2 * L.nx : (size_t)L.n, off = sharded ? L.nx : 0;
-    for (int s = 0; s < 5; ++s) L.c[s] = ar.take<double>(cells) + off;
-    L.dinv = ar.take<double>(cells) + off;
-    k.r[l] = ar.take<double>(cells) + off; k.z[l] = ar.take<double>(cells) + off; k.t[l] = ar.take<double>(cells) + off;
-  }
-  const int nxg = d.nx[sp.g], rows_g = d.ny[sp.g] / sp.world;      // (ny_g = ny >> g exactly: nyl % 2^g == 0)
-  k.chunk.nx = nxg; k.chunk.ny = rows_g; k.chunk.n = nxg * rows_g; k.chunk.per_x = per_x; k.chunk.per_y = per_y;
-  for (int s = 0; s < 5; ++s) k.chunk.c[s] = ar.take<double>(k.chunk.n);
-  k.chunk.dinv = ar.take<double>(k.chunk.n);
-  k.rchunk = ar.take<double>(k.chunk.n);
-  const int nx = d.nx[0];
-  const size_t n0 = (size_t)nx * sp.nyl, nh0 = n0 + 2 * nx;
-  if (sp.g > 0) { k.ro = k.r[0]; k.zo = nullptr; }
-  else { k.ro = ar.take<double>(nh0) + nx; k.zo = ar.take<double>(nh0) + nx; }
-  k.p[0] = ar.take<double>(nh0) + nx; k.p[1] = ar.take<double>(nh0) + nx; k.x = ar.take<double>(nh0) + nx;
-  k.q = ar.take<double>(n0);
-  k.parts = ar.take<double>(4 * kMgGrid);
-  k.part_rz = ar.take<double>(kMgGrid); k.part_pq = ar.take<double>(kMgGrid); k.part_max = ar.take<double>(kMgGrid);
-  k.scal = ar.take<double>(SC_COUNT_MG);
-  k.gmax = ar.take<double>(kMaxRanks);
-  k.st = ar.take<MgState>(1);
-  return ar.ok();
-}
+template <typename C>
 static size_t mg_slab_rank_bytes(const MgSlabPlan& sp) {
   Arena ar(reinterpret_cast<void*>(256), ~(size_t)0);
-  MgSlabRank k;
+  MgSlabRankT<C> k;
   mg_slab_carve(sp, 0, 0, ar, k);
   return align_up(ar.used, 256);
 }
 static size_t mg_slab_g_bytes(int local_ranks) { return align_up((size_t)local_ranks * kMgSlabG * sizeof(double), 256); }
 
-// ---- the driver ------------------------------------------------------------------------------------------------------------------------------
-struct MgSlab {
-  std::vector<MgSlabRank> R;
-  MgLink link;
-  MgSlabPlan sp;
-  int per_x, per_y;
-  hipStream_t s;
-  bool use_tail;
-
-  int nloc() const { return (int)R.size(); }
-  GeoSlab geo(const MgSlabRank& k, int l) const {
-    GeoSlab g;
-    g.row0 = k.rank * (l == 0 ? sp.nyl : sp.rows[l]); g.nyg = sp.d.ny[l]; g.coarse_global = (l + 1 >= sp.g) ? 1 : 0; g.dg = nullptr; g.ncells = (double)sp.d.nx[0] * sp.d.ny[0];
-    return g;
+// ---- what the driver launches, by the type of the cycle's values (float: mg_slab_f32.h) ---------------------------------------------------------
+template <typename C> struct MgSlabOps;
+template <>
+struct MgSlabOps<double> {
+  typedef MgSlabRank RK;
+  static constexpr bool kRunsG0 = true;
+  static Lv& outer(RK& k, int g) { return g > 0 ? k.lv[0] : k.chunk; }                  // the fp64 level 0 the set-up writes (g = 0: the chunk IS the rank's rows of level 0)
+  static void level0(RK&, hipStream_t) {}
+  static void zero_halos(RK& k, int l, hipStream_t s) {
+    MgHalos h{9, {k.lv[l].c[0], k.lv[l].c[1], k.lv[l].c[2], k.lv[l].c[3], k.lv[l].c[4], k.lv[l].dinv, k.r[l], k.z[l], k.t[l]}};
+    mg_slab_zero_halos<<<grid_for(k.lv[l].nx, kBlock, 64), kBlock, 0, s>>>(h, k.lv[l].nx, k.lv[l].n);
   }
-  // the view mg_cycle takes of a rank's replicated levels
-  MgPlan rep(const MgSlabRank& k) const {
+  static void coarsen_slab(const Lv& F, const Lv& Cc, const GeoSlab& g, hipStream_t s) { mg_coarsen_slab<<<mg_grid(Cc.n), kBlock, 0, s>>>(F, Cc, g); }
+  static void coarsen(const Lv& F, const Lv& Cc, hipStream_t s) { mg_coarsen<<<mg_grid(Cc.n), kBlock, 0, s>>>(F, Cc); }
+  static bool quads(const Lv&) { return false; }
+  // the first sweep (nu 1) or the first two (ph_pre2) from a zero guess
+  static void pre(const Lv& L, const double* r, double* z, const MgState* st, const GeoSlab& g, int nu, bool, hipStream_t s) {
+    if (nu >= 2) mg_pre2_slab<<<mg_grid(L.n), kBlock, 0, s>>>(L, r, z, st, g);
+    else mg_pre1<<<mg_grid(L.n), kBlock, 0, s>>>(L, r, z, st);
+  }
+  // one sweep; returns the number of (r, z) partials (part_rz given); rd: the outer residual (the float32 cycle's other factor)
+  static int jacobi(const Lv& L, const double* r, const double* zin, double* zout, const double* e, int nxc, double* part_rz, const MgState* st, const GeoSlab& g,
+                    bool, const double*, hipStream_t s) {
+    const int gl = mg_grid(L.n);
+    mg_jacobi_slab<<<gl, kBlock, 0, s>>>(L, r, zin, zout, e, nxc, part_rz, st, g);
+    return gl;
+  }
+  static void restrict_to(const Lv& L, const double* r, const double* z, double* rc, int nxc, int nyc, const MgState* st, const GeoSlab& g, bool, hipStream_t s) {
+    mg_restrict_slab<<<mg_grid(nxc * nyc), kBlock, 0, s>>>(L, r, z, rc, nxc, nyc, st, g);
+  }
+  // levels g .. coarsest on a rank's replicated copy, as the one-GPU plan runs them
+  static double* replicated(const MgSlabPlan& sp, bool use_tail, bool, RK& k, int nu, int*, hipStream_t s) {
     MgPlan P;
     P.nlev = sp.d.nlev; P.tail_first = sp.tail_first;
     for (int l = 0; l < P.nlev; ++l) { P.lv[l] = k.lv[l]; P.r[l] = k.r[l]; P.z[l] = k.z[l]; P.t[l] = k.t[l]; }
     P.part_rz = k.part_rz; P.st = k.st;
-    return P;
+    int n_rz = 0;
+    return mg_cycle(P, k.r[sp.g], nu, use_tail, &n_rz, s, sp.g);
   }
+  static const double* gather_src(RK& k, int g) { return g > 0 ? k.rchunk : k.ro; }
+  static void init(const Lv& L0, RK& k, int g0, hipStream_t s) { mg_init<<<g0, kBlock, 0, s>>>(L0, k.b, k.x, k.ro, k.scal); }
+  static void residual(const Lv& L0, RK& k, int g0, const GeoSlab& g, hipStream_t s) { mg_residual_slab<<<g0, kBlock, 0, s>>>(L0, k.b, k.x, k.ro, k.scal, k.st, g); }
+  static void direction(const Lv& L0, RK& k, int g0, int it, int restart, const GeoSlab& g, hipStream_t s) {
+    mg_direction_slab<<<g0, kBlock, 0, s>>>(L0, k.z_top, k.p[it & 1], k.p[(it + 1) & 1], k.q, k.g, 1, k.scal, it, restart, k.part_pq, k.st, g);
+  }
+  static void update(int n0, RK& k, int g0, int it, hipStream_t s) {
+    mg_update<<<g0, kBlock, 0, s>>>(n0, k.x, k.ro, k.p[(it + 1) & 1], k.q, k.scal, it, k.g + 1, 1, k.part_max, k.st);
+  }
+  static void export_level(const Lv& L, double* out, hipStream_t s) { mg_export<<<mg_grid(L.n), kBlock, 0, s>>>(L, out); }
+  // one cycle from the caller's rows of r, its rows of z out
+  static int load_r(RK& k, const double* rows, size_t n, hipStream_t s) {
+    PISO_HIP_CHECK(hipMemcpyAsync(k.ro, rows, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    return PISO_OK;
+  }
+  static int store_z(RK& k, double* rows, size_t n, hipStream_t s) {
+    PISO_HIP_CHECK(hipMemcpyAsync(rows, k.z_top, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    return PISO_OK;
+  }
+};
+
+// ---- the driver ------------------------------------------------------------------------------------------------------------------------------
+template <typename C>
+struct MgSlabT {
+  typedef MgSlabRankT<C> RK;
+  typedef MgSlabOps<C> Ops;
+  typedef typename RK::Level Level;
+  std::vector<RK> R;
+  MgLink link;
+  MgSlabPlan sp;
+  int per_x, per_y;
+  hipStream_t s;
+  bool use_tail, vec;
+  int vec_mask = 0;
+
+  int nloc() const { return (int)R.size(); }
+  GeoSlab geo(const RK& k, int l) const {
+    GeoSlab g;
+    g.row0 = k.rank * (l == 0 ? sp.nyl : sp.rows[l]); g.nyg = sp.d.ny[l]; g.coarse_global = (l + 1 >= sp.g) ? 1 : 0; g.dg = nullptr; g.ncells = (double)sp.d.nx[0] * sp.d.ny[0];
+    return g;
+  }
+  bool quads(const RK& k, int l) const { return vec && Ops::quads(k.lv[l]); }
 
   // carve `ws` (the g buffers of all local ranks first, contiguous: the loopback all-reduce walks them)
   int carve(const char* who, void* ws, size_t bytes) {
-    const size_t per_rank = mg_slab_rank_bytes(sp), gb = mg_slab_g_bytes(nloc());
+    const size_t per_rank = mg_slab_rank_bytes<C>(sp), gb = mg_slab_g_bytes(nloc());
     char msg[96];
     if (bytes < gb + per_rank * nloc()) { snprintf(msg, sizeof(msg), "%s: workspace too small", who); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
     PISO_HIP_CHECK(hipMemsetAsync(ws, 0, gb, s));
@@ -292,29 +316,26 @@ struct MgSlab {
     MgState* pinned = nullptr;
     PISO_TRY(mg_pinned(&pinned));
     const int nx = sp.d.nx[0], n0 = nx * sp.nyl, g0 = mg_grid(n0);
-    for (MgSlabRank& k : R) {
+    for (RK& k : R) {
       PISO_HIP_CHECK(hipMemsetAsync(k.st, 0, sizeof(MgState), s));
-      for (int l = 0; l < sp.g; ++l) {
-        MgHalos h{9, {k.lv[l].c[0], k.lv[l].c[1], k.lv[l].c[2], k.lv[l].c[3], k.lv[l].c[4], k.lv[l].dinv, k.r[l], k.z[l], k.t[l]}};
-        mg_slab_zero_halos<<<grid_for(k.lv[l].nx, kBlock, 64), kBlock, 0, s>>>(h, k.lv[l].nx, k.lv[l].n);
-      }
+      for (int l = 0; l < sp.g; ++l) Ops::zero_halos(k, l, s);
       MgHalos h{3, {k.p[0], k.p[1], k.x}};
-      if (sp.g == 0) { h.a[3] = k.ro; h.a[4] = k.zo; h.count = 5; }
+      if (sp.g == 0) { h.a[3] = k.ro; h.a[4] = reinterpret_cast<double*>(k.zo); h.count = 5; }      // (g = 0 is the fp64 cycle's alone)
       mg_slab_zero_halos<<<grid_for(nx, kBlock, 64), kBlock, 0, s>>>(h, nx, n0);
       mg_slab_diag<<<g0, kBlock, 0, s>>>(k.Lin, k.p[0], n0);          // (p[0] is free until the first direction)
     }
     // (around the ring whatever the border: the whole-grid set-up looks at the wrapped row's diagonal there too)
-    PISO_TRY(link.exchange(R, [](MgSlabRank& k) { return k.p[0]; }, nx, sp.nyl, true));
-    for (MgSlabRank& k : R) {
+    PISO_TRY(link.exchange(R, [](RK& k) { return k.p[0]; }, nx, sp.nyl, true));
+    for (RK& k : R) {
       GeoSlab g = geo(k, 0);
       g.dg = k.p[0];
-      Lv L0 = sp.g > 0 ? k.lv[0] : k.chunk;
-      mg_setup0_slab<<<g0, kBlock, 0, s>>>(k.Lin, L0, k.b, k.parts, k.st, g);
+      mg_setup0_slab<<<g0, kBlock, 0, s>>>(k.Lin, Ops::outer(k, sp.g), k.b, k.parts, k.st, g);
+      Ops::level0(k, s);
       mg_slab_setup_collapse<<<1, kBlock, 0, s>>>(k.parts, g0, k.st, k.g);
     }
     PISO_TRY(link.allreduce(R, 4, 5));
-    PISO_TRY(link.allgather(R, [](MgSlabRank& k) { return k.g + 9; }, [](MgSlabRank& k) { return k.gmax; }, 1));
-    for (MgSlabRank& k : R) {
+    PISO_TRY(link.allgather(R, [](RK& k) { return k.g + 9; }, [](RK& k) { return k.gmax; }, 1));
+    for (RK& k : R) {
       mg_slab_setup_spread<<<1, 64, 0, s>>>(k.g, k.gmax, sp.world, k.parts, k.st);
       mg_setup_fin<<<1, kBlock, 0, s>>>(k.parts, sp.world, k.scal, rank_deficient, n0 * sp.world, k.st);
       MgHalos h{2, {k.p[0], k.p[1]}};                                 // (the diagonals' halo rows: p must start from zero ones)
@@ -322,19 +343,16 @@ struct MgSlab {
     }
     // the sharded levels: halo rows of the diagonal (coarsening reads the neighbours' presence) and of dinv, once per solve
     for (int l = 0; l < sp.g; ++l) {
-      PISO_TRY(link.exchange(R, [l](MgSlabRank& k) { return k.lv[l].c[2]; }, sp.d.nx[l], sp.rows[l]));
-      PISO_TRY(link.exchange(R, [l](MgSlabRank& k) { return k.lv[l].dinv; }, sp.d.nx[l], sp.rows[l]));
-      for (MgSlabRank& k : R) {
-        const Lv& Cc = l + 1 < sp.g ? k.lv[l + 1] : k.chunk;
-        mg_coarsen_slab<<<mg_grid(Cc.n), kBlock, 0, s>>>(k.lv[l], Cc, geo(k, l));
-      }
+      PISO_TRY(link.exchange(R, [l](RK& k) { return k.lv[l].c[2]; }, sp.d.nx[l], sp.rows[l]));
+      PISO_TRY(link.exchange(R, [l](RK& k) { return k.lv[l].dinv; }, sp.d.nx[l], sp.rows[l]));
+      for (RK& k : R) Ops::coarsen_slab(k.lv[l], l + 1 < sp.g ? k.lv[l + 1] : k.chunk, geo(k, l), s);
     }
     // level g: the ranks' rows, all-gathered
     for (int a = 0; a < 6; ++a)
-      PISO_TRY(link.allgather(R, [a](MgSlabRank& k) { return a < 5 ? k.chunk.c[a] : k.chunk.dinv; },
-                              [a, this](MgSlabRank& k) { return a < 5 ? k.lv[sp.g].c[a] : k.lv[sp.g].dinv; }, (size_t)R[0].chunk.n));
-    for (MgSlabRank& k : R)
-      for (int l = sp.g; l + 1 < sp.d.nlev; ++l) mg_coarsen<<<mg_grid(k.lv[l + 1].n), kBlock, 0, s>>>(k.lv[l], k.lv[l + 1]);
+      PISO_TRY(link.allgather(R, [a](RK& k) { return a < 5 ? k.chunk.c[a] : k.chunk.dinv; },
+                              [a, this](RK& k) { return a < 5 ? k.lv[sp.g].c[a] : k.lv[sp.g].dinv; }, (size_t)R[0].chunk.n));
+    for (RK& k : R)
+      for (int l = sp.g; l + 1 < sp.d.nlev; ++l) Ops::coarsen(k.lv[l], k.lv[l + 1], s);
     PISO_LAUNCH_CHECK();
     PISO_HIP_CHECK(hipMemcpyAsync(pinned, R[0].st, sizeof(MgState), hipMemcpyDeviceToHost, s));
     PISO_HIP_CHECK(hipStreamSynchronize(s));
@@ -358,72 +376,73 @@ struct MgSlab {
   int halo(int l, Sel sel) { return link.exchange(R, sel, sp.d.nx[l], sp.rows[l]); }
 
   // z = M^-1 r on every rank's rows: leaves R[q].z_top (halo rows filled) and the rank's part of (r, z) in g[0]
+  // (the cycle reads r[l] on sharded levels: r[0] is the outer r itself under the fp64 cycle, fl32 of it under the float32 cycle)
   int cycle(int nu) {
     const int G = sp.g, nx = sp.d.nx[0], n0 = nx * sp.nyl;
-    std::vector<std::vector<double*>> zc(nloc(), std::vector<double*>(kMgMaxLevels, nullptr));
-    auto rl = [](MgSlabRank& k, int l) { return l == 0 ? k.ro : k.r[l]; };
+    std::vector<std::vector<C*>> zc(nloc(), std::vector<C*>(kMgMaxLevels, nullptr));
+    vec_mask = 0;
     for (int l = 0; l < G; ++l) {                                       // down the sharded levels
-      const int gl = mg_grid(R[0].lv[l].n);
-      if (nu >= 2) PISO_TRY(halo(l, [&](MgSlabRank& k) { return rl(k, l); }));
+      const bool x4 = quads(R[0], l);
+      if (x4) vec_mask |= 1 << l;
+      if (nu >= 2) PISO_TRY(halo(l, [&](RK& k) { return k.r[l]; }));
       for (int q = 0; q < nloc(); ++q) {
-        MgSlabRank& k = R[q];
+        RK& k = R[q];
         zc[q][l] = k.z[l];
-        if (nu >= 2) mg_pre2_slab<<<gl, kBlock, 0, s>>>(k.lv[l], rl(k, l), k.z[l], k.st, geo(k, l));
-        else mg_pre1<<<gl, kBlock, 0, s>>>(k.lv[l], rl(k, l), k.z[l], k.st);
+        Ops::pre(k.lv[l], k.r[l], k.z[l], k.st, geo(k, l), nu, x4, s);
       }
       for (int sw = 2; sw < nu; ++sw) {
-        PISO_TRY(halo(l, [&](MgSlabRank& k) { return zc[&k - R.data()][l]; }));
+        PISO_TRY(halo(l, [&](RK& k) { return zc[&k - R.data()][l]; }));
         for (int q = 0; q < nloc(); ++q) {
-          MgSlabRank& k = R[q];
-          double* nxt = zc[q][l] == k.z[l] ? k.t[l] : k.z[l];
-          mg_jacobi_slab<<<gl, kBlock, 0, s>>>(k.lv[l], rl(k, l), zc[q][l], nxt, nullptr, 0, nullptr, k.st, geo(k, l));
+          RK& k = R[q];
+          C* nxt = zc[q][l] == k.z[l] ? k.t[l] : k.z[l];
+          Ops::jacobi(k.lv[l], k.r[l], zc[q][l], nxt, nullptr, 0, nullptr, k.st, geo(k, l), x4, nullptr, s);
           zc[q][l] = nxt;
         }
       }
-      PISO_TRY(halo(l, [&](MgSlabRank& k) { return zc[&k - R.data()][l]; }));
+      PISO_TRY(halo(l, [&](RK& k) { return zc[&k - R.data()][l]; }));
       for (int q = 0; q < nloc(); ++q) {
-        MgSlabRank& k = R[q];
-        const Lv& Cc = l + 1 < G ? k.lv[l + 1] : k.chunk;
-        mg_restrict_slab<<<mg_grid(Cc.n), kBlock, 0, s>>>(k.lv[l], rl(k, l), zc[q][l], l + 1 < G ? k.r[l + 1] : k.rchunk, Cc.nx, Cc.ny, k.st, geo(k, l));
+        RK& k = R[q];
+        const Level& Cc = l + 1 < G ? k.lv[l + 1] : k.chunk;
+        Ops::restrict_to(k.lv[l], k.r[l], zc[q][l], l + 1 < G ? k.r[l + 1] : k.rchunk, Cc.nx, Cc.ny, k.st, geo(k, l), x4, s);
       }
     }
     // level g: the ranks' rows of the residual, all-gathered; levels g .. coarsest on every rank, as the one-GPU plan runs them
-    PISO_TRY(link.allgather(R, [G](MgSlabRank& k) { return G > 0 ? k.rchunk : k.ro; }, [G](MgSlabRank& k) { return k.r[G]; }, (size_t)R[0].chunk.n));
-    std::vector<double*> zg(nloc());
-    for (int q = 0; q < nloc(); ++q) {
-      int n_rz = 0;
-      zg[q] = mg_cycle(rep(R[q]), R[q].r[G], nu, use_tail, &n_rz, s, G);
-    }
+    PISO_TRY(link.allgather(R, [G](RK& k) { return Ops::gather_src(k, G); }, [G](RK& k) { return k.r[G]; }, (size_t)R[0].chunk.n));
+    std::vector<C*> zg(nloc());
+    for (int q = 0; q < nloc(); ++q) zg[q] = Ops::replicated(sp, use_tail, vec, R[q], nu, &vec_mask, s);
     int n_rz = 0;
-    if (G == 0) {
-      n_rz = mg_grid(n0);
-      for (int q = 0; q < nloc(); ++q) {
-        MgSlabRank& k = R[q];
-        mg_slab_take_rows<<<mg_grid(n0 + 2 * nx), kBlock, 0, s>>>(zg[q], k.zo, nx, sp.nyl, k.rank * sp.nyl, sp.d.ny[0], per_y, k.st);
-        mg_slab_dot<<<n_rz, kBlock, 0, s>>>(k.ro, k.zo, n0, k.part_rz, k.st);
-        k.z_top = k.zo;
+    if constexpr (Ops::kRunsG0) {
+      if (G == 0) {
+        n_rz = mg_grid(n0);
+        for (int q = 0; q < nloc(); ++q) {
+          RK& k = R[q];
+          mg_slab_take_rows<<<mg_grid(n0 + 2 * nx), kBlock, 0, s>>>(zg[q], k.zo, nx, sp.nyl, k.rank * sp.nyl, sp.d.ny[0], per_y, k.st);
+          mg_slab_dot<<<n_rz, kBlock, 0, s>>>(k.ro, k.zo, n0, k.part_rz, k.st);
+          k.z_top = k.zo;
+        }
       }
     }
     for (int l = G - 1; l >= 0; --l) {                                  // up the sharded levels
-      const int gl = mg_grid(R[0].lv[l].n);
-      if (l + 1 < G) PISO_TRY(halo(l + 1, [&](MgSlabRank& k) { return zc[&k - R.data()][l + 1]; }));      // e of a sharded coarser level
+      const bool x4 = quads(R[0], l);
+      if (l + 1 < G) PISO_TRY(halo(l + 1, [&](RK& k) { return zc[&k - R.data()][l + 1]; }));      // e of a sharded coarser level
       for (int sw = 0; sw < nu; ++sw) {
-        if (sw > 0) PISO_TRY(halo(l, [&](MgSlabRank& k) { return zc[&k - R.data()][l]; }));               // (sweep 0: filled before the restriction)
+        if (sw > 0) PISO_TRY(halo(l, [&](RK& k) { return zc[&k - R.data()][l]; }));               // (sweep 0: filled before the restriction)
         for (int q = 0; q < nloc(); ++q) {
-          MgSlabRank& k = R[q];
-          double* nxt = zc[q][l] == k.z[l] ? k.t[l] : k.z[l];
-          const double* e = sw == 0 ? (l + 1 < G ? zc[q][l + 1] : zg[q]) : nullptr;
-          mg_jacobi_slab<<<gl, kBlock, 0, s>>>(k.lv[l], rl(k, l), zc[q][l], nxt, e, sp.d.nx[l + 1], (l == 0 && sw == nu - 1) ? k.part_rz : nullptr, k.st, geo(k, l));
+          RK& k = R[q];
+          C* nxt = zc[q][l] == k.z[l] ? k.t[l] : k.z[l];
+          const C* e = sw == 0 ? (l + 1 < G ? zc[q][l + 1] : zg[q]) : nullptr;
+          const bool last = l == 0 && sw == nu - 1;
+          const int gl = Ops::jacobi(k.lv[l], k.r[l], zc[q][l], nxt, e, sp.d.nx[l + 1], last ? k.part_rz : nullptr, k.st, geo(k, l), x4, last ? k.ro : nullptr, s);
+          if (last) n_rz = gl;
           zc[q][l] = nxt;
         }
       }
       if (l == 0) {
-        n_rz = gl;
-        PISO_TRY(halo(0, [&](MgSlabRank& k) { return zc[&k - R.data()][0]; }));                           // for the direction
+        PISO_TRY(halo(0, [&](RK& k) { return zc[&k - R.data()][0]; }));                           // for the direction
         for (int q = 0; q < nloc(); ++q) R[q].z_top = zc[q][0];
       }
     }
-    for (MgSlabRank& k : R) mg_slab_collapse<<<1, kBlock, 0, s>>>(k.part_rz, n_rz, k.g, k.st);
+    for (RK& k : R) mg_slab_collapse<<<1, kBlock, 0, s>>>(k.part_rz, n_rz, k.g, k.st);
     PISO_LAUNCH_CHECK();
     return PISO_OK;
   }
@@ -434,28 +453,27 @@ struct MgSlab {
     PISO_TRY(mg_pinned(&pinned));
     const int nx = sp.d.nx[0], n0 = nx * sp.nyl, g0 = mg_grid(n0);
     const int check_every = opt(OPT_MG_CHECK_EVERY) > 0 ? opt(OPT_MG_CHECK_EVERY) : kCheckEvery;
-    auto L0 = [&](MgSlabRank& k) { Lv L = sp.g > 0 ? k.lv[0] : k.chunk; L.nx = nx; L.ny = sp.nyl; L.n = n0; return L; };    // (g = 0: the chunk IS the rank's rows of level 0)
-    for (MgSlabRank& k : R) mg_init<<<g0, kBlock, 0, s>>>(L0(k), k.b, k.x, k.ro, k.scal);
+    auto L0 = [&](RK& k) { Lv L = Ops::outer(k, sp.g); L.nx = nx; L.ny = sp.nyl; L.n = n0; return L; };
+    for (RK& k : R) Ops::init(L0(k), k, g0, s);
     bool done = false;
     int iterations = max_iterations;
     for (int it = 0; it < max_iterations && !done; ++it) {
       const bool restart = it > 0 && (it + 1) % residual_reset == 0;
       if (restart) {
-        PISO_TRY(link.exchange(R, [](MgSlabRank& k) { return k.x; }, nx, sp.nyl));
-        for (MgSlabRank& k : R) mg_residual_slab<<<g0, kBlock, 0, s>>>(L0(k), k.b, k.x, k.ro, k.scal, k.st, geo(k, 0));
+        PISO_TRY(link.exchange(R, [](RK& k) { return k.x; }, nx, sp.nyl));
+        for (RK& k : R) Ops::residual(L0(k), k, g0, geo(k, 0), s);
       }
       PISO_TRY(cycle(sweeps));
       PISO_TRY(link.allreduce(R, 0, 1));
-      for (MgSlabRank& k : R)
-        mg_direction_slab<<<g0, kBlock, 0, s>>>(L0(k), k.z_top, k.p[it & 1], k.p[(it + 1) & 1], k.q, k.g, 1, k.scal, it, (restart || it == 0) ? 1 : 0, k.part_pq, k.st, geo(k, 0));
-      for (MgSlabRank& k : R) mg_slab_collapse<<<1, kBlock, 0, s>>>(k.part_pq, g0, k.g + 1, k.st);
+      for (RK& k : R) Ops::direction(L0(k), k, g0, it, (restart || it == 0) ? 1 : 0, geo(k, 0), s);
+      for (RK& k : R) mg_slab_collapse<<<1, kBlock, 0, s>>>(k.part_pq, g0, k.g + 1, k.st);
       PISO_TRY(link.allreduce(R, 1, 1));
-      for (MgSlabRank& k : R) {
-        mg_update<<<g0, kBlock, 0, s>>>(n0, k.x, k.ro, k.p[(it + 1) & 1], k.q, k.scal, it, k.g + 1, 1, k.part_max, k.st);
+      for (RK& k : R) {
+        Ops::update(n0, k, g0, it, s);
         mg_slab_collapse_max<<<1, kBlock, 0, s>>>(k.part_max, g0, k.g + 2, k.st);
       }
-      PISO_TRY(link.allgather(R, [](MgSlabRank& k) { return k.g + 2; }, [](MgSlabRank& k) { return k.gmax; }, 1));
-      for (MgSlabRank& k : R) mg_check<<<1, kBlock, 0, s>>>(k.gmax, sp.world, accuracy, it + 1, k.st);
+      PISO_TRY(link.allgather(R, [](RK& k) { return k.g + 2; }, [](RK& k) { return k.gmax; }, 1));
+      for (RK& k : R) mg_check<<<1, kBlock, 0, s>>>(k.gmax, sp.world, accuracy, it + 1, k.st);
       PISO_LAUNCH_CHECK();
       if ((it + 1) % check_every == 0 || it + 1 == max_iterations) {
         PISO_HIP_CHECK(hipMemcpyAsync(pinned, R[0].st, sizeof(MgState), hipMemcpyDeviceToHost, s));
@@ -464,12 +482,12 @@ struct MgSlab {
       }
     }
     if (rank_deficient) {
-      for (MgSlabRank& k : R) {
+      for (RK& k : R) {
         mg_sum_x<<<g0, kBlock, 0, s>>>(L0(k), k.x, k.parts);
         mg_slab_collapse<<<1, kBlock, 0, s>>>(k.parts, g0, k.g + 3, nullptr);
       }
       PISO_TRY(link.allreduce(R, 3, 1));
-      for (MgSlabRank& k : R) mg_finish_slab<<<g0, kBlock, 0, s>>>(L0(k), k.x, k.g + 3, 1, k.scal, geo(k, 0));
+      for (RK& k : R) mg_finish_slab<<<g0, kBlock, 0, s>>>(L0(k), k.x, k.g + 3, 1, k.scal, geo(k, 0));
       PISO_LAUNCH_CHECK();
     }
     if (iterations_out) *iterations_out = iterations;
@@ -482,7 +500,7 @@ struct MgSlab {
   void record(int sweeps, int iterations, int cycles, int recomputed) const {
     int* d = tl_mg_dispatch;
     d[MD_LEVELS] = sp.d.nlev; d[MD_TAIL_FIRST] = use_tail ? sp.tail_first : -1; d[MD_SWEEPS] = sweeps; d[MD_ITERATIONS] = iterations;
-    d[MD_CYCLES] = cycles; d[MD_RESIDUAL_RECOMPUTATIONS] = recomputed; d[MD_CYCLE_ELEM] = 8; d[MD_VEC_MASK] = 0;
+    d[MD_CYCLES] = cycles; d[MD_RESIDUAL_RECOMPUTATIONS] = recomputed; d[MD_CYCLE_ELEM] = (int)sizeof(C); d[MD_VEC_MASK] = vec_mask;
     tl_mg_dispatch_n = MD_COUNT;
   }
 
@@ -494,17 +512,26 @@ struct MgSlab {
     return PISO_OK;
   }
 };
+typedef MgSlabT<double> MgSlab;
 
-// the plan of a call: refusals are the plan's, with its message
-static int mg_slab_begin(MgSlab& M, const char* who, int nx, int nyl, int world, int local_ranks, int per_x, int per_y, int sweeps, PisoComm* pc, hipStream_t s) {
+// the plan of a call: refusals are the plan's, with its message; the float32 cycle refuses a plan that replicates the whole cycle (g = 0)
+template <typename C>
+static int mg_slab_begin(MgSlabT<C>& M, const char* who, int nx, int nyl, int world, int local_ranks, int per_x, int per_y, int sweeps, PisoComm* pc, hipStream_t s) {
   char msg[320];
   if (sweeps < 1 || sweeps > 8) { snprintf(msg, sizeof(msg), "%s: sweeps must be 1 .. 8", who); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
   if (nyl < 1 || world < 1 || world > kMaxRanks) { snprintf(msg, sizeof(msg), "%s: needs 1 .. %d ranks with at least one row each", who, kMaxRanks); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
   M.sp = mg_slab_plan(nx, nyl * world, world, opt(OPT_MG_SLAB_GATHER_CELLS));
   if (M.sp.status) { snprintf(msg, sizeof(msg), "%s: %s", who, M.sp.msg); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
+  if (!MgSlabOps<C>::kRunsG0 && M.sp.g == 0) {
+    snprintf(msg, sizeof(msg), "%s: the whole %d x %d grid is within the gather limit (g = 0), so the cycle is replicated and a float32 cycle has nothing to gain; "
+             "a solve cut into y-slabs needs cycle_dtype=torch.float64 here", who, nx, nyl * world);
+    set_error_msg(msg);
+    return PISO_ERR_INVALID_ARG;
+  }
   M.per_x = per_x ? 1 : 0; M.per_y = per_y ? 1 : 0; M.s = s;
   M.link = MgLink{pc, world, per_y != 0, s};
   M.use_tail = M.sp.tail_first >= 0 && opt(OPT_MG_TAIL) != 0;
+  M.vec = opt(OPT_MG_F32_VEC) != 0;
   M.R.resize(local_ranks);
   return PISO_OK;
 }

@@ -58,6 +58,11 @@ int comm_allreduce_i32(PisoComm* pc, int* buf, int count, hipStream_t s);
 int comm_allgather_f64(PisoComm* pc, const double* src, double* dst, size_t count, hipStream_t s);
 int comm_exchange_rows(PisoComm* pc, bool periodic_y, double* row0, int nx, int ny, hipStream_t s);
 int comm_exchange_segments(PisoComm* pc, void* vec, int dtype, const HaloMsg* m4, hipStream_t s);
+// The float rows of the float32 multigrid cycle (mg_slab_f32.h).  Peer transport: a halo row travels in the row slots of the f64 exchange,
+// the 32 bits of a float per 8-byte word (the int instance of the segment messages' kernel; nx <= row_cap), and a float of the gather is ONE tagged word of the gather
+// area {32 payload bits | epoch} (count * world <= kGatherCells); both share the sequence numbers of their f64 twins.  RCCL: ncclFloat.
+int comm_allgather_f32(PisoComm* pc, const float* src, float* dst, size_t count, hipStream_t s);
+int comm_exchange_rows_f32(PisoComm* pc, bool periodic_y, float* row0, int nx, int ny, hipStream_t s);
 int comm_agree(PisoComm* pc, const char* who, hipStream_t s, bool ring_of_one = false);
 int comm_ready(const PisoComm* pc, const char* msg);
 

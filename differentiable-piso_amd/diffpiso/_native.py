@@ -91,6 +91,11 @@ lib.piso_mg_vcycle_slab_emulated_f64.argtypes = [_i, _i, _i, _i, _i, _vp, _vp, _
 lib.piso_mg_vcycle_slab_emulated_f64.restype = _i
 lib.piso_mg_level_slab_emulated_f64.argtypes = [_i, _i, _i, _i, _i, _i, _vp, _i, _ip, _ip, _vp, _vp, _sz, _vp]
 lib.piso_mg_level_slab_emulated_f64.restype = _i
+lib.piso_mg_slab_workspace_bytes_cycle.argtypes = [_i, _i, _i, _i, _i]
+lib.piso_mg_slab_workspace_bytes_cycle.restype = _sz
+for _n in ("pcg_solve_slab", "vcycle_slab", "level_slab", "pcg_solve_slab_emulated", "vcycle_slab_emulated", "level_slab_emulated"):
+    getattr(lib, "piso_mg_%s_c32_f64" % _n).argtypes = getattr(lib, "piso_mg_%s_f64" % _n).argtypes
+    getattr(lib, "piso_mg_%s_c32_f64" % _n).restype = _i
 lib.piso_mg_last_dispatch.argtypes = [_ip, _i]
 lib.piso_mg_last_dispatch.restype = _i
 lib.piso_cg_fixed_iterations_f64.argtypes = [_i, _i, _i, _i, _vp, _vp, _vp, _i, _i, C.POINTER(C.c_float), _vp, _sz, _vp]
@@ -184,6 +189,8 @@ lib.piso_comm_exchange.argtypes = [_vp, _vp, _i, _ip, _vp]
 lib.piso_comm_exchange.restype = _i
 lib.piso_comm_allgather_f64.argtypes = [_vp, _vp, _vp, _i, _vp]
 lib.piso_comm_allgather_f64.restype = _i
+lib.piso_comm_allgather_f32.argtypes = lib.piso_comm_allgather_f64.argtypes
+lib.piso_comm_allgather_f32.restype = _i
 lib.piso_comm_check.argtypes = [_vp, _vp]
 lib.piso_comm_check.restype = _i
 lib.piso_cg_slab_workspace_bytes.argtypes = [_i, _i, _i]

@@ -306,15 +306,24 @@ def cg_solve_slab_emulated(slabs, nx, ny, per_x, per_y, L, div, accuracy, max_it
     return x, it.value
 
 
-# ---- the multigrid-preconditioned CG (solvers.mg_solve_native) on y-slabs: csrc/mg_slab.h -----------------------------------------------
-def _mg_slab_workspace(nx, nyl, world, local_ranks, device, tag):
-    nbytes = N.lib.piso_mg_slab_workspace_bytes(int(nx), int(nyl), int(world), int(local_ranks))
+# ---- the multigrid-preconditioned CG (solvers.mg_solve_native) on y-slabs: csrc/mg_slab.h, csrc/mg_slab_f32.h -----------------------------
+# cycle_dtype=torch.float32: the float32 V-cycle under the same fp64, sharded outer iteration (the *_c32_f64 entries); a plan that replicates
+# the whole cycle (g = 0) is refused there.
+def _mg_slab_fn(stem, cycle_dtype):
+    from .solvers import _mg_cycle_elem
+    return getattr(N.lib, "piso_mg_%s_%s" % (stem, "f64" if _mg_cycle_elem(cycle_dtype) == 8 else "c32_f64"))
+
+
+def _mg_slab_workspace(nx, nyl, world, local_ranks, device, tag, cycle_dtype=torch.float64):
+    from .solvers import _mg_cycle_elem
+    nbytes = N.lib.piso_mg_slab_workspace_bytes_cycle(int(nx), int(nyl), int(world), int(local_ranks), _mg_cycle_elem(cycle_dtype))
     if nbytes == 0:       # refused shape: let the entry point say why (it checks the plan before it looks at the workspace)
         nbytes = 256
     return N.workspace(nbytes, device, tag)
 
 
-def mg_solve_slab(comm, nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset, sweeps=2, gather=True):
+def mg_solve_slab(comm, nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset, sweeps=2, gather=True,
+                  cycle_dtype=torch.float64):
     """Distributed counterpart of solvers.mg_solve_native: L [ny*nx*5] and div [ny*nx] are the FULL (replicated) arrays; this rank solves
     its slab.  gather=True: every rank returns the full solution (through torch.distributed); gather=False: only its own rows."""
     assert L.dtype == torch.float64, "slab multigrid: fp64"
@@ -322,7 +331,8 @@ def mg_solve_slab(comm, nx, ny, per_x, per_y, L, div, accuracy, max_iterations, 
     nyl, off = j1 - j0, j0 * nx
     L_loc = L.reshape(-1)[off * 5:(off + nyl * nx) * 5].contiguous()
     d_loc = div.reshape(-1).to(torch.float64)[off:off + nyl * nx].contiguous()
-    x_loc, it = mg_solve_slab_local(comm, nx, nyl, per_x, per_y, L_loc, d_loc, accuracy, max_iterations, rank_deficient, residual_reset, sweeps)
+    x_loc, it = mg_solve_slab_local(comm, nx, nyl, per_x, per_y, L_loc, d_loc, accuracy, max_iterations, rank_deficient, residual_reset, sweeps,
+                                    cycle_dtype=cycle_dtype)
     if not gather or comm.world == 1:
         return x_loc, it
     import torch.distributed as dist
@@ -332,69 +342,80 @@ def mg_solve_slab(comm, nx, ny, per_x, per_y, L, div, accuracy, max_iterations, 
     return torch.cat(parts).to(d_loc.device), it
 
 
-def mg_solve_slab_local(comm, nx, nyl, per_x, per_y, L_loc, d_loc, accuracy, max_iterations, rank_deficient, residual_reset, sweeps=2):
+def mg_solve_slab_local(comm, nx, nyl, per_x, per_y, L_loc, d_loc, accuracy, max_iterations, rank_deficient, residual_reset, sweeps=2,
+                        cycle_dtype=torch.float64):
     """The same with this rank's slab only: L_loc [nyl*nx*5], d_loc [nyl*nx] (nothing is replicated) -> (its rows of x, iterations)."""
     if L_loc.dtype != torch.float64:
         raise N.PisoNativeError("the multigrid pressure solver is fp64 only; use the plain CG (cg_solve_slab) for float32")
+    fn = _mg_slab_fn("pcg_solve_slab", cycle_dtype)
     d_loc = d_loc.reshape(-1).to(torch.float64).contiguous()
     x_loc = torch.empty_like(d_loc)
-    ws = _mg_slab_workspace(nx, nyl, comm.world, 1, d_loc.device, "mg_slab")
+    ws = _mg_slab_workspace(nx, nyl, comm.world, 1, d_loc.device, "mg_slab", cycle_dtype)
     it = C.c_int(0)
-    st = N.lib.piso_mg_pcg_solve_slab_f64(comm.handle, nx, nyl, int(per_x), int(per_y), N.ptr(L_loc), N.ptr(d_loc), N.ptr(x_loc), C.c_float(accuracy),
-                                          int(max_iterations), int(bool(rank_deficient)), int(residual_reset), int(sweeps), C.byref(it), N.ptr(ws),
-                                          C.c_size_t(ws.numel()), N.stream_ptr())
+    st = fn(comm.handle, nx, nyl, int(per_x), int(per_y), N.ptr(L_loc), N.ptr(d_loc), N.ptr(x_loc), C.c_float(accuracy),
+            int(max_iterations), int(bool(rank_deficient)), int(residual_reset), int(sweeps), C.byref(it), N.ptr(ws),
+            C.c_size_t(ws.numel()), N.stream_ptr())
     N.check(st, "piso_mg_pcg_solve_slab")
     return x_loc, it.value
 
 
-def mg_solve_slab_emulated(slabs, nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset, sweeps=2, workspace=None):
+def mg_solve_slab_emulated(slabs, nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset, sweeps=2, workspace=None,
+                           cycle_dtype=torch.float64):
     """`slabs` virtual ranks on one device (rows copied between them, no communicator): test harness for every cut."""
+    fn = _mg_slab_fn("pcg_solve_slab_emulated", cycle_dtype)
     d = div.reshape(-1).to(torch.float64).contiguous()
     x = torch.empty_like(d)
-    ws = workspace if workspace is not None else _mg_slab_workspace(nx, ny // slabs, slabs, slabs, d.device, "mg_slab_emu")
+    ws = workspace if workspace is not None else _mg_slab_workspace(nx, ny // slabs, slabs, slabs, d.device, "mg_slab_emu", cycle_dtype)
     it = C.c_int(0)
-    st = N.lib.piso_mg_pcg_solve_slab_emulated_f64(int(slabs), nx, ny, int(per_x), int(per_y), N.ptr(L), N.ptr(d), N.ptr(x), C.c_float(accuracy),
-                                                   int(max_iterations), int(bool(rank_deficient)), int(residual_reset), int(sweeps), C.byref(it),
-                                                   N.ptr(ws), C.c_size_t(ws.numel()), N.stream_ptr())
+    st = fn(int(slabs), nx, ny, int(per_x), int(per_y), N.ptr(L), N.ptr(d), N.ptr(x), C.c_float(accuracy),
+            int(max_iterations), int(bool(rank_deficient)), int(residual_reset), int(sweeps), C.byref(it),
+            N.ptr(ws), C.c_size_t(ws.numel()), N.stream_ptr())
     N.check(st, "piso_mg_pcg_solve_slab_emulated")
     return x, it.value
 
 
-def mg_vcycle_slab_local(comm, nx, nyl, per_x, per_y, L_loc, r_loc, sweeps=2, workspace=None):
+def mg_vcycle_slab_local(comm, nx, nyl, per_x, per_y, L_loc, r_loc, sweeps=2, workspace=None, cycle_dtype=torch.float64):
     """This rank's rows of z = M^-1 r: one V-cycle through the communicator (tests, measurements)."""
+    fn = _mg_slab_fn("vcycle_slab", cycle_dtype)
     r_loc = r_loc.reshape(-1).to(torch.float64).contiguous()
     z = torch.empty_like(r_loc)
-    ws = workspace if workspace is not None else _mg_slab_workspace(nx, nyl, comm.world, 1, r_loc.device, "mg_slab")
-    N.check(N.lib.piso_mg_vcycle_slab_f64(comm.handle, nx, nyl, int(per_x), int(per_y), N.ptr(L_loc), N.ptr(r_loc), N.ptr(z), int(sweeps), N.ptr(ws),
-                                          C.c_size_t(ws.numel()), N.stream_ptr()), "piso_mg_vcycle_slab")
+    ws = workspace if workspace is not None else _mg_slab_workspace(nx, nyl, comm.world, 1, r_loc.device, "mg_slab", cycle_dtype)
+    N.check(fn(comm.handle, nx, nyl, int(per_x), int(per_y), N.ptr(L_loc), N.ptr(r_loc), N.ptr(z), int(sweeps), N.ptr(ws),
+               C.c_size_t(ws.numel()), N.stream_ptr()), "piso_mg_vcycle_slab")
     return z
 
 
-def mg_vcycle_slab_emulated(slabs, nx, ny, per_x, per_y, L, r, sweeps=2, workspace=None):
+def mg_vcycle_slab_emulated(slabs, nx, ny, per_x, per_y, L, r, sweeps=2, workspace=None, cycle_dtype=torch.float64):
+    fn = _mg_slab_fn("vcycle_slab_emulated", cycle_dtype)
     r = r.reshape(-1).to(torch.float64).contiguous()
     z = torch.empty_like(r)
-    ws = workspace if workspace is not None else _mg_slab_workspace(nx, ny // slabs, slabs, slabs, r.device, "mg_slab_emu")
-    N.check(N.lib.piso_mg_vcycle_slab_emulated_f64(int(slabs), nx, ny, int(per_x), int(per_y), N.ptr(L), N.ptr(r), N.ptr(z), int(sweeps), N.ptr(ws),
-                                                   C.c_size_t(ws.numel()), N.stream_ptr()), "piso_mg_vcycle_slab_emulated")
+    ws = workspace if workspace is not None else _mg_slab_workspace(nx, ny // slabs, slabs, slabs, r.device, "mg_slab_emu", cycle_dtype)
+    N.check(fn(int(slabs), nx, ny, int(per_x), int(per_y), N.ptr(L), N.ptr(r), N.ptr(z), int(sweeps), N.ptr(ws),
+               C.c_size_t(ws.numel()), N.stream_ptr()), "piso_mg_vcycle_slab_emulated")
     return z
 
 
-def mg_level_slab_emulated(slabs, rank, nx, ny, per_x, per_y, L, level):
-    """-> (virtual rank `rank`'s rows of a sharded level, or the whole replicated level, [rows * nxl, 5]; nxl; rows) (tests)."""
-    ws = _mg_slab_workspace(nx, ny // slabs, slabs, slabs, L.device, "mg_slab_emu")
+def mg_level_slab_emulated(slabs, rank, nx, ny, per_x, per_y, L, level, cycle_dtype=torch.float64):
+    """-> (virtual rank `rank`'s rows of a sharded level, or the whole replicated level, [rows * nxl, 5]; nxl; rows) (tests); the float32
+    cycle's entries come widened to float64."""
+    fn = _mg_slab_fn("level_slab_emulated", cycle_dtype)
+    ws = _mg_slab_workspace(nx, ny // slabs, slabs, slabs, L.device, "mg_slab_emu", cycle_dtype)
     nxl, rows = C.c_int(0), C.c_int(0)
     args = (int(slabs), int(rank), nx, ny, int(per_x), int(per_y), N.ptr(L), int(level), C.byref(nxl), C.byref(rows))
-    N.check(N.lib.piso_mg_level_slab_emulated_f64(*args, None, N.ptr(ws), C.c_size_t(ws.numel()), N.stream_ptr()), "piso_mg_level_slab_emulated")
+    N.check(fn(*args, None, N.ptr(ws), C.c_size_t(ws.numel()), N.stream_ptr()), "piso_mg_level_slab_emulated")
     out = torch.empty((nxl.value * rows.value, 5), dtype=torch.float64, device=L.device)
-    N.check(N.lib.piso_mg_level_slab_emulated_f64(*args, N.ptr(out), N.ptr(ws), C.c_size_t(ws.numel()), N.stream_ptr()), "piso_mg_level_slab_emulated")
+    N.check(fn(*args, N.ptr(out), N.ptr(ws), C.c_size_t(ws.numel()), N.stream_ptr()), "piso_mg_level_slab_emulated")
     return out, nxl.value, rows.value
 
 
 def comm_allgather(comm, src):
-    """piso_comm_allgather_f64: every rank's `src` (float64, the same length everywhere) in rank order, on every rank."""
+    """piso_comm_allgather_f64 / _f32: every rank's `src` (float64 or float32, the same length everywhere) in rank order, on every rank."""
     src = src.contiguous()
-    dst = torch.empty(src.numel() * comm.world, dtype=torch.float64, device=src.device)
-    N.check(N.lib.piso_comm_allgather_f64(comm.handle, N.ptr(src), N.ptr(dst), src.numel(), N.stream_ptr()), "piso_comm_allgather_f64")
+    if src.dtype not in (torch.float64, torch.float32):
+        raise ValueError("comm_allgather carries float64 or float32 (got %r)" % (src.dtype,))
+    fn, name = (N.lib.piso_comm_allgather_f64, "piso_comm_allgather_f64") if src.dtype == torch.float64 else (N.lib.piso_comm_allgather_f32, "piso_comm_allgather_f32")
+    dst = torch.empty(src.numel() * comm.world, dtype=src.dtype, device=src.device)
+    N.check(fn(comm.handle, N.ptr(src), N.ptr(dst), src.numel(), N.stream_ptr()), name)
     N.check(N.lib.piso_comm_check(comm.handle, N.stream_ptr()), "piso_comm_check")
     return dst
 

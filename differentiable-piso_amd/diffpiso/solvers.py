@@ -664,8 +664,11 @@ class PisoPressureSolverMultigrid(PisoPressureSolverCudaCustom):
     launch or host round trip per iteration and are the better choice.  fp64 only: cast_to_double=False is refused.
     cycle_dtype=torch.float32 (opt-in) keeps that fp64 iteration - x, r, p, q, the operator, every sum, the stopping rule - and runs the
     V-cycle, hierarchy included, in float32 (csrc/mg_f32.h): the same counts or a few more iterations (DESIGN.md 3.7 has both tables), r is
-    not scaled, so a residual beyond float32's range never converges and tolerances below ~1e-30 are outside that mode.  It is one-GPU only:
-    with a communicator that would cut the solve it is refused.
+    not scaled, so a residual beyond float32's range never converges and tolerances below ~1e-30 are outside that mode.  It runs on y-slabs
+    too (csrc/mg_slab_f32.h: the sharded levels and the gathered rows of level g are float32, so the halo rows and the gather carry half the
+    bytes in the same number of collectives; the outer iteration stays fp64 and sharded) - except where the plan replicates the whole cycle
+    (g = 0: the whole grid within the gather limit of 8192 cells), which has nothing to gain from float32 and is refused with a message
+    naming cycle_dtype=torch.float64.
     With a distributed.SlabCommunicator of more than one rank in `slab_comm` the solve is cut into y-slabs like the plain solver's (csrc/mg_slab.h:
     fine levels sharded with halo rows, the levels of at most 8192 cells replicated; ny / ranks must be divisible by 2^g, g the first replicated
     level, else the call is refused and names the plain solver); with `.sharded` L holds the rank's rows and the result stays on them.  Anything
@@ -698,19 +701,21 @@ class PisoPressureSolverMultigrid(PisoPressureSolverCudaCustom):
             raise N.PisoNativeError("PisoPressureSolverMultigrid is fp64 only; use PisoPressureSolverCudaCustom for float32")
         # (option slab_force: a communicator of ONE rank still runs the slab solve - a ring of one, tests)
         if self.slab_comm is not None and (self.slab_comm.world > 1 or N.get_option("slab_force") > 0):
-            if self.cycle_dtype != torch.float64:
+            # (the plan is asked on the host, before the communicator is touched: g = 0 replicates the whole cycle, where float32 gains nothing)
+            ny_all = self.slab_comm.step_sharding.nyl * self.slab_comm.world if self.slab_comm.sharded else ny
+            if self.cycle_dtype != torch.float64 and N.mg_slab_plan(nx, ny_all, self.slab_comm.world)["g"] == 0:
                 raise N.PisoNativeError("PisoPressureSolverMultigrid: the float32 cycle runs on one GPU only; a solve cut into y-slabs needs "
                                         "cycle_dtype=torch.float64")
             if self.slab_comm.sharded:       # slab-decomposed STEP: L holds the rank's owned rows, div its stored rows; the result stays there
                 sh = self.slab_comm.step_sharding
                 d_loc = sh.owned_cells(div.reshape(-1).to(torch.float64)).reshape(-1).contiguous()
                 x_loc, it = mg_solve_slab_local(self.slab_comm, nx, sh.nyl, per_x, per_y, L, d_loc, accuracy, max_iterations, rank_deficient,
-                                                residual_reset, self.smoothing_sweeps)
+                                                residual_reset, self.smoothing_sweeps, cycle_dtype=self.cycle_dtype)
                 x = torch.zeros(sh.n_cells, dtype=x_loc.dtype, device=x_loc.device)
                 sh.owned_cells(x).copy_(x_loc.view(sh.nyl, nx))
                 return x, it
             return mg_solve_slab(self.slab_comm, nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset,
-                                 self.smoothing_sweeps)
+                                 self.smoothing_sweeps, cycle_dtype=self.cycle_dtype)
         return mg_solve_native(nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset, self.smoothing_sweeps,
                                self.cycle_dtype)
 

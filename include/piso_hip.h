@@ -402,6 +402,30 @@ int piso_mg_vcycle_slab_emulated_f64(int slabs, int nx, int ny, int periodic_x, 
                                      int sweeps, void* workspace, size_t workspace_bytes, piso_stream_t stream);
 int piso_mg_level_slab_emulated_f64(int slabs, int rank, int nx, int ny, int periodic_x, int periodic_y, const double* laplace, int level, int* nx_out,
                                     int* rows_out, double* laplace_level_out, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+/* The float32 cycle on y-slabs (csrc/mg_slab_f32.h): the _c32_f64 twins of the six slab entries take the arguments of their _f64 namesakes and
+ * run the float32 cycle of piso_mg_*_c32_f64 on the same plan - the outer iteration stays fp64 and sharded, the sharded levels hold the
+ * rank's float rows with halo rows, the rank's float rows of level g are all-gathered and levels g .. coarsest run replicated in
+ * float32.  The collectives per iteration are the fp64 plan's in number; the halo rows and the gather carry half the bytes.  Against the
+ * one-GPU float32 cycle the hierarchy and a cycle are bit for bit the same.  One more refusal (PISO_ERR_INVALID_ARG): a plan with g = 0 -
+ * the whole grid within the gather limit, the cycle replicated altogether - has nothing to gain from float32 and wants the _f64 entries.
+ * piso_mg_slab_workspace_bytes_cycle: the workspace for cycle_elem_size 4 or 8 (8: piso_mg_slab_workspace_bytes; anything else, a refused
+ * plan, or g = 0 with 4: 0). */
+size_t piso_mg_slab_workspace_bytes_cycle(int nx, int ny_local, int world, int local_ranks, int cycle_elem_size);
+int piso_mg_pcg_solve_slab_c32_f64(void* comm, int nx, int ny_local, int periodic_x, int periodic_y, const double* laplace_local,
+                                   const double* divergence_local, double* x_out_local, float accuracy, int max_iterations, int rank_deficient,
+                                   int residual_reset, int sweeps, int* iterations_out, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+int piso_mg_vcycle_slab_c32_f64(void* comm, int nx, int ny_local, int periodic_x, int periodic_y, const double* laplace_local, const double* r_local,
+                                double* z_local, int sweeps, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+int piso_mg_level_slab_c32_f64(void* comm, int nx, int ny_local, int periodic_x, int periodic_y, const double* laplace_local, int level, int* nx_out,
+                               int* rows_out, double* laplace_level_out, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+int piso_mg_pcg_solve_slab_emulated_c32_f64(int slabs, int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence,
+                                            double* x_out, float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps,
+                                            int* iterations_out, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+int piso_mg_vcycle_slab_emulated_c32_f64(int slabs, int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* r_in,
+                                         double* z_out, int sweeps, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+int piso_mg_level_slab_emulated_c32_f64(int slabs, int rank, int nx, int ny, int periodic_x, int periodic_y, const double* laplace, int level,
+                                        int* nx_out, int* rows_out, double* laplace_level_out, void* workspace, size_t workspace_bytes,
+                                        piso_stream_t stream);
 /* What the calling thread's last multigrid solve / cycle ran (fp64, float32 cycle or slab); returns the number of fields (8):
  *    0 levels         levels of the hierarchy
  *    1 tail_first     first level that ran inside the one-workgroup tail kernel (-1: none)
@@ -410,7 +434,7 @@ int piso_mg_level_slab_emulated_f64(int slabs, int rank, int nx, int ny, int per
  *    4 cycles         V-cycles that contributed to the result
  *    5 residual_recomputations
  *    6 cycle_elem     bytes of a value of the cycle: 8, or 4 after a piso_mg_*_c32_f64 entry
- *    7 vec_mask       bit l set where level l ran the four-cell float32 kernels (0 for the fp64 and the slab paths) */
+ *    7 vec_mask       bit l set where level l ran the four-cell float32 kernels (0 for the fp64 paths) */
 int piso_mg_last_dispatch(int* out, int capacity);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -517,6 +541,9 @@ int piso_comm_check(void* comm, piso_stream_t stream);
  * transport: a host-launched mailbox kernel, count * world <= 8192 (more: PISO_ERR_INVALID_ARG); one rank copies, unless the option
  * "slab_force" sends the chunk through its own mailbox.  The bits arrive unchanged (NaN payloads, -0.0, infinities). */
 int piso_comm_allgather_f64(void* comm, const void* src, void* dst, int count, piso_stream_t stream);
+/* ... and of `count` floats per rank (the float rows of the float32 multigrid cycle): peer transport count * world <= 8192, a float is
+ * one tagged word of the gather area; RCCL: ncclFloat.  The bits arrive unchanged. */
+int piso_comm_allgather_f32(void* comm, const void* src, void* dst, int count, piso_stream_t stream);
 /* Slab-decomposed ILU(0)-BiCGStab (either transport): same arguments as piso_multi_bicgstab_ilu_*, all arrays FULL on every rank
  * (the assembly is cheap and replicated); the rank works on the face rows of its ny / world cell rows, which must be whole
  * preconditioner bands (ny / world a multiple of the band height: then the banded ILU(0) is the single-GPU one and the iterates

@@ -1,7 +1,9 @@
 """The slab multigrid before any link: median ms per solve of (a) the one-GPU multigrid, (b) the slab multigrid through a peer communicator
-of ONE rank (halo rows through the rank's own mailbox, the collapse kernels, the gather of level g as a copy) and (c) the plain slab CG
+of ONE rank (halo rows through the rank's own mailbox, the collapse kernels, the gather of level g as a copy), (c) the same slab multigrid
+with the float32 cycle (cycle_dtype=torch.float32: float halo rows and gather, the fp64 outer iteration) and (d) the plain slab CG
 through the same communicator, at 1e-5 and 1e-10 on 1024 x 256 walls, 1024^2 and 2048^2 (periodic and walls).  (b) / (a) is what the halo
-rows, the collectives' kernels and the gather cost on one GPU; the collectives per iteration (from the plan) are what a real node multiplies
+rows, the collectives' kernels and the gather cost on one GPU, (c) / (b) what the float32 cycle is worth on slabs (a plan with g = 0 has no
+column (c): the float32 cycle is refused there); the collectives per iteration (from the plan) are what a real node multiplies
 by its hop.  Warmed up, medians of interleaved repeats, every timing ends in a device synchronise.  Needs a GPU.
 
     python scripts/bench_mg_slab.py [--reps 5] [--sizes 1024x256w,1024x1024,1024x1024w,2048x2048,2048x2048w]
@@ -58,7 +60,11 @@ def main():
             for tol in (1e-5, 1e-10):
                 run = {"mg_one_gpu": lambda: mg_solve_native(nx, ny, per, per, L, b, tol, 500, True, 1000),
                        "mg_slab_ring_of_one": lambda: mg_solve_slab_local(comm, nx, ny, per, per, L.reshape(-1), b, tol, 500, True, 1000),
+                       "mg_slab_f32_ring_of_one": lambda: mg_solve_slab_local(comm, nx, ny, per, per, L.reshape(-1), b, tol, 500, True, 1000,
+                                                                              cycle_dtype=torch.float32),
                        "plain_slab_ring_of_one": lambda: cg_solve_slab(comm, nx, ny, per, per, L.reshape(-1), b, tol, PLAIN_CAP, True, 1000, gather=False)}
+                if g == 0:
+                    del run["mg_slab_f32_ring_of_one"]
                 ms, its = {k: [] for k in run}, {}
                 for k in run:
                     run[k]()                                   # warm-up
@@ -70,6 +76,8 @@ def main():
                            ms={k: statistics.median(v) for k, v in ms.items()}, ms_spread={k: (min(v), max(v)) for k, v in ms.items()},
                            plain_hit_cap=its["plain_slab_ring_of_one"] >= PLAIN_CAP)
                 row["slab_over_one_gpu"] = row["ms"]["mg_slab_ring_of_one"] / row["ms"]["mg_one_gpu"]
+                if g > 0:
+                    row["slab_f32_over_slab_f64"] = row["ms"]["mg_slab_f32_ring_of_one"] / row["ms"]["mg_slab_ring_of_one"]
                 row["slab_mg_faster_than_plain_slab"] = row["ms"]["mg_slab_ring_of_one"] < row["ms"]["plain_slab_ring_of_one"]
                 print(json.dumps(row), flush=True)
     finally:
