@@ -61,7 +61,7 @@ static_assert(kMinDim == kPlanMinDim && kTailCells == kPlanTailCells && kTailLds
               kMgMaxLevels == kPlanMaxLevels, "mg_slab_plan.h and mg.hip disagree about the hierarchy's constants");
 
 // (MgState, the SC_* slots of `scal`, the level structs Lv / LvF and kMgGrid: mg_slab_carve.h, host code a driver can walk)
-enum { MG_FLAG_BORDER = 1, MG_FLAG_ZERO_DIAG_ROW = 2, MG_FLAG_NOT_SINGULAR = 4 };
+enum { MG_FLAG_BORDER = 1, MG_FLAG_ZERO_DIAG_ROW = 2, MG_FLAG_NOT_SINGULAR = 4, MG_FLAG_NOT_PREPARED = 8 };      // (the last: mg_prepared.h)
 static_assert(kPlanMaxRanks == kMaxRanks, "mg_slab_carve.h and peer.h disagree about the ranks of a node");
 
 struct Walk { int begin, step; };
@@ -374,6 +374,7 @@ static int mg_common_args(const char* who, int nx, int ny, const void* a, const 
 #include "mg_slab.h"
 #include "mg_f32.h"
 #include "mg_slab_f32.h"
+#include "mg_prepared.h"
 
 namespace piso {
 
@@ -528,45 +529,7 @@ int piso_mg_pcg_solve_f64(int nx, int ny, int periodic_x, int periodic_y, const 
   MgPlan P;
   if (!mg_plan(nx, ny, periodic_x ? 1 : 0, periodic_y ? 1 : 0, ar, P)) { set_error_msg("piso_mg_pcg_solve: workspace too small"); return PISO_ERR_INVALID_ARG; }
   if (int rc = mg_build(P, laplace, divergence, rank_deficient ? 1 : 0, stream)) return rc;
-  MgState* pinned = nullptr;
-  if (int rc = mg_pinned(&pinned)) return rc;
-  const Lv& L0 = P.lv[0];
-  const int n = L0.n, g0 = mg_grid(n);
-  const bool use_tail = mg_use_tail(P);
-  const int check_every = opt(OPT_MG_CHECK_EVERY) > 0 ? opt(OPT_MG_CHECK_EVERY) : kCheckEvery;
-  double* r = P.r[0];
-  mg_init<<<g0, kBlock, 0, stream>>>(L0, divergence, x_out, r, P.scal);
-  bool done = false;
-  int iterations = max_iterations;
-  for (int k = 0; k < max_iterations && !done; ++k) {
-    const bool restart = k > 0 && (k + 1) % residual_reset == 0;
-    if (restart) mg_residual<<<g0, kBlock, 0, stream>>>(L0, divergence, x_out, r, P.scal, P.st);
-    int n_rz = 0;
-    const double* z = mg_cycle(P, r, sweeps, use_tail, &n_rz, stream);
-    mg_direction<<<g0, kBlock, 0, stream>>>(L0, z, P.p[k & 1], P.p[(k + 1) & 1], P.q, P.part_rz, n_rz, P.scal, k, (restart || k == 0) ? 1 : 0, P.part_pq, P.st);
-    mg_update<<<g0, kBlock, 0, stream>>>(n, x_out, r, P.p[(k + 1) & 1], P.q, P.scal, k, P.part_pq, g0, P.part_max, P.st);
-    mg_check<<<1, kBlock, 0, stream>>>(P.part_max, g0, accuracy, k + 1, P.st);
-    PISO_LAUNCH_CHECK();
-    if ((k + 1) % check_every == 0 || k + 1 == max_iterations) {
-      PISO_HIP_CHECK(hipMemcpyAsync(pinned, P.st, sizeof(MgState), hipMemcpyDeviceToHost, stream));
-      PISO_HIP_CHECK(hipStreamSynchronize(stream));
-      if (pinned->done) { done = true; iterations = pinned->iterations; }
-    }
-  }
-  if (rank_deficient) {
-    mg_sum_x<<<g0, kBlock, 0, stream>>>(L0, x_out, P.parts);
-    mg_finish<<<g0, kBlock, 0, stream>>>(L0, x_out, P.parts, g0, P.scal);
-    PISO_LAUNCH_CHECK();
-  }
-  PISO_HIP_CHECK(hipStreamSynchronize(stream));
-  if (iterations_out) *iterations_out = iterations;
-  int recomputed = 0;
-  for (int k = 1; k < iterations; ++k) recomputed += (k + 1) % residual_reset == 0;
-  int* d = tl_mg_dispatch;
-  d[MD_LEVELS] = P.nlev; d[MD_TAIL_FIRST] = use_tail ? P.tail_first : -1; d[MD_SWEEPS] = sweeps; d[MD_ITERATIONS] = iterations;
-  d[MD_CYCLES] = iterations; d[MD_RESIDUAL_RECOMPUTATIONS] = recomputed; d[MD_CYCLE_ELEM] = 8; d[MD_VEC_MASK] = 0;
-  tl_mg_dispatch_n = MD_COUNT;
-  return PISO_OK;
+  return mg_pcg_run(P, divergence, x_out, accuracy, max_iterations, rank_deficient ? 1 : 0, residual_reset, sweeps, iterations_out, stream);
 }
 
 int piso_mg_vcycle_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* r_in, double* z_out, int sweeps,
@@ -578,17 +541,7 @@ int piso_mg_vcycle_f64(int nx, int ny, int periodic_x, int periodic_y, const dou
   MgPlan P;
   if (!mg_plan(nx, ny, periodic_x ? 1 : 0, periodic_y ? 1 : 0, ar, P)) { set_error_msg("piso_mg_vcycle: workspace too small"); return PISO_ERR_INVALID_ARG; }
   if (int rc = mg_build(P, laplace, nullptr, 0, stream)) return rc;
-  const bool use_tail = mg_use_tail(P);
-  int n_rz = 0;
-  const double* z = mg_cycle(P, r_in, sweeps, use_tail, &n_rz, stream);
-  PISO_LAUNCH_CHECK();
-  PISO_HIP_CHECK(hipMemcpyAsync(z_out, z, (size_t)P.lv[0].n * sizeof(double), hipMemcpyDeviceToDevice, stream));
-  PISO_HIP_CHECK(hipStreamSynchronize(stream));
-  int* d = tl_mg_dispatch;
-  d[MD_LEVELS] = P.nlev; d[MD_TAIL_FIRST] = use_tail ? P.tail_first : -1; d[MD_SWEEPS] = sweeps; d[MD_ITERATIONS] = 0; d[MD_CYCLES] = 1;
-  d[MD_RESIDUAL_RECOMPUTATIONS] = 0; d[MD_CYCLE_ELEM] = 8; d[MD_VEC_MASK] = 0;
-  tl_mg_dispatch_n = MD_COUNT;
-  return PISO_OK;
+  return mg_vcycle_run(P, r_in, z_out, sweeps, false, stream);
 }
 
 int piso_mg_level_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, int level, int* nx_out, int* ny_out,
@@ -619,13 +572,6 @@ size_t piso_mg_workspace_bytes_cycle(int nx, int ny, int cycle_elem_size) {
   return ar.used;
 }
 
-static void mg_record_f32(const MgRunF& R, int iterations, int cycles, int recomputed) {
-  int* d = tl_mg_dispatch;
-  d[MD_LEVELS] = R.P.nlev; d[MD_TAIL_FIRST] = R.use_tail ? R.P.tail_first : -1; d[MD_SWEEPS] = R.nu; d[MD_ITERATIONS] = iterations;
-  d[MD_CYCLES] = cycles; d[MD_RESIDUAL_RECOMPUTATIONS] = recomputed; d[MD_CYCLE_ELEM] = 4; d[MD_VEC_MASK] = R.vec_mask;
-  tl_mg_dispatch_n = MD_COUNT;
-}
-
 int piso_mg_pcg_solve_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence, double* x_out,
                               float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps, int* iterations_out,
                               void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
@@ -637,43 +583,7 @@ int piso_mg_pcg_solve_c32_f64(int nx, int ny, int periodic_x, int periodic_y, co
   MgPlanF P;
   if (!mg_plan_f32(nx, ny, periodic_x ? 1 : 0, periodic_y ? 1 : 0, ar, P)) { set_error_msg("piso_mg_pcg_solve: workspace too small"); return PISO_ERR_INVALID_ARG; }
   if (int rc = mg_build_f32(P, laplace, divergence, rank_deficient ? 1 : 0, stream)) return rc;
-  MgState* pinned = nullptr;
-  if (int rc = mg_pinned(&pinned)) return rc;
-  const Lv& L0 = P.L0;
-  const int n = L0.n, g0 = mg_grid(n);
-  MgRunF R{P, sweeps, P.tail_first >= 0 && opt(OPT_MG_TAIL) != 0, opt(OPT_MG_F32_VEC) != 0, stream};
-  const int check_every = opt(OPT_MG_CHECK_EVERY) > 0 ? opt(OPT_MG_CHECK_EVERY) : kCheckEvery;
-  double* r = P.r64;
-  float* r32 = P.r[0];
-  mg_init_f32<<<g0, kBlock, 0, stream>>>(L0, divergence, x_out, r, P.scal, r32);
-  bool done = false;
-  int iterations = max_iterations;
-  for (int k = 0; k < max_iterations && !done; ++k) {
-    const bool restart = k > 0 && (k + 1) % residual_reset == 0;
-    if (restart) mg_residual_f32<<<g0, kBlock, 0, stream>>>(L0, divergence, x_out, r, P.scal, P.st, r32);
-    int n_rz = 0;
-    const float* z = R.cycle(r32, r, &n_rz);
-    mg_direction_f32<<<g0, kBlock, 0, stream>>>(L0, z, P.p[k & 1], P.p[(k + 1) & 1], P.q, P.part_rz, n_rz, P.scal, k, (restart || k == 0) ? 1 : 0, P.part_pq, P.st);
-    mg_update_f32<<<g0, kBlock, 0, stream>>>(n, x_out, r, P.p[(k + 1) & 1], P.q, P.scal, k, P.part_pq, g0, P.part_max, P.st, r32);
-    mg_check<<<1, kBlock, 0, stream>>>(P.part_max, g0, accuracy, k + 1, P.st);
-    PISO_LAUNCH_CHECK();
-    if ((k + 1) % check_every == 0 || k + 1 == max_iterations) {
-      PISO_HIP_CHECK(hipMemcpyAsync(pinned, P.st, sizeof(MgState), hipMemcpyDeviceToHost, stream));
-      PISO_HIP_CHECK(hipStreamSynchronize(stream));
-      if (pinned->done) { done = true; iterations = pinned->iterations; }
-    }
-  }
-  if (rank_deficient) {
-    mg_sum_x<<<g0, kBlock, 0, stream>>>(L0, x_out, P.parts);
-    mg_finish<<<g0, kBlock, 0, stream>>>(L0, x_out, P.parts, g0, P.scal);
-    PISO_LAUNCH_CHECK();
-  }
-  PISO_HIP_CHECK(hipStreamSynchronize(stream));
-  if (iterations_out) *iterations_out = iterations;
-  int recomputed = 0;
-  for (int k = 1; k < iterations; ++k) recomputed += (k + 1) % residual_reset == 0;
-  mg_record_f32(R, iterations, iterations, recomputed);
-  return PISO_OK;
+  return mg_pcg_run(P, divergence, x_out, accuracy, max_iterations, rank_deficient ? 1 : 0, residual_reset, sweeps, iterations_out, stream);
 }
 
 int piso_mg_vcycle_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* r_in, double* z_out, int sweeps,
@@ -685,16 +595,7 @@ int piso_mg_vcycle_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const
   MgPlanF P;
   if (!mg_plan_f32(nx, ny, periodic_x ? 1 : 0, periodic_y ? 1 : 0, ar, P)) { set_error_msg("piso_mg_vcycle: workspace too small"); return PISO_ERR_INVALID_ARG; }
   if (int rc = mg_build_f32(P, laplace, nullptr, 0, stream)) return rc;
-  MgRunF R{P, sweeps, P.tail_first >= 0 && opt(OPT_MG_TAIL) != 0, opt(OPT_MG_F32_VEC) != 0, stream};
-  const int n = P.L0.n;
-  mg_cast_f32<<<mg_grid(n), kBlock, 0, stream>>>(n, r_in, P.r[0]);
-  int n_rz = 0;
-  const float* z = R.cycle(P.r[0], nullptr, &n_rz);
-  mg_widen_f32<<<mg_grid(n), kBlock, 0, stream>>>(n, z, z_out);
-  PISO_LAUNCH_CHECK();
-  PISO_HIP_CHECK(hipStreamSynchronize(stream));
-  mg_record_f32(R, 0, 1, 0);
-  return PISO_OK;
+  return mg_vcycle_run(P, r_in, z_out, sweeps, false, stream);
 }
 
 int piso_mg_level_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, int level, int* nx_out, int* ny_out,

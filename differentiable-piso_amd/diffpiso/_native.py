@@ -75,6 +75,17 @@ lib.piso_mg_vcycle_c32_f64.argtypes = lib.piso_mg_vcycle_f64.argtypes
 lib.piso_mg_vcycle_c32_f64.restype = _i
 lib.piso_mg_level_c32_f64.argtypes = lib.piso_mg_level_f64.argtypes
 lib.piso_mg_level_c32_f64.restype = _i
+lib.piso_mg_hierarchy_bytes.argtypes = [_i, _i, _i]
+lib.piso_mg_hierarchy_bytes.restype = _sz
+lib.piso_mg_solve_workspace_bytes.argtypes = [_i, _i, _i]
+lib.piso_mg_solve_workspace_bytes.restype = _sz
+for _s in ("_f64", "_c32_f64"):
+    getattr(lib, "piso_mg_prepare" + _s).argtypes = [_i, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _sz, _vp]
+    getattr(lib, "piso_mg_prepare" + _s).restype = _i
+    getattr(lib, "piso_mg_pcg_solve_prepared" + _s).argtypes = [_i, _i, _i, _i, _vp, _sz, _vp, _vp, _f, _i, _i, _i, _i, _ip, _vp, _sz, _vp]
+    getattr(lib, "piso_mg_pcg_solve_prepared" + _s).restype = _i
+    getattr(lib, "piso_mg_vcycle_prepared" + _s).argtypes = [_i, _i, _i, _i, _vp, _sz, _vp, _vp, _i, _vp, _sz, _vp]
+    getattr(lib, "piso_mg_vcycle_prepared" + _s).restype = _i
 lib.piso_mg_slab_workspace_bytes.argtypes = [_i, _i, _i, _i]
 lib.piso_mg_slab_workspace_bytes.restype = _sz
 lib.piso_mg_slab_plan.argtypes = [_i, _i, _i, _i, _ip, _i]

@@ -554,6 +554,10 @@ class PisoPressureSolverCudaCustom(PoissonSolver):
                                  residual_reset)
         return cg_solve_native(nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset)
 
+    def _laplace(self, nx, ny, active, accessible, a0, dt, sharding):
+        """The pressure matrix of one solve_flat call (PisoPressureSolverMultigrid may hand back the previous call's)."""
+        return laplace_matrix_native(nx, ny, active, accessible, a0, dt, sharding)
+
     def solve(self, scaling_field, divergence, guess, enable_backprop, simulation_physics, offset=0, unrolling_step=0):
         # `guess` is ignored exactly like in the reference (init_with_zeros=True, piso_cuda_pressure_solver.py:95)
         scaling_field = scaling_field if isinstance(scaling_field, StaggeredGrid) else StaggeredGrid(scaling_field)
@@ -585,7 +589,7 @@ class PisoPressureSolverCudaCustom(PoissonSolver):
         else:
             loc = sharding.sim_tensors(simulation_physics, dev)
             active, accessible = loc["active"], loc["accessible"]
-        L = laplace_matrix_native(nx, ny, active, accessible, a0, dt, sharding)
+        L = self._laplace(nx, ny, active, accessible, a0, dt, sharding)
         per_y, per_x = [bool(b) for b in simulation_physics.bool_periodic]          # given (y, x), flipped for the op (:95)
         pressure, iteration = _PressureSolveFn.apply(divergence, L, self, nx, ny, per_x, per_y, rank_def)
         self.solve_count = self.solve_count + .001
@@ -654,6 +658,81 @@ def mg_level_native(nx, ny, per_x, per_y, L, level, cycle_dtype=torch.float64):
     return out, nxl.value, nyl.value
 
 
+class MgHierarchy(object):
+    """A multigrid hierarchy built once and solved on any number of times (csrc/mg_prepared.h).  Owns `buf`, a byte tensor of its own of
+    piso_mg_hierarchy_bytes - never the shared N.workspace(..., "mg"), which any other solver instance may overwrite: everything that depends
+    on the matrix only (the fp64 level 0 and, for cycle_dtype=torch.float32, the float32 levels too).  After prepare(L) it keeps a tensor
+    that shares L's storage alive, so that the recorded pointer cannot be handed to another tensor while the record is compared, and records
+    `key` = (data_ptr, _version, nx, ny, per_x, per_y, rank_deficient, cycle_dtype, device).  What the key cannot see is a matrix overwritten
+    through a raw pointer (a kernel of the library writing into L, a ctypes call): neither the pointer nor the version changes then."""
+
+    def __init__(self, nx, ny, per_x, per_y, rank_deficient, cycle_dtype=torch.float64, device=None):
+        self.elem = _mg_cycle_elem(cycle_dtype)
+        self.nx, self.ny, self.per_x, self.per_y = int(nx), int(ny), bool(per_x), bool(per_y)
+        self.rank_deficient, self.cycle_dtype = bool(rank_deficient), cycle_dtype
+        nbytes = N.lib.piso_mg_hierarchy_bytes(self.nx, self.ny, self.elem)
+        if nbytes == 0:
+            raise N.PisoNativeError("the multigrid pressure solver needs at least 4 cells in each dimension (got %d x %d); "
+                                    "use PisoPressureSolverCudaCustom" % (ny, nx))
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.buf = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+        self.buf[:256].zero_()                      # (memory the allocator hands back may still hold the header of a hierarchy that was freed)
+        self.matrix = None
+        self.key = None
+
+    def _suffix(self):
+        return "_f64" if self.elem == 8 else "_c32_f64"
+
+    def scratch(self):
+        return N.workspace(N.lib.piso_mg_solve_workspace_bytes(self.nx, self.ny, self.elem), self.device, "mg_solve")
+
+    def prepare(self, L):
+        """Builds the hierarchy of L [N][5] into the buffer; the library's three refusals leave it without a valid header."""
+        if L.dtype != torch.float64:
+            raise N.PisoNativeError("the multigrid pressure solver is fp64 only; use the plain CG (cg_solve_native) for float32")
+        self.matrix, self.key = None, None
+        ws = self.scratch()
+        fn = getattr(N.lib, "piso_mg_prepare" + self._suffix())
+        N.check(fn(self.nx, self.ny, int(self.per_x), int(self.per_y), N.ptr(L), int(self.rank_deficient), N.ptr(self.buf), C.c_size_t(self.buf.numel()),
+                   N.ptr(ws), C.c_size_t(ws.numel()), N.stream_ptr()), "piso_mg_prepare")
+        self.matrix = L.detach()
+        self.key = self.key_of(L, self.nx, self.ny, self.per_x, self.per_y, self.rank_deficient, self.cycle_dtype)
+        return self
+
+    @staticmethod
+    def key_of(L, nx, ny, per_x, per_y, rank_deficient, cycle_dtype):
+        return (L.data_ptr(), L._version, int(nx), int(ny), bool(per_x), bool(per_y), bool(rank_deficient), cycle_dtype, L.device)
+
+
+def mg_prepare_native(nx, ny, per_x, per_y, L, rank_deficient, cycle_dtype=torch.float64):
+    """-> MgHierarchy of L, ready for mg_solve_prepared_native / mg_vcycle_prepared_native."""
+    return MgHierarchy(nx, ny, per_x, per_y, rank_deficient, cycle_dtype, L.device).prepare(L)
+
+
+def mg_solve_prepared_native(h, div, accuracy, max_iterations, residual_reset, sweeps=2):
+    """-> (x, iterations) of mg_solve_native on the matrix `h` was prepared from, bit for bit, without the set-up and its host look."""
+    div = div.reshape(-1).to(torch.float64).contiguous()
+    x = torch.empty_like(div)
+    ws = h.scratch()
+    it = C.c_int(0)
+    fn = getattr(N.lib, "piso_mg_pcg_solve_prepared" + h._suffix())
+    st = fn(h.nx, h.ny, int(h.per_x), int(h.per_y), N.ptr(h.buf), C.c_size_t(h.buf.numel()), N.ptr(div), N.ptr(x), C.c_float(accuracy),
+            int(max_iterations), int(h.rank_deficient), int(residual_reset), int(sweeps), C.byref(it), N.ptr(ws), C.c_size_t(ws.numel()), N.stream_ptr())
+    N.check(st, "piso_mg_pcg_solve_prepared")
+    return x, it.value
+
+
+def mg_vcycle_prepared_native(h, r, sweeps=2):
+    """z = M^-1 r of mg_vcycle_native on a prepared hierarchy, bit for bit."""
+    r = r.reshape(-1).to(torch.float64).contiguous()
+    z = torch.empty_like(r)
+    ws = h.scratch()
+    fn = getattr(N.lib, "piso_mg_vcycle_prepared" + h._suffix())
+    N.check(fn(h.nx, h.ny, int(h.per_x), int(h.per_y), N.ptr(h.buf), C.c_size_t(h.buf.numel()), N.ptr(r), N.ptr(z), int(sweeps), N.ptr(ws),
+               C.c_size_t(ws.numel()), N.stream_ptr()), "piso_mg_vcycle_prepared")
+    return z
+
+
 class PisoPressureSolverMultigrid(PisoPressureSolverCudaCustom):
     """Opt-in pressure solver: CG preconditioned by one multigrid V-cycle per iteration (csrc/mg.hip).  The reference has no such
     solver.  It solves the system PisoPressureSolverCudaCustom solves, to the same stopping rule (max|r| < accuracy), in tens of
@@ -676,11 +755,20 @@ class PisoPressureSolverMultigrid(PisoPressureSolverCudaCustom):
     The fluid cells must be CONNECTED: a pocket of fluid enclosed by solid cells is not detected, and the solve then runs to `max_iterations`
     without converging (as the plain solver does).  Grids whose hierarchy stops after 0 or 1 coarsenings (a dimension below 8 or 16 cells
     next to a long one) are preconditioned poorly: ~200 iterations instead of tens.
+    reuse_hierarchy=True (opt-in, one GPU) separates set-up from solve: the solver keeps ONE MgHierarchy, the last one built, and solves on it
+    whenever the incoming matrix is the tensor it was built from (same storage pointer and version, grid, periodic flags, rank_deficient,
+    cycle_dtype, device), and solve_flat keeps the last (a0, masks, nx, ny) -> L the same way, so the two correctors of a step and their
+    adjoints share one matrix tensor, one hierarchy and one host look where the default builds four.  Results are those of the default bit
+    for bit.  The one thing the key cannot see is a matrix (or a0) overwritten through a raw pointer, outside torch's version counter: call
+    drop_hierarchy() after that.  The cache holds memory until it is dropped or replaced: the matrix [N][5] fp64 and a0, the fp64 level 0
+    (48 bytes a cell) and the coarser levels (fp64 cycle: 16 more) or, in float32 mode, the float32 levels (32 more).  `stats` counts
+    hierarchy_builds, hierarchy_reuses and laplace_builds in either mode.  Refused (naming reuse_hierarchy=False) with a slab communicator
+    in use: sharded hierarchies are not kept.
     Forward and adjoint solves, `last_iterations`, `stats` and SimulationParameters(pressure_solver=...) work as with the plain
     solver."""
 
     def __init__(self, dx, accuracy=1e-5, max_iterations=2000, residual_reset=10, randomized_restarts=0, cast_to_double=True,
-                 smoothing_sweeps=2, cycle_dtype=torch.float64):
+                 smoothing_sweeps=2, cycle_dtype=torch.float64, reuse_hierarchy=False):
         if not cast_to_double:
             raise ValueError("PisoPressureSolverMultigrid is fp64 only (cast_to_double=True); use PisoPressureSolverCudaCustom for float32")
         if not 1 <= int(smoothing_sweeps) <= 8:
@@ -691,6 +779,28 @@ class PisoPressureSolverMultigrid(PisoPressureSolverCudaCustom):
         self.name = "HIP multigrid-preconditioned Conjugate Gradient"
         self.smoothing_sweeps = int(smoothing_sweeps)
         self.cycle_dtype = cycle_dtype
+        self.reuse_hierarchy = bool(reuse_hierarchy)
+        self._hierarchy = None           # the last MgHierarchy built (reuse_hierarchy)
+        self._laplace_cache = None       # (key, the tensors the key points at, L) of the last solve_flat (reuse_hierarchy)
+        for k in ("hierarchy_builds", "hierarchy_reuses", "laplace_builds"):
+            dict.__setitem__(self.stats, k, 0)
+
+    def drop_hierarchy(self):
+        """Forgets the kept hierarchy and matrix (and frees their memory): the next solve builds both."""
+        self._hierarchy = None
+        self._laplace_cache = None
+
+    def _laplace(self, nx, ny, active, accessible, a0, dt, sharding):
+        if not self.reuse_hierarchy or sharding is not None:
+            self.stats.add("laplace_builds", 1)
+            return laplace_matrix_native(nx, ny, active, accessible, a0, dt, sharding)
+        key = (a0.data_ptr(), a0._version, active.data_ptr(), active._version, accessible.data_ptr(), accessible._version, nx, ny, dt, a0.device)
+        if self._laplace_cache is None or self._laplace_cache[0] != key:
+            self._laplace_cache = None
+            L = laplace_matrix_native(nx, ny, active, accessible, a0, dt, sharding)
+            self.stats.add("laplace_builds", 1)
+            self._laplace_cache = (key, (a0, active, accessible), L)      # (the tensors stay alive: their pointers cannot be handed out again)
+        return self._laplace_cache[2]
 
     def _cg(self, nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset):
         from .distributed import SlabCommunicator, mg_solve_slab, mg_solve_slab_local
@@ -701,6 +811,9 @@ class PisoPressureSolverMultigrid(PisoPressureSolverCudaCustom):
             raise N.PisoNativeError("PisoPressureSolverMultigrid is fp64 only; use PisoPressureSolverCudaCustom for float32")
         # (option slab_force: a communicator of ONE rank still runs the slab solve - a ring of one, tests)
         if self.slab_comm is not None and (self.slab_comm.world > 1 or N.get_option("slab_force") > 0):
+            if self.reuse_hierarchy:         # (before the communicator is touched)
+                raise N.PisoNativeError("PisoPressureSolverMultigrid: a hierarchy is kept on one GPU only; a solve cut into y-slabs needs "
+                                        "reuse_hierarchy=False")
             # (the plan is asked on the host, before the communicator is touched: g = 0 replicates the whole cycle, where float32 gains nothing)
             ny_all = self.slab_comm.step_sharding.nyl * self.slab_comm.world if self.slab_comm.sharded else ny
             if self.cycle_dtype != torch.float64 and N.mg_slab_plan(nx, ny_all, self.slab_comm.world)["g"] == 0:
@@ -716,8 +829,18 @@ class PisoPressureSolverMultigrid(PisoPressureSolverCudaCustom):
                 return x, it
             return mg_solve_slab(self.slab_comm, nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset,
                                  self.smoothing_sweeps, cycle_dtype=self.cycle_dtype)
-        return mg_solve_native(nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset, self.smoothing_sweeps,
-                               self.cycle_dtype)
+        if not self.reuse_hierarchy:
+            self.stats.add("hierarchy_builds", 1)
+            return mg_solve_native(nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset, self.smoothing_sweeps,
+                                   self.cycle_dtype)
+        h = self._hierarchy
+        if h is None or h.key != MgHierarchy.key_of(L, nx, ny, per_x, per_y, rank_deficient, self.cycle_dtype):
+            self._hierarchy = None           # (freed before its successor is allocated; a refused prepare leaves none)
+            h = self._hierarchy = mg_prepare_native(nx, ny, per_x, per_y, L, rank_deficient, self.cycle_dtype)
+            self.stats.add("hierarchy_builds", 1)
+        else:
+            self.stats.add("hierarchy_reuses", 1)
+        return mg_solve_prepared_native(h, div, accuracy, max_iterations, residual_reset, self.smoothing_sweeps)
 
     @staticmethod
     def last_dispatch():

@@ -371,6 +371,37 @@ int piso_mg_vcycle_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const
                            int sweeps, void* workspace, size_t workspace_bytes, piso_stream_t stream);
 int piso_mg_level_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, int level, int* nx_out, int* ny_out,
                           double* laplace_level_out, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+/* A PREPARED hierarchy (csrc/mg_prepared.h): set-up once, any number of solves of the same matrix.  piso_mg_prepare_* runs the set-up of
+ * piso_mg_pcg_solve_* into `hierarchy`, a buffer of piso_mg_hierarchy_bytes(nx, ny, cycle_elem_size) bytes the caller owns and keeps (the
+ * five coefficient arrays and the Jacobi weights of every level - for the float32 cycle the fp64 level 0 and the float32 levels - and the
+ * sums the constant mode needs), makes the one host look with the three PISO_ERR_UNSUPPORTED_PATTERN refusals, and on success seals the
+ * buffer with a device-side header (nx, ny, the periodic flags, the cycle's element size, rank_deficient), written last: a refused or failed
+ * prepare leaves no valid header.  piso_mg_pcg_solve_prepared_* / piso_mg_vcycle_prepared_* take the arguments of piso_mg_pcg_solve_* /
+ * piso_mg_vcycle_* with (hierarchy, hierarchy_bytes) in place of `laplace` and a scratch workspace of piso_mg_solve_workspace_bytes(nx, ny,
+ * cycle_elem_size) bytes (every call may use another one; prepare takes one too), make no host look before the first iteration and return
+ * x, the count and the piso_mg_last_dispatch record of the ordinary call bit for bit.  Their first kernel compares the header with the
+ * call's arguments; a mismatch ends the solve on the device and is reported at the first regular look: PISO_ERR_INVALID_ARG, "not a
+ * hierarchy prepared for this grid" (a cycle runs on a hierarchy prepared with either rank_deficient).  Buffers below the two sizes are
+ * refused on the host.  Both size functions return 0 where piso_mg_workspace_bytes_cycle does.  The caller must not change the matrix's
+ * hierarchy behind the library's back: the buffer is only read by a solve, so solves on it may follow each other on one stream. */
+size_t piso_mg_hierarchy_bytes(int nx, int ny, int cycle_elem_size);
+size_t piso_mg_solve_workspace_bytes(int nx, int ny, int cycle_elem_size);
+int piso_mg_prepare_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, int rank_deficient, void* hierarchy,
+                        size_t hierarchy_bytes, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+int piso_mg_pcg_solve_prepared_f64(int nx, int ny, int periodic_x, int periodic_y, const void* hierarchy, size_t hierarchy_bytes,
+                                   const double* divergence, double* x_out, float accuracy, int max_iterations, int rank_deficient,
+                                   int residual_reset, int sweeps, int* iterations_out, void* workspace, size_t workspace_bytes,
+                                   piso_stream_t stream);
+int piso_mg_vcycle_prepared_f64(int nx, int ny, int periodic_x, int periodic_y, const void* hierarchy, size_t hierarchy_bytes, const double* r_in,
+                                double* z_out, int sweeps, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+int piso_mg_prepare_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, int rank_deficient, void* hierarchy,
+                            size_t hierarchy_bytes, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+int piso_mg_pcg_solve_prepared_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const void* hierarchy, size_t hierarchy_bytes,
+                                       const double* divergence, double* x_out, float accuracy, int max_iterations, int rank_deficient,
+                                       int residual_reset, int sweeps, int* iterations_out, void* workspace, size_t workspace_bytes,
+                                       piso_stream_t stream);
+int piso_mg_vcycle_prepared_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const void* hierarchy, size_t hierarchy_bytes,
+                                    const double* r_in, double* z_out, int sweeps, void* workspace, size_t workspace_bytes, piso_stream_t stream);
 /* The same solver on y-slabs (csrc/mg_slab.h, csrc/mg_slab_plan.h): every rank owns ny_local = ny / world contiguous rows and passes its
  * rows of laplace / divergence / x, otherwise the arguments of piso_mg_pcg_solve_f64.  Levels 0 .. g - 1 are sharded (a rank's rows
  * plus one halo row below and above), level g - the first of at most 8192 cells, or of at most "mg_slab_gather_cells" cells where that
