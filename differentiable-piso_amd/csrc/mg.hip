@@ -33,6 +33,7 @@
 // iterations queued after convergence see the device flag and return at once, so neither x nor the count depends on the cadence.
 //
 // Opt-in: the same iteration around a float32 cycle (mg_f32.h, piso_mg_*_c32_f64); this file's kernels are its fp64 outer iteration.
+// Opt-in: a start from a guess x0 instead of x = 0 where its residual is below the right-hand side (mg_guess.h, piso_mg_*_guess_*).
 #include <vector>
 
 #include "mg_slab_carve.h"
@@ -374,6 +375,7 @@ static int mg_common_args(const char* who, int nx, int ny, const void* a, const 
 #include "mg_slab.h"
 #include "mg_f32.h"
 #include "mg_slab_f32.h"
+#include "mg_guess.h"
 #include "mg_prepared.h"
 
 namespace piso {
@@ -417,6 +419,7 @@ static int mg_slab_solve_comm(const char* who, void* comm, int nx, int ny_local,
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   char msg[128];
   if (max_iterations < 1 || residual_reset < 1) { snprintf(msg, sizeof(msg), "%s: max_iterations and residual_reset must be positive", who); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
+  tl_mg_last_guess = 0;                                       // (a slab solve takes no guess)
   MgSlabT<C> M;
   PISO_TRY(mg_slab_comm_begin(M, who, comm, nx, ny_local, periodic_x, periodic_y, laplace_local, divergence_local, x_out_local, workspace, workspace_bytes, sweeps, stream));
   M.R[0].b = divergence_local;
@@ -433,6 +436,7 @@ static int mg_slab_solve_emulated(const char* who, int slabs, int nx, int ny, in
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   char msg[128];
   if (max_iterations < 1 || residual_reset < 1) { snprintf(msg, sizeof(msg), "%s: max_iterations and residual_reset must be positive", who); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
+  tl_mg_last_guess = 0;
   MgSlabT<C> M;
   PISO_TRY(mg_slab_emulated_begin(M, who, slabs, nx, ny, periodic_x, periodic_y, laplace, divergence, x_out, workspace, workspace_bytes, sweeps, stream));
   const size_t n = (size_t)nx * (ny / slabs);
@@ -508,6 +512,36 @@ static int mg_slab_level_emulated(const char* who, int slabs, int rank, int nx, 
 
 using namespace piso;
 
+// the ordinary solve entries, with and without a guess (x0 NULL: none)
+static int mg_solve_entry_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence, double* x_out,
+                              float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps, int* iterations_out,
+                              void* workspace, size_t workspace_bytes, piso_stream_t stream_, const double* x0) {
+  const OptScope knobs;
+  tl_mg_last_guess = 0;                                       // (until the solve returns: a refused call reports no guess)
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (int rc = mg_common_args("piso_mg_pcg_solve", nx, ny, laplace, divergence, x_out, workspace, sweeps)) return rc;
+  if (max_iterations < 1 || residual_reset < 1) { set_error_msg("piso_mg_pcg_solve: max_iterations and residual_reset must be positive"); return PISO_ERR_INVALID_ARG; }
+  Arena ar(workspace, workspace_bytes);
+  MgPlan P;
+  if (!mg_plan(nx, ny, periodic_x ? 1 : 0, periodic_y ? 1 : 0, ar, P)) { set_error_msg("piso_mg_pcg_solve: workspace too small"); return PISO_ERR_INVALID_ARG; }
+  if (int rc = mg_build(P, laplace, divergence, rank_deficient ? 1 : 0, stream)) return rc;
+  return mg_pcg_run(P, divergence, x_out, accuracy, max_iterations, rank_deficient ? 1 : 0, residual_reset, sweeps, iterations_out, stream, x0);
+}
+static int mg_solve_entry_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence, double* x_out,
+                                  float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps, int* iterations_out,
+                                  void* workspace, size_t workspace_bytes, piso_stream_t stream_, const double* x0) {
+  const OptScope knobs;
+  tl_mg_last_guess = 0;                                       // (until the solve returns: a refused call reports no guess)
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (int rc = mg_common_args("piso_mg_pcg_solve", nx, ny, laplace, divergence, x_out, workspace, sweeps)) return rc;
+  if (max_iterations < 1 || residual_reset < 1) { set_error_msg("piso_mg_pcg_solve: max_iterations and residual_reset must be positive"); return PISO_ERR_INVALID_ARG; }
+  Arena ar(workspace, workspace_bytes);
+  MgPlanF P;
+  if (!mg_plan_f32(nx, ny, periodic_x ? 1 : 0, periodic_y ? 1 : 0, ar, P)) { set_error_msg("piso_mg_pcg_solve: workspace too small"); return PISO_ERR_INVALID_ARG; }
+  if (int rc = mg_build_f32(P, laplace, divergence, rank_deficient ? 1 : 0, stream)) return rc;
+  return mg_pcg_run(P, divergence, x_out, accuracy, max_iterations, rank_deficient ? 1 : 0, residual_reset, sweeps, iterations_out, stream, x0);
+}
+
 extern "C" {
 
 size_t piso_mg_workspace_bytes(int nx, int ny) {
@@ -520,16 +554,15 @@ size_t piso_mg_workspace_bytes(int nx, int ny) {
 
 int piso_mg_pcg_solve_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence, double* x_out,
                           float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps, int* iterations_out,
-                          void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
-  const piso::OptScope knobs;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (int rc = mg_common_args("piso_mg_pcg_solve", nx, ny, laplace, divergence, x_out, workspace, sweeps)) return rc;
-  if (max_iterations < 1 || residual_reset < 1) { set_error_msg("piso_mg_pcg_solve: max_iterations and residual_reset must be positive"); return PISO_ERR_INVALID_ARG; }
-  Arena ar(workspace, workspace_bytes);
-  MgPlan P;
-  if (!mg_plan(nx, ny, periodic_x ? 1 : 0, periodic_y ? 1 : 0, ar, P)) { set_error_msg("piso_mg_pcg_solve: workspace too small"); return PISO_ERR_INVALID_ARG; }
-  if (int rc = mg_build(P, laplace, divergence, rank_deficient ? 1 : 0, stream)) return rc;
-  return mg_pcg_run(P, divergence, x_out, accuracy, max_iterations, rank_deficient ? 1 : 0, residual_reset, sweeps, iterations_out, stream);
+                          void* workspace, size_t workspace_bytes, piso_stream_t stream) {
+  return mg_solve_entry_f64(nx, ny, periodic_x, periodic_y, laplace, divergence, x_out, accuracy, max_iterations, rank_deficient, residual_reset, sweeps,
+                            iterations_out, workspace, workspace_bytes, stream, nullptr);
+}
+int piso_mg_pcg_solve_guess_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence, const double* x0,
+                                double* x_out, float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps,
+                                int* iterations_out, void* workspace, size_t workspace_bytes, piso_stream_t stream) {
+  return mg_solve_entry_f64(nx, ny, periodic_x, periodic_y, laplace, divergence, x_out, accuracy, max_iterations, rank_deficient, residual_reset, sweeps,
+                            iterations_out, workspace, workspace_bytes, stream, x0);
 }
 
 int piso_mg_vcycle_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* r_in, double* z_out, int sweeps,
@@ -574,16 +607,15 @@ size_t piso_mg_workspace_bytes_cycle(int nx, int ny, int cycle_elem_size) {
 
 int piso_mg_pcg_solve_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence, double* x_out,
                               float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps, int* iterations_out,
-                              void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
-  const piso::OptScope knobs;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (int rc = mg_common_args("piso_mg_pcg_solve", nx, ny, laplace, divergence, x_out, workspace, sweeps)) return rc;
-  if (max_iterations < 1 || residual_reset < 1) { set_error_msg("piso_mg_pcg_solve: max_iterations and residual_reset must be positive"); return PISO_ERR_INVALID_ARG; }
-  Arena ar(workspace, workspace_bytes);
-  MgPlanF P;
-  if (!mg_plan_f32(nx, ny, periodic_x ? 1 : 0, periodic_y ? 1 : 0, ar, P)) { set_error_msg("piso_mg_pcg_solve: workspace too small"); return PISO_ERR_INVALID_ARG; }
-  if (int rc = mg_build_f32(P, laplace, divergence, rank_deficient ? 1 : 0, stream)) return rc;
-  return mg_pcg_run(P, divergence, x_out, accuracy, max_iterations, rank_deficient ? 1 : 0, residual_reset, sweeps, iterations_out, stream);
+                              void* workspace, size_t workspace_bytes, piso_stream_t stream) {
+  return mg_solve_entry_c32_f64(nx, ny, periodic_x, periodic_y, laplace, divergence, x_out, accuracy, max_iterations, rank_deficient, residual_reset, sweeps,
+                                iterations_out, workspace, workspace_bytes, stream, nullptr);
+}
+int piso_mg_pcg_solve_guess_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence, const double* x0,
+                                    double* x_out, float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps,
+                                    int* iterations_out, void* workspace, size_t workspace_bytes, piso_stream_t stream) {
+  return mg_solve_entry_c32_f64(nx, ny, periodic_x, periodic_y, laplace, divergence, x_out, accuracy, max_iterations, rank_deficient, residual_reset, sweeps,
+                                iterations_out, workspace, workspace_bytes, stream, x0);
 }
 
 int piso_mg_vcycle_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* r_in, double* z_out, int sweeps,
@@ -672,6 +704,8 @@ int piso_mg_slab_plan(int nx, int ny, int world, int gather_cells, int* out, int
 PISO_MG_SLAB_ENTRIES(_f64, double)
 PISO_MG_SLAB_ENTRIES(_c32_f64, float)
 #undef PISO_MG_SLAB_ENTRIES
+
+int piso_mg_last_guess(void) { return tl_mg_last_guess; }
 
 int piso_mg_last_dispatch(int* out, int capacity) {
   const int n = tl_mg_dispatch_n < capacity ? tl_mg_dispatch_n : capacity;

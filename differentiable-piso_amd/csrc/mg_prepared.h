@@ -72,7 +72,7 @@ static int mg_recomputations(int iterations, int residual_reset) {
 }
 
 static int mg_pcg_run(const MgPlan& P, const double* divergence, double* x_out, float accuracy, int max_iterations, int rank_deficient,
-                      int residual_reset, int sweeps, int* iterations_out, hipStream_t stream) {
+                      int residual_reset, int sweeps, int* iterations_out, hipStream_t stream, const double* x0 = nullptr) {
   MgState* pinned = nullptr;
   if (int rc = mg_pinned(&pinned)) return rc;
   const Lv& L0 = P.lv[0];
@@ -80,7 +80,7 @@ static int mg_pcg_run(const MgPlan& P, const double* divergence, double* x_out, 
   const bool use_tail = mg_use_tail(P);
   const int check_every = opt(OPT_MG_CHECK_EVERY) > 0 ? opt(OPT_MG_CHECK_EVERY) : kCheckEvery;
   double* r = P.r[0];
-  mg_init<<<g0, kBlock, 0, stream>>>(L0, divergence, x_out, r, P.scal);
+  mg_start(L0, divergence, x0, x_out, r, nullptr, P.scal, P.parts, P.part_max, accuracy, P.st, stream);
   bool done = false;
   int iterations = max_iterations;
   for (int k = 0; k < max_iterations && !done; ++k) {
@@ -104,11 +104,12 @@ static int mg_pcg_run(const MgPlan& P, const double* divergence, double* x_out, 
   }
   PISO_HIP_CHECK(hipStreamSynchronize(stream));
   if (iterations_out) *iterations_out = iterations;
+  mg_guess_record(x0, pinned);
   mg_record(P.nlev, use_tail ? P.tail_first : -1, sweeps, iterations, iterations, mg_recomputations(iterations, residual_reset), 8, 0);
   return PISO_OK;
 }
 static int mg_pcg_run(const MgPlanF& P, const double* divergence, double* x_out, float accuracy, int max_iterations, int rank_deficient,
-                          int residual_reset, int sweeps, int* iterations_out, hipStream_t stream) {
+                          int residual_reset, int sweeps, int* iterations_out, hipStream_t stream, const double* x0 = nullptr) {
   MgState* pinned = nullptr;
   if (int rc = mg_pinned(&pinned)) return rc;
   const Lv& L0 = P.L0;
@@ -117,7 +118,7 @@ static int mg_pcg_run(const MgPlanF& P, const double* divergence, double* x_out,
   const int check_every = opt(OPT_MG_CHECK_EVERY) > 0 ? opt(OPT_MG_CHECK_EVERY) : kCheckEvery;
   double* r = P.r64;
   float* r32 = P.r[0];
-  mg_init_f32<<<g0, kBlock, 0, stream>>>(L0, divergence, x_out, r, P.scal, r32);
+  mg_start(L0, divergence, x0, x_out, r, r32, P.scal, P.parts, P.part_max, accuracy, P.st, stream);
   bool done = false;
   int iterations = max_iterations;
   for (int k = 0; k < max_iterations && !done; ++k) {
@@ -141,6 +142,7 @@ static int mg_pcg_run(const MgPlanF& P, const double* divergence, double* x_out,
   }
   PISO_HIP_CHECK(hipStreamSynchronize(stream));
   if (iterations_out) *iterations_out = iterations;
+  mg_guess_record(x0, pinned);
   mg_record_f32(R, iterations, iterations, mg_recomputations(iterations, residual_reset));
   return PISO_OK;
 }
@@ -236,8 +238,9 @@ static int mg_prepare(int nx, int ny, int periodic_x, int periodic_y, const doub
 template <typename C>
 static int mg_solve_prepared(int nx, int ny, int periodic_x, int periodic_y, const void* hierarchy, size_t hierarchy_bytes, const double* divergence,
                              double* x_out, float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps, int* iterations_out,
-                             void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
+                             void* workspace, size_t workspace_bytes, piso_stream_t stream_, const double* x0) {
   const OptScope knobs;
+  tl_mg_last_guess = 0;                                       // (until the solve returns: a refused call reports no guess)
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   const int px = periodic_x ? 1 : 0, py = periodic_y ? 1 : 0, rd = rank_deficient ? 1 : 0;
   if (int rc = mg_common_args("piso_mg_pcg_solve_prepared", nx, ny, hierarchy, divergence, x_out, workspace, sweeps)) return rc;
@@ -249,7 +252,7 @@ static int mg_solve_prepared(int nx, int ny, int periodic_x, int periodic_y, con
   mg_rhs_sums<<<g0, kBlock, 0, stream>>>(mg_header(nx, ny, px, py, (int)sizeof(C), rd), H.hdr, H.L0.dinv, H.L0.n, divergence, P.parts, P.st);
   mg_rhs_fin<<<1, kBlock, 0, stream>>>(P.parts, g0, H.scal, P.scal, rd);
   PISO_LAUNCH_CHECK();
-  return mg_pcg_run(P, divergence, x_out, accuracy, max_iterations, rd, residual_reset, sweeps, iterations_out, stream);
+  return mg_pcg_run(P, divergence, x_out, accuracy, max_iterations, rd, residual_reset, sweeps, iterations_out, stream, x0);
 }
 template <typename C>
 static int mg_vcycle_prepared(int nx, int ny, int periodic_x, int periodic_y, const void* hierarchy, size_t hierarchy_bytes, const double* r_in, double* z_out,
@@ -283,7 +286,14 @@ size_t piso_mg_solve_workspace_bytes(int nx, int ny, int cycle_elem_size) { retu
                                          const double* divergence, double* x_out, float accuracy, int max_iterations, int rank_deficient, int residual_reset,    \
                                          int sweeps, int* iterations_out, void* workspace, size_t workspace_bytes, piso_stream_t stream) {                       \
     return piso::mg_solve_prepared<C>(nx, ny, periodic_x, periodic_y, hierarchy, hierarchy_bytes, divergence, x_out, accuracy, max_iterations, rank_deficient,   \
-                                      residual_reset, sweeps, iterations_out, workspace, workspace_bytes, stream);                                               \
+                                      residual_reset, sweeps, iterations_out, workspace, workspace_bytes, stream, nullptr);                                      \
+  }                                                                                                                                                              \
+  int piso_mg_pcg_solve_prepared_guess##SUFFIX(int nx, int ny, int periodic_x, int periodic_y, const void* hierarchy, size_t hierarchy_bytes,                    \
+                                               const double* divergence, const double* x0, double* x_out, float accuracy, int max_iterations,                    \
+                                               int rank_deficient, int residual_reset, int sweeps, int* iterations_out, void* workspace,                         \
+                                               size_t workspace_bytes, piso_stream_t stream) {                                                                   \
+    return piso::mg_solve_prepared<C>(nx, ny, periodic_x, periodic_y, hierarchy, hierarchy_bytes, divergence, x_out, accuracy, max_iterations, rank_deficient,   \
+                                      residual_reset, sweeps, iterations_out, workspace, workspace_bytes, stream, x0);                                           \
   }                                                                                                                                                              \
   int piso_mg_vcycle_prepared##SUFFIX(int nx, int ny, int periodic_x, int periodic_y, const void* hierarchy, size_t hierarchy_bytes, const double* r_in,         \
                                       double* z_out, int sweeps, void* workspace, size_t workspace_bytes, piso_stream_t stream) {                                \

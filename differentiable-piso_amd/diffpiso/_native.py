@@ -75,6 +75,13 @@ lib.piso_mg_vcycle_c32_f64.argtypes = lib.piso_mg_vcycle_f64.argtypes
 lib.piso_mg_vcycle_c32_f64.restype = _i
 lib.piso_mg_level_c32_f64.argtypes = lib.piso_mg_level_f64.argtypes
 lib.piso_mg_level_c32_f64.restype = _i
+for _s in ("_f64", "_c32_f64"):            # (x0 after the divergence; NULL: the namesake's call)
+    getattr(lib, "piso_mg_pcg_solve_guess" + _s).argtypes = [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _ip, _vp, _sz, _vp]
+    getattr(lib, "piso_mg_pcg_solve_guess" + _s).restype = _i
+    getattr(lib, "piso_mg_pcg_solve_prepared_guess" + _s).argtypes = [_i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _f, _i, _i, _i, _i, _ip, _vp, _sz, _vp]
+    getattr(lib, "piso_mg_pcg_solve_prepared_guess" + _s).restype = _i
+lib.piso_mg_last_guess.argtypes = []
+lib.piso_mg_last_guess.restype = _i
 lib.piso_mg_hierarchy_bytes.argtypes = [_i, _i, _i]
 lib.piso_mg_hierarchy_bytes.restype = _sz
 lib.piso_mg_solve_workspace_bytes.argtypes = [_i, _i, _i]
@@ -338,3 +345,8 @@ def mg_slab_plan(nx, ny, world, gather_cells=0):
 def mg_last_dispatch():
     """What this thread's last multigrid solve / cycle ran (include/piso_hip.h: piso_mg_last_dispatch), as a dict; {} if none."""
     return _last_dispatch(lib.piso_mg_last_dispatch, "piso_mg_last_dispatch", MG_DISPATCH_FIELDS)
+
+
+def mg_last_guess():
+    """What this thread's last multigrid solve did with its guess (include/piso_hip.h: piso_mg_last_guess): 0 none given, 1 accepted, 2 rejected."""
+    return int(lib.piso_mg_last_guess())

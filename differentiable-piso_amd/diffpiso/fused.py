@@ -212,9 +212,11 @@ def divergence(faces, geom, per_x, per_y):
 
 
 def piso_step_fused(velocity, pressure, pressure_inc1, pressure_inc2, dt, sim, dirichlet_values, viscosity_field, forcing_term,
-                    unrolling_step, warn, full_output):
+                    unrolling_step, warn, full_output, increments_out=None):
     """piso_step (diffpiso/piso_tf.py:11-81) on the fused kernels.  Called by piso.piso_step; same arguments and results.  With
-    `sim.sharding` (sharding.StepSharding) the fields are SlabStaggered / SlabCentered: the rank's stored rows (local storage)."""
+    `sim.sharding` (sharding.StepSharding) the fields are SlabStaggered / SlabCentered: the rank's stored rows (local storage).
+    A pressure solver with `use_guess` (PisoPressureSolverMultigrid(use_guess=True)) starts corrector 1 from `pressure_inc1` and corrector 2
+    from `pressure_inc2` - the previous step's solutions of the same two systems; `increments_out` (a list) receives this step's two."""
     from .piso import _CsrMatVec, assemble_from_padded
     from .solvers import LinearSolverCudaMultiBicgstabILU
     ny, nx = [int(r) for r in velocity.resolution]
@@ -283,7 +285,11 @@ def piso_step_fused(velocity, pressure, pressure_inc1, pressure_inc2, dt, sim, d
     dx_factor = dxdy / (float(velocity.dx[0]) ** 2)
     with torch.no_grad():
         a0 = a0_vfirst(Aflat, geom, dx_factor)
-    p1, _, Lap1 = sim.pressure_solver.solve_flat(a0, v1div, sim, unrolling_step=unrolling_step)
+    use_guess = getattr(sim.pressure_solver, "use_guess", False)
+    if use_guess:
+        p1, _, Lap1 = sim.pressure_solver.solve_flat(a0, v1div, sim, unrolling_step=unrolling_step, guess=pressure_inc1.data)
+    else:
+        p1, _, Lap1 = sim.pressure_solver.solve_flat(a0, v1div, sim, unrolling_step=unrolling_step)
     geom1 = geom if pressure_inc1.extrapolation == pressure.extrapolation else Geometry(nx, ny, velocity.dx, beta, pressure_inc1.extrapolation, acc, sh)
     s2, delta = _FaceOp.apply(FACE_CORR1, geom1, p1, star, None, None, Aflat, None)
 
@@ -291,7 +297,10 @@ def piso_step_fused(velocity, pressure, pressure_inc1, pressure_inc2, dt, sim, d
     m_delta = _CsrMatVec.apply(delta, matrix_values, row_pointers, column_indices, nx, ny, sh, (per_x, per_y))
     H, Hb = _HContribution.apply(m_delta, delta, Aflat, geom)
     H_div = divergence(Hb, geom, per_x, per_y)
-    p2, _, Lap2 = sim.pressure_solver.solve_flat(a0, H_div, sim, unrolling_step=1000 + unrolling_step)
+    if use_guess:
+        p2, _, Lap2 = sim.pressure_solver.solve_flat(a0, H_div, sim, unrolling_step=1000 + unrolling_step, guess=pressure_inc2.data)
+    else:
+        p2, _, Lap2 = sim.pressure_solver.solve_flat(a0, H_div, sim, unrolling_step=1000 + unrolling_step)
     geom2 = geom if pressure_inc2.extrapolation == pressure.extrapolation else Geometry(nx, ny, velocity.dx, beta, pressure_inc2.extrapolation, acc, sh)
     s3 = _FaceOp.apply(FACE_FINAL, geom2, p2, s2, H, None, Aflat, None)
     velocity_s3 = faces_to_grid(s3, geom, velocity.box, velocity.extrapolation)
@@ -302,6 +311,8 @@ def piso_step_fused(velocity, pressure, pressure_inc1, pressure_inc2, dt, sim, d
     else:
         pressure_inc1, pressure_inc2 = pressure_inc1.rewrap(p1), pressure_inc2.rewrap(p2)
     pressure = pressure + pressure_inc1 + pressure_inc2                             # :75
+    if increments_out is not None:
+        increments_out[:] = [pressure_inc1, pressure_inc2]
 
     if full_output:
         grid = (lambda t: t) if sh is not None else (lambda t: faces_to_grid(t, geom, velocity.box, velocity.extrapolation).staggered_tensor())

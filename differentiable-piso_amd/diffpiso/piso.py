@@ -221,10 +221,11 @@ def explicit_H_csr(matrix_values, row_pointers, column_indices, velocity, stagge
 
 
 def piso_step(velocity, pressure, pressure_inc1, pressure_inc2, dt, simulation_physics, dirichlet_values,
-              viscosity_field=None, forcing_term=None, unrolling_step=0, warn=None, full_output=False, **kwargs):
+              viscosity_field=None, forcing_term=None, unrolling_step=0, warn=None, full_output=False, increments_out=None, **kwargs):
     """diffpiso/piso_tf.py:11-81 on the fused HIP glue kernels (`fused.piso_step_fused`: one launch per statement of the reference's
     step, forward and reverse mode with the reference's custom gradients).  There is no other implementation in the package: the
-    statement-by-statement torch transcription that the tests hold the fused path to lives in tests/piso_step_transcription.py."""
+    statement-by-statement torch transcription that the tests hold the fused path to lives in tests/piso_step_transcription.py.
+    increments_out: a list that receives this step's two pressure increments (what a solver with `use_guess` starts the next step from)."""
     from . import stencils
     if not (velocity.flat if hasattr(velocity, "flat") else velocity.data[0].data).is_cuda:
         raise N.PisoNativeError("piso_step: the fields must live on the GPU (the PISO path has no CPU implementation)")
@@ -233,4 +234,4 @@ def piso_step(velocity, pressure, pressure_inc1, pressure_inc2, dt, simulation_p
                          "transposes are available through the stencil functions only")
     from .fused import piso_step_fused
     return piso_step_fused(velocity, pressure, pressure_inc1, pressure_inc2, dt, simulation_physics, dirichlet_values,
-                           viscosity_field, forcing_term, unrolling_step, warn, full_output)
+                           viscosity_field, forcing_term, unrolling_step, warn, full_output, increments_out)

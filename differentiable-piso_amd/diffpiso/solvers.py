@@ -486,9 +486,14 @@ class _PressureSolveFn(torch.autograd.Function):
     applied to the incoming gradient (the operator is symmetric)."""
 
     @staticmethod
-    def forward(ctx, divergence, L, solver, nx, ny, per_x, per_y, rank_deficient):
-        x, it = solver._cg(nx, ny, per_x, per_y, L, divergence, _scalar(solver.accuracy), solver.max_iterations,
-                           rank_deficient, solver.residual_reset)
+    def forward(ctx, divergence, L, solver, nx, ny, per_x, per_y, rank_deficient, guess=None):
+        # (`guess`: only a solver that asks for one is handed one - PisoPressureSolverMultigrid(use_guess=True); never differentiated)
+        if guess is None:
+            x, it = solver._cg(nx, ny, per_x, per_y, L, divergence, _scalar(solver.accuracy), solver.max_iterations,
+                               rank_deficient, solver.residual_reset)
+        else:
+            x, it = solver._cg(nx, ny, per_x, per_y, L, divergence, _scalar(solver.accuracy), solver.max_iterations,
+                               rank_deficient, solver.residual_reset, x0=guess)
         solver.last_iterations = it
         solver.stats.add("solves", 1)
         solver.stats.add("iterations", it)
@@ -506,7 +511,7 @@ class _PressureSolveFn(torch.autograd.Function):
         solver.last_adjoint_iterations = it
         solver.stats.add("adjoint_solves", 1)
         solver.stats.add("adjoint_iterations", it)
-        return g.reshape(shape).to(torch.float32), None, None, None, None, None, None, None
+        return g.reshape(shape).to(torch.float32), None, None, None, None, None, None, None, None
 
 
 class PisoPressureSolverCudaCustom(PoissonSolver):
@@ -564,8 +569,12 @@ class PisoPressureSolverCudaCustom(PoissonSolver):
         a0 = flatten_staggered_data(scaling_field, coord_flip=False).detach().to(torch.float32)   # v first (:70)
         return self.solve_flat(a0, divergence, simulation_physics, unrolling_step=unrolling_step)
 
-    def solve_flat(self, a0_vfirst, divergence, simulation_physics, unrolling_step=0):
+    def _guess_for_solve(self, guess, divergence):
+        return None                                          # (init_with_zeros=True; PisoPressureSolverMultigrid(use_guess=True) overrides)
+
+    def solve_flat(self, a0_vfirst, divergence, simulation_physics, unrolling_step=0, guess=None):
         """`solve` with the face coefficients already in the op's layout (flat, v faces first, :70); used by the fused step."""
+        guess = self._guess_for_solve(guess, divergence)
         dt = torch.float64 if self.cast_to_double else torch.float32
         sharding = getattr(simulation_physics, "sharding", None)
         ny, nx = (int(divergence.shape[1]), int(divergence.shape[2])) if sharding is None else (sharding.ny, sharding.nx)
@@ -591,7 +600,10 @@ class PisoPressureSolverCudaCustom(PoissonSolver):
             active, accessible = loc["active"], loc["accessible"]
         L = self._laplace(nx, ny, active, accessible, a0, dt, sharding)
         per_y, per_x = [bool(b) for b in simulation_physics.bool_periodic]          # given (y, x), flipped for the op (:95)
-        pressure, iteration = _PressureSolveFn.apply(divergence, L, self, nx, ny, per_x, per_y, rank_def)
+        if guess is None:
+            pressure, iteration = _PressureSolveFn.apply(divergence, L, self, nx, ny, per_x, per_y, rank_def)
+        else:
+            pressure, iteration = _PressureSolveFn.apply(divergence, L, self, nx, ny, per_x, per_y, rank_def, guess)
         self.solve_count = self.solve_count + .001
         return pressure, iteration, L
 
@@ -617,18 +629,48 @@ def mg_workspace(nx, ny, device, cycle_dtype=torch.float64):
     return N.workspace(nbytes, device, "mg")
 
 
-def mg_solve_native(nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset, sweeps=2, cycle_dtype=torch.float64):
+def _mg_guess(x0, div):
+    """The guess of a multigrid solve as the library takes it - detached, float64, flat - or the refusal of one that does not fit `div`
+    (before any launch)."""
+    if not isinstance(x0, torch.Tensor):
+        raise TypeError("a multigrid guess must be a tensor (got %s)" % type(x0).__name__)
+    if not x0.is_floating_point():
+        raise TypeError("a multigrid guess must be a floating-point tensor (got %s)" % x0.dtype)
+    if x0.numel() != div.numel():
+        raise ValueError("a multigrid guess must have the solution's %d cells (got %d)" % (div.numel(), x0.numel()))
+    if x0.device != div.device:
+        raise ValueError("a multigrid guess must live on the right-hand side's device %s (got %s)" % (div.device, x0.device))
+    return x0.detach().reshape(-1).to(torch.float64).contiguous()
+
+
+def _mg_x_out(x_out, div):
+    if x_out is None:
+        return torch.empty_like(div)
+    if x_out.dtype != torch.float64 or x_out.numel() != div.numel() or x_out.device != div.device or not x_out.is_contiguous():
+        raise ValueError("x_out must be a contiguous float64 tensor of the solution's %d cells on %s" % (div.numel(), div.device))
+    return x_out
+
+
+def mg_solve_native(nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset, sweeps=2, cycle_dtype=torch.float64,
+                    x0=None, x_out=None):
     """-> (x, iterations): multigrid-preconditioned CG on the system cg_solve_native solves (csrc/mg.hip; fp64).  cycle_dtype=torch.float32:
-    the same fp64 iteration around a float32 V-cycle (csrc/mg_f32.h)."""
+    the same fp64 iteration around a float32 V-cycle (csrc/mg_f32.h).  x0: a guess the solve starts from where its residual is below the
+    right-hand side, else from zero (csrc/mg_guess.h; N.mg_last_guess() says which); x_out: where the result goes (x0 itself is allowed)."""
     if L.dtype != torch.float64:
         raise N.PisoNativeError("the multigrid pressure solver is fp64 only; use the plain CG (cg_solve_native) for float32")
-    fn = N.lib.piso_mg_pcg_solve_f64 if _mg_cycle_elem(cycle_dtype) == 8 else N.lib.piso_mg_pcg_solve_c32_f64
+    sfx = "_f64" if _mg_cycle_elem(cycle_dtype) == 8 else "_c32_f64"
     div = div.reshape(-1).to(torch.float64).contiguous()
-    x = torch.empty_like(div)
+    guess = None if x0 is None else (x0 if x0 is x_out else _mg_guess(x0, div))
+    x = _mg_x_out(x_out, div)
     ws = mg_workspace(nx, ny, div.device, cycle_dtype)
     it = C.c_int(0)
-    st = fn(nx, ny, int(per_x), int(per_y), N.ptr(L), N.ptr(div), N.ptr(x), C.c_float(accuracy), int(max_iterations),
-            int(bool(rank_deficient)), int(residual_reset), int(sweeps), C.byref(it), N.ptr(ws), C.c_size_t(ws.numel()), N.stream_ptr())
+    head = (nx, ny, int(per_x), int(per_y), N.ptr(L), N.ptr(div))
+    tail = (N.ptr(x), C.c_float(accuracy), int(max_iterations), int(bool(rank_deficient)), int(residual_reset), int(sweeps), C.byref(it), N.ptr(ws),
+            C.c_size_t(ws.numel()), N.stream_ptr())
+    if guess is None:
+        st = getattr(N.lib, "piso_mg_pcg_solve" + sfx)(*(head + tail))
+    else:
+        st = getattr(N.lib, "piso_mg_pcg_solve_guess" + sfx)(*(head + (N.ptr(guess),) + tail))
     N.check(st, "piso_mg_pcg_solve")
     return x, it.value
 
@@ -711,13 +753,23 @@ def mg_prepare_native(nx, ny, per_x, per_y, L, rank_deficient, cycle_dtype=torch
 
 def mg_solve_prepared_native(h, div, accuracy, max_iterations, residual_reset, sweeps=2):
     """-> (x, iterations) of mg_solve_native on the matrix `h` was prepared from, bit for bit, without the set-up and its host look."""
+    return mg_solve_prepared_guess_native(h, div, None, accuracy, max_iterations, residual_reset, sweeps)
+
+
+def mg_solve_prepared_guess_native(h, div, x0, accuracy, max_iterations, residual_reset, sweeps=2, x_out=None):
+    """mg_solve_prepared_native from the guess `x0` (None: no guess), x and count of mg_solve_native(..., x0=x0) bit for bit; x_out as there."""
     div = div.reshape(-1).to(torch.float64).contiguous()
-    x = torch.empty_like(div)
+    guess = None if x0 is None else (x0 if x0 is x_out else _mg_guess(x0, div))
+    x = _mg_x_out(x_out, div)
     ws = h.scratch()
     it = C.c_int(0)
-    fn = getattr(N.lib, "piso_mg_pcg_solve_prepared" + h._suffix())
-    st = fn(h.nx, h.ny, int(h.per_x), int(h.per_y), N.ptr(h.buf), C.c_size_t(h.buf.numel()), N.ptr(div), N.ptr(x), C.c_float(accuracy),
-            int(max_iterations), int(h.rank_deficient), int(residual_reset), int(sweeps), C.byref(it), N.ptr(ws), C.c_size_t(ws.numel()), N.stream_ptr())
+    head = (h.nx, h.ny, int(h.per_x), int(h.per_y), N.ptr(h.buf), C.c_size_t(h.buf.numel()), N.ptr(div))
+    tail = (N.ptr(x), C.c_float(accuracy), int(max_iterations), int(h.rank_deficient), int(residual_reset), int(sweeps), C.byref(it), N.ptr(ws),
+            C.c_size_t(ws.numel()), N.stream_ptr())
+    if guess is None:
+        st = getattr(N.lib, "piso_mg_pcg_solve_prepared" + h._suffix())(*(head + tail))
+    else:
+        st = getattr(N.lib, "piso_mg_pcg_solve_prepared_guess" + h._suffix())(*(head + (N.ptr(guess),) + tail))
     N.check(st, "piso_mg_pcg_solve_prepared")
     return x, it.value
 
@@ -764,11 +816,22 @@ class PisoPressureSolverMultigrid(PisoPressureSolverCudaCustom):
     (48 bytes a cell) and the coarser levels (fp64 cycle: 16 more) or, in float32 mode, the float32 levels (32 more).  `stats` counts
     hierarchy_builds, hierarchy_reuses and laplace_builds in either mode.  Refused (naming reuse_hierarchy=False) with a slab communicator
     in use: sharded hierarchies are not kept.
+    use_guess=True (opt-in, one GPU) starts a forward solve from the guess it is handed instead of from zero (csrc/mg_guess.h): `solve(...,
+    guess, ...)` and `solve_flat(..., guess=...)` pass it on - detached and cast to float64, so no gradient flows through it; a tensor of
+    another size or device is refused before any launch - piso_step hands corrector 1 and 2 the `pressure_inc1` / `pressure_inc2` it
+    receives, and run_piso_steps / unroll_piso_steps hand step n's increments to step n + 1.  The device keeps a guess only where
+    max|b' - L x0| < max|b'| (b' the right-hand side the iteration sees): in a start-up transient the previous increment is a worse start
+    than zero, and such a guess, like one holding a NaN, becomes the solve from zero, bit for bit.  A settled flow saves 1 - 2 of its 3 - 6
+    iterations a solve (DESIGN.md 3.7 has the tables and what two more launches cost a small grid).  With a guess the result agrees with the
+    default's to the tolerance the solve is run at, not bit for bit.  `stats` of a solver built with the option counts guesses_accepted and
+    guesses_rejected.  The adjoint solve always starts from zero (the previous adjoint is no better a start).  Works with reuse_hierarchy
+    and both cycle_dtypes; refused (naming use_guess=False) with a slab communicator in use.  Off, `guess` is ignored as the plain solver
+    ignores it.
     Forward and adjoint solves, `last_iterations`, `stats` and SimulationParameters(pressure_solver=...) work as with the plain
     solver."""
 
     def __init__(self, dx, accuracy=1e-5, max_iterations=2000, residual_reset=10, randomized_restarts=0, cast_to_double=True,
-                 smoothing_sweeps=2, cycle_dtype=torch.float64, reuse_hierarchy=False):
+                 smoothing_sweeps=2, cycle_dtype=torch.float64, reuse_hierarchy=False, use_guess=False):
         if not cast_to_double:
             raise ValueError("PisoPressureSolverMultigrid is fp64 only (cast_to_double=True); use PisoPressureSolverCudaCustom for float32")
         if not 1 <= int(smoothing_sweeps) <= 8:
@@ -780,9 +843,10 @@ class PisoPressureSolverMultigrid(PisoPressureSolverCudaCustom):
         self.smoothing_sweeps = int(smoothing_sweeps)
         self.cycle_dtype = cycle_dtype
         self.reuse_hierarchy = bool(reuse_hierarchy)
+        self.use_guess = bool(use_guess)
         self._hierarchy = None           # the last MgHierarchy built (reuse_hierarchy)
         self._laplace_cache = None       # (key, the tensors the key points at, L) of the last solve_flat (reuse_hierarchy)
-        for k in ("hierarchy_builds", "hierarchy_reuses", "laplace_builds"):
+        for k in ("hierarchy_builds", "hierarchy_reuses", "laplace_builds") + (("guesses_accepted", "guesses_rejected") if self.use_guess else ()):
             dict.__setitem__(self.stats, k, 0)
 
     def drop_hierarchy(self):
@@ -802,7 +866,29 @@ class PisoPressureSolverMultigrid(PisoPressureSolverCudaCustom):
             self._laplace_cache = (key, (a0, active, accessible), L)      # (the tensors stay alive: their pointers cannot be handed out again)
         return self._laplace_cache[2]
 
-    def _cg(self, nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset):
+    def solve(self, scaling_field, divergence, guess, enable_backprop, simulation_physics, offset=0, unrolling_step=0):
+        # (use_guess off: `guess` is ignored like the plain solver's)
+        scaling_field = scaling_field if isinstance(scaling_field, StaggeredGrid) else StaggeredGrid(scaling_field)
+        a0 = flatten_staggered_data(scaling_field, coord_flip=False).detach().to(torch.float32)
+        guess = getattr(guess, "data", guess) if self.use_guess else None       # (a CenteredGrid or its tensor)
+        return self.solve_flat(a0, divergence, simulation_physics, unrolling_step=unrolling_step, guess=guess)
+
+    def _slabs_in_use(self):
+        # (option slab_force: a communicator of ONE rank still runs the slab solve - a ring of one, tests)
+        return self.slab_comm is not None and (getattr(self.slab_comm, "world", 1) > 1 or getattr(self.slab_comm, "sharded", False) or
+                                               N.get_option("slab_force") > 0)
+
+    def _guess_for_solve(self, guess, divergence):
+        if not self.use_guess or guess is None:
+            return None
+        if self._slabs_in_use():             # (before the guess is looked at: a sharded step's fields have the rank's cells only)
+            self._refuse_guess_on_slabs()
+        return _mg_guess(guess, divergence)                  # (detached, float64; a wrong size or device is refused here, before any launch)
+
+    def _refuse_guess_on_slabs(self):
+        raise N.PisoNativeError("PisoPressureSolverMultigrid: a guess is taken on one GPU only; a solve cut into y-slabs needs use_guess=False")
+
+    def _cg(self, nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset, x0=None):
         from .distributed import SlabCommunicator, mg_solve_slab, mg_solve_slab_local
         if self.slab_comm is not None and not isinstance(self.slab_comm, SlabCommunicator):
             raise N.PisoNativeError("PisoPressureSolverMultigrid cuts a solve into y-slabs over a distributed.SlabCommunicator only; anything else "
@@ -811,7 +897,9 @@ class PisoPressureSolverMultigrid(PisoPressureSolverCudaCustom):
             raise N.PisoNativeError("PisoPressureSolverMultigrid is fp64 only; use PisoPressureSolverCudaCustom for float32")
         # (option slab_force: a communicator of ONE rank still runs the slab solve - a ring of one, tests)
         if self.slab_comm is not None and (self.slab_comm.world > 1 or N.get_option("slab_force") > 0):
-            if self.reuse_hierarchy:         # (before the communicator is touched)
+            if self.use_guess:               # (before the communicator is touched)
+                self._refuse_guess_on_slabs()
+            if self.reuse_hierarchy:
                 raise N.PisoNativeError("PisoPressureSolverMultigrid: a hierarchy is kept on one GPU only; a solve cut into y-slabs needs "
                                         "reuse_hierarchy=False")
             # (the plan is asked on the host, before the communicator is touched: g = 0 replicates the whole cycle, where float32 gains nothing)
@@ -829,10 +917,13 @@ class PisoPressureSolverMultigrid(PisoPressureSolverCudaCustom):
                 return x, it
             return mg_solve_slab(self.slab_comm, nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset,
                                  self.smoothing_sweeps, cycle_dtype=self.cycle_dtype)
+        if not self.use_guess:
+            x0 = None
         if not self.reuse_hierarchy:
             self.stats.add("hierarchy_builds", 1)
-            return mg_solve_native(nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset, self.smoothing_sweeps,
-                                   self.cycle_dtype)
+            out = mg_solve_native(nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank_deficient, residual_reset, self.smoothing_sweeps,
+                                  self.cycle_dtype, x0=x0)
+            return self._count_guess(x0, out)
         h = self._hierarchy
         if h is None or h.key != MgHierarchy.key_of(L, nx, ny, per_x, per_y, rank_deficient, self.cycle_dtype):
             self._hierarchy = None           # (freed before its successor is allocated; a refused prepare leaves none)
@@ -840,7 +931,14 @@ class PisoPressureSolverMultigrid(PisoPressureSolverCudaCustom):
             self.stats.add("hierarchy_builds", 1)
         else:
             self.stats.add("hierarchy_reuses", 1)
-        return mg_solve_prepared_native(h, div, accuracy, max_iterations, residual_reset, self.smoothing_sweeps)
+        return self._count_guess(x0, mg_solve_prepared_guess_native(h, div, x0, accuracy, max_iterations, residual_reset, self.smoothing_sweeps))
+
+    def _count_guess(self, x0, out):
+        if x0 is not None:
+            for k in ("guesses_accepted", "guesses_rejected"):       # (use_guess switched on after construction)
+                dict.setdefault(self.stats, k, 0)
+            self.stats.add("guesses_accepted" if N.mg_last_guess() == 1 else "guesses_rejected", 1)
+        return out
 
     @staticmethod
     def last_dispatch():

@@ -55,6 +55,9 @@ def unroll_piso_steps(velocity, pressure, dt, sim_physics, step_count=1, loss_in
     # piso_cuda_pressure_solver.py:95 - so they are built once per unroll: two fills instead of four launches per step)
     pressure_inc1 = _centered_like(pressure, torch.full_like(pressure.data, 5e-13))
     pressure_inc2 = _centered_like(pressure, torch.full_like(pressure.data, 1e-12))
+    # a solver that starts from a guess (PisoPressureSolverMultigrid(use_guess=True)) gets step n's increments in step n + 1, detached: no
+    # gradient flows through a guess
+    carry = [] if getattr(sim_physics.pressure_solver, "use_guess", False) else None
     for i in range(step_count):
         if i > 0 and loss_influence_range and i % loss_influence_range == 0:          # :436-438
             velnew = _staggered_like(velnew, velnew.staggered_tensor().detach())
@@ -63,7 +66,10 @@ def unroll_piso_steps(velocity, pressure, dt, sim_physics, step_count=1, loss_in
             dirichlet_values = dirichlet_update_fn(i, sim_physics.dirichlet_values)
         forcing = forcing_fn(i, velnew, pnew) if forcing_fn is not None else None
         vel_piso, p_piso, warn[i] = piso_step(velnew, pnew, pressure_inc1, pressure_inc2, dt, sim_physics, dirichlet_values,
-                                              viscosity_field=viscosity_field, forcing_term=forcing, unrolling_step=i)
+                                              viscosity_field=viscosity_field, forcing_term=forcing, unrolling_step=i,
+                                              **({} if carry is None else {"increments_out": carry}))
+        if carry:
+            pressure_inc1, pressure_inc2 = (_centered_like(inc, inc.data.detach()) for inc in carry)
         velocity_all_steps.append(vel_piso)
         pressure_all_steps.append(p_piso)
         # (:472-473 re-wraps the step's results in new grids around the same data; the step's own result objects carry their flat face

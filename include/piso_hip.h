@@ -457,6 +457,34 @@ int piso_mg_vcycle_slab_emulated_c32_f64(int slabs, int nx, int ny, int periodic
 int piso_mg_level_slab_emulated_c32_f64(int slabs, int rank, int nx, int ny, int periodic_x, int periodic_y, const double* laplace, int level,
                                         int* nx_out, int* rows_out, double* laplace_level_out, void* workspace, size_t workspace_bytes,
                                         piso_stream_t stream);
+/* Starting from a GUESS (csrc/mg_guess.h; opt-in, one GPU).  The four *_guess_* entries take the arguments of their namesakes plus
+ * `x0` after `divergence`: nx * ny doubles, the same pointer as x_out or disjoint from it.  x0 NULL is the namesake's call.  Otherwise, with
+ * b' the right-hand side the iteration sees (zero on absent cells, its mean over the present cells removed where rank_deficient) and x0~ =
+ * x0 on the present cells, 0 elsewhere (x0 is not read for its values on absent cells), the device forms r_g = b' - L x0~ and ACCEPTS the
+ * guess iff max|r_g| < max|b'| (strict; false for a NaN or Inf in r_g and for x0 = 0): the solve then starts from x = x0~, r = r_g, and is
+ * done with 0 iterations where max|r_g| < accuracy already.  A REJECTED guess starts from x = 0, r = b': the namesake's x, count and
+ * piso_mg_last_dispatch record bit for bit (a solve without an accepted guess always runs at least one iteration).  The guard is there
+ * because the previous time step's solution is a worse start than zero in a start-up transient - its residual then exceeds the right-hand
+ * side.  The iteration, its stopping rule and the constant mode are untouched (the end of a rank-deficient solve replaces
+ * the mean of x, so the mean of x0 is immaterial); workspace sizes are those of the namesakes; the cost is two more small launches.
+ * Adjoint solves and the slab entries take no guess.
+ * piso_mg_last_guess: what the calling thread's last piso_mg_pcg_solve* call (slab entries included) did with its guess - 0 none given, 1
+ * accepted, 2 rejected; reset to 0 when such a call begins and filled when its solve returns, so a refused or failed call reports 0. */
+int piso_mg_pcg_solve_guess_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence, const double* x0,
+                                double* x_out, float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps,
+                                int* iterations_out, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+int piso_mg_pcg_solve_guess_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence, const double* x0,
+                                    double* x_out, float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps,
+                                    int* iterations_out, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+int piso_mg_pcg_solve_prepared_guess_f64(int nx, int ny, int periodic_x, int periodic_y, const void* hierarchy, size_t hierarchy_bytes,
+                                         const double* divergence, const double* x0, double* x_out, float accuracy, int max_iterations,
+                                         int rank_deficient, int residual_reset, int sweeps, int* iterations_out, void* workspace,
+                                         size_t workspace_bytes, piso_stream_t stream);
+int piso_mg_pcg_solve_prepared_guess_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const void* hierarchy, size_t hierarchy_bytes,
+                                             const double* divergence, const double* x0, double* x_out, float accuracy, int max_iterations,
+                                             int rank_deficient, int residual_reset, int sweeps, int* iterations_out, void* workspace,
+                                             size_t workspace_bytes, piso_stream_t stream);
+int piso_mg_last_guess(void);
 /* What the calling thread's last multigrid solve / cycle ran (fp64, float32 cycle or slab); returns the number of fields (8):
  *    0 levels         levels of the hierarchy
  *    1 tail_first     first level that ran inside the one-workgroup tail kernel (-1: none)
