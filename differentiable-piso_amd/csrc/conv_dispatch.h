@@ -24,6 +24,18 @@ inline ConvGeom conv_geom(int H, int W, int cin, int cout, int ks, int pad) {
   return ConvGeom{H, W, H + 2 * pad - ks + 1, W + 2 * pad - ks + 1, pad, cin, cout};
 }
 
+// The general geometry of piso_conv2d_forward_ex / piso_conv2d_wgrad_ex (the *_ex_kernel instances): padding per axis, and per axis
+//     out[y][x][co] = sum over (ky, kx, ci) of in[Y][X][ci] w[ky][kx][ci][co],  Y = y + ky - pad_y, X = x + kx - pad_x
+// where a coordinate outside the image contributes nothing on a zero-padded axis and is taken modulo the extent on a WRAPPED one.
+struct ConvGeomEx {
+  int H, W;
+  int Ho, Wo;
+  int pad_y, pad_x;
+  int wrap_h, wrap_w;  // what a coordinate that left the image is moved by: H / W on a wrapped axis, 0 on a zero-padded one
+  int cin, cout;
+};
+constexpr int kConvGeometryFields = 4;   // piso_conv_last_geometry: pad_y, pad_x, wrap_y, wrap_x
+
 constexpr int round_up(int v, int m) { return (v + m - 1) / m * m; }
 constexpr int ceil_div(int v, int m) { return (v + m - 1) / m; }
 constexpr int padded_cin(int cin) { return cin <= 4 ? 4 : round_up(cin, 16); }
@@ -79,12 +91,18 @@ struct ConvQuery {
   bool null_ptr;                     // one of the entry's pointers is NULL
   bool operands_off16, result_off16; // not 16-byte aligned: `in` or the second operand (w_laid_out / grad_out); wgrad: dw or workspace
   size_t workspace_bytes;            // wgrad
+  // the *_ex entries: `pad` is pad_y, and
+  bool ex = false;
+  int pad_x = 0;
+  int wrap_y = 0, wrap_x = 0;        // != 0: the axis is periodic
 };
 constexpr int kConvRecordFields = 15;
 struct ConvPlan {
   int status = PISO_OK;              // != PISO_OK: the call is refused with `msg`, nothing else of the plan is to be used
   const char* msg = nullptr;
-  ConvGeom g;
+  ConvGeom g;                        // (a *_ex plan: Ho, Wo, cin, cout as launched; pad = pad_y)
+  bool ex = false;                   // the *_ex_kernel twins run, with
+  ConvGeomEx gx;
   // the dispatch record (include/piso_hip.h: piso_conv_last_dispatch; with g.Ho, g.Wo) = the launch of the main kernel: grid (grid_x, grid_y), block
   int entry, KS, C, NT, IPW, family, leaky, grid_x, grid_y, block, rows_per_block, nblocks, reducer;
   int reduce_grid;                   // gridDim.x of the reducer
@@ -99,8 +117,25 @@ inline ConvPlan conv_plan(const ConvQuery& q) {
   ConvPlan p{};
   const auto refuse = [&p](const char* msg) { p.status = PISO_ERR_INVALID_ARG; p.msg = msg; return p; };
   p.g = conv_geom(q.H, q.W, q.cin, q.cout, q.ks, q.pad);
+  p.ex = q.ex;
+  if (q.ex) {
+    p.g.Wo = q.W + 2 * q.pad_x - q.ks + 1;
+    p.gx = ConvGeomEx{q.H, q.W, p.g.Ho, p.g.Wo, q.pad, q.pad_x, q.wrap_y ? q.H : 0, q.wrap_x ? q.W : 0, q.cin, q.cout};
+  }
   const ConvGeom& g = p.g;
   const int cin = q.cin, cout = q.cout, ks = q.ks;
+  // the two rules of a wrapped axis (after the entry's own argument checks, below)
+  const auto wrap_refusal = [&q]() -> const char* {
+    const bool fwd = q.entry == CE_FORWARD;
+    if (!q.ex) return nullptr;
+    if ((q.wrap_y && q.pad != q.ks / 2) || (q.wrap_x && q.pad_x != q.ks / 2))
+      return fwd ? "piso_conv2d_forward_ex: invalid argument (a wrapped axis must have pad == ks / 2: it keeps its extent, and the adjoint is again such a convolution)"
+                 : "piso_conv2d_wgrad_ex: invalid argument (a wrapped axis must have pad == ks / 2: it keeps its extent, and the adjoint is again such a convolution)";
+    if ((q.wrap_y && q.H < q.pad) || (q.wrap_x && q.W < q.pad_x))
+      return fwd ? "piso_conv2d_forward_ex: invalid argument (a wrapped axis must have an extent >= its pad: an index wraps at most once)"
+                 : "piso_conv2d_wgrad_ex: invalid argument (a wrapped axis must have an extent >= its pad: an index wraps at most once)";
+    return nullptr;
+  };
   const bool sizes_ok = g.Ho >= 1 && g.Wo >= 1 && cin >= 1 && cout >= 1 && cout <= 64 && cin <= 64;
   const bool lds = q.conv_lds != 0;                          // (option conv_lds 0: the direct kernels)
   p.entry = q.entry; p.KS = ks; p.NT = round_up(cout, 16) / 16; p.grid_y = 1; p.block = kConvBlock;
@@ -111,12 +146,14 @@ inline ConvPlan conv_plan(const ConvQuery& q) {
     if (conv_fwd_loads16(p.C) && q.operands_off16)
       return refuse("piso_conv2d_forward: invalid argument (with more than 4 input channels `in` and `w_laid_out` must be 16-byte aligned)");
     if (!conv_with_shape<kConvFwd>(ks, p.C, p.NT, [](auto) {})) return refuse("piso_conv2d_forward: this (kernel size, channels) combination is not instantiated");
+    if (const char* why = wrap_refusal()) return refuse(why);
     p.family = lds && conv_fwd_has_lds(ks, p.C) ? CF_FWD_LDS : CF_FWD_DIRECT;
     p.leaky = q.leaky != 0;
     p.grid_x = ceil_div(ceil_div(g.Wo, 64) * g.Ho, kConvBlock / 64);       // a wave owns a tile of 64 pixels of one output row
     return p;
   }
   if (q.null_ptr || !sizes_ok || q.workspace_bytes < conv_wgrad_workspace_bytes(ks, cin, cout)) return refuse("piso_conv2d_wgrad: invalid argument");
+  if (const char* why = wrap_refusal()) return refuse(why);
   p.C = round_up(cin, 16) / 16;
   p.reducer = conv_wg_reducer(cout);
   if ((p.reducer == 4 && q.result_off16) || (conv_wg_loads16(cin, cout) && q.operands_off16))

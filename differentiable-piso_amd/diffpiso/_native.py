@@ -159,6 +159,12 @@ lib.piso_conv2d_forward.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _
 lib.piso_conv2d_forward.restype = _i
 lib.piso_conv2d_wgrad.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]
 lib.piso_conv2d_wgrad.restype = _i
+lib.piso_conv2d_forward_ex.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]
+lib.piso_conv2d_forward_ex.restype = _i
+lib.piso_conv2d_wgrad_ex.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]
+lib.piso_conv2d_wgrad_ex.restype = _i
+lib.piso_conv_last_geometry.argtypes = [_ip, _i]
+lib.piso_conv_last_geometry.restype = _i
 lib.piso_leaky_relu_backward.argtypes = [_vp, _vp, _vp, _sz, _vp]
 lib.piso_leaky_relu_backward.restype = _i
 
@@ -325,6 +331,15 @@ def conv_last_dispatch():
     """Which kernel instance this thread's last piso_conv2d_forward / piso_conv2d_wgrad ran (include/piso_hip.h: piso_conv_last_dispatch),
     as a dict; {} if the thread has not run a convolution."""
     return _last_dispatch(lib.piso_conv_last_dispatch, "piso_conv_last_dispatch", CONV_DISPATCH_FIELDS)
+
+
+CONV_GEOMETRY_FIELDS = ("pad_y", "pad_x", "wrap_y", "wrap_x")
+
+
+def conv_last_geometry():
+    """The geometry of this thread's last convolution (include/piso_hip.h: piso_conv_last_geometry) as a dict; {} after piso_conv2d_forward /
+    piso_conv2d_wgrad (one pad, no wrap: the call's own argument) or before any convolution."""
+    return _last_dispatch(lib.piso_conv_last_geometry, "piso_conv_last_geometry", CONV_GEOMETRY_FIELDS)
 
 
 MG_DISPATCH_FIELDS = ("levels", "tail_first", "sweeps", "iterations", "cycles", "residual_recomputations", "cycle_elem", "vec_mask")

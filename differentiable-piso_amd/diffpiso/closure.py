@@ -47,25 +47,53 @@ def _cached_layouts(w_oihw):
     return hit[1], hit[2]
 
 
+def _pad2(pad):
+    """pad as (pad_y, pad_x): an int is the same padding on both axes."""
+    if isinstance(pad, (tuple, list)):
+        if len(pad) != 2:
+            raise ValueError("pad: an int or (pad_y, pad_x)")
+        return int(pad[0]), int(pad[1])
+    return int(pad), int(pad)
+
+
+def _wrap2(wrap):
+    """wrap as (wrap_y, wrap_x) of bools; None: no axis is periodic."""
+    if wrap is None:
+        return False, False
+    if isinstance(wrap, (bool, int, np.bool_)):
+        return bool(wrap), bool(wrap)
+    if len(wrap) != 2:
+        raise ValueError("wrap: (wrap_y, wrap_x)")
+    return bool(wrap[0]), bool(wrap[1])
+
+
 class _Conv2dLeaky(torch.autograd.Function):
     """One layer of the closure on the matrix cores: out = [leaky_relu_0.2](conv2d(x, w)), NHWC, batch 1, stride 1, no bias
     (tf.nn.conv2d + tf.nn.leaky_relu of networks.py:21-44).  Reverse mode: g' = g * leaky'(out) (leaky ReLU has a positive slope:
     the sign of the saved output is the sign of the pre-activation); input gradient = the same kernel with flipped, transposed
-    weights on g'; weight gradient = piso_conv2d_wgrad."""
+    weights on g'; weight gradient = piso_conv2d_wgrad.
+    geom None: one zero padding `pad` on every side - piso_conv2d_forward / piso_conv2d_wgrad.  geom (pad_y, pad_x, wrap_y, wrap_x):
+    the general geometry - piso_conv2d_forward_ex / piso_conv2d_wgrad_ex, the input gradient with pad' = k - 1 - pad per axis and the
+    same wrap (include/piso_hip.h)."""
 
     @staticmethod
-    def forward(ctx, x, w_oihw, pad, leaky):
+    def forward(ctx, x, w_oihw, pad, leaky, geom=None):
         from . import _native as N
         x = x.contiguous()
         cout, cin, k, _ = w_oihw.shape
         _, H, W, _ = x.shape
         wl, _ = _cached_layouts(w_oihw)
-        Ho, Wo = H + 2 * pad - k + 1, W + 2 * pad - k + 1
+        pad_y, pad_x = (pad, pad) if geom is None else geom[:2]
+        Ho, Wo = H + 2 * pad_y - k + 1, W + 2 * pad_x - k + 1
         out = torch.empty((1, Ho, Wo, cout), dtype=torch.float32, device=x.device)
-        N.check(N.lib.piso_conv2d_forward(N.ptr(x), N.ptr(wl), N.ptr(out), H, W, cin, cout, k, pad, int(leaky), N.stream_ptr()),
-                "piso_conv2d_forward")
+        if geom is None:
+            N.check(N.lib.piso_conv2d_forward(N.ptr(x), N.ptr(wl), N.ptr(out), H, W, cin, cout, k, pad, int(leaky), N.stream_ptr()),
+                    "piso_conv2d_forward")
+        else:
+            N.check(N.lib.piso_conv2d_forward_ex(N.ptr(x), N.ptr(wl), N.ptr(out), H, W, cin, cout, k, pad_y, pad_x, geom[2], geom[3], int(leaky),
+                                                 N.stream_ptr()), "piso_conv2d_forward_ex")
         ctx.save_for_backward(x, w_oihw, out if leaky else None)
-        ctx.meta = (pad, leaky, Ho, Wo)
+        ctx.meta = (pad, leaky, Ho, Wo, geom)
         return out
 
     @staticmethod
@@ -73,7 +101,7 @@ class _Conv2dLeaky(torch.autograd.Function):
         import ctypes as C
         from . import _native as N
         x, w_oihw, out = ctx.saved_tensors
-        pad, leaky, Ho, Wo = ctx.meta
+        pad, leaky, Ho, Wo, geom = ctx.meta
         cout, cin, k, _ = w_oihw.shape
         _, H, W, _ = x.shape
         g = g.contiguous()
@@ -90,27 +118,54 @@ class _Conv2dLeaky(torch.autograd.Function):
                 raise N.PisoNativeError("conv2d input gradient: output channels must be <= 4 or a multiple of 16")
             _, wd = _cached_layouts(w_oihw)
             dx = torch.empty_like(x)
-            N.check(N.lib.piso_conv2d_forward(N.ptr(gp), N.ptr(wd), N.ptr(dx), Ho, Wo, cop, cin, k, k - 1 - pad, 0, N.stream_ptr()),
-                    "piso_conv2d_forward (input gradient)")
+            if geom is None:
+                N.check(N.lib.piso_conv2d_forward(N.ptr(gp), N.ptr(wd), N.ptr(dx), Ho, Wo, cop, cin, k, k - 1 - pad, 0, N.stream_ptr()),
+                        "piso_conv2d_forward (input gradient)")
+            else:                                            # (a wrapped axis: pad = k // 2 = k - 1 - pad and Ho = H - the adjoint wraps the same way)
+                N.check(N.lib.piso_conv2d_forward_ex(N.ptr(gp), N.ptr(wd), N.ptr(dx), Ho, Wo, cop, cin, k, k - 1 - geom[0], k - 1 - geom[1], geom[2], geom[3], 0,
+                                                     N.stream_ptr()), "piso_conv2d_forward_ex (input gradient)")
         if ctx.needs_input_grad[1]:
             ws = N.workspace(N.lib.piso_conv2d_wgrad_workspace_bytes(k, cin, cout), x.device, "conv_wgrad")
             dw_hwio = torch.empty((k, k, cin, cout), dtype=torch.float32, device=x.device)
-            N.check(N.lib.piso_conv2d_wgrad(N.ptr(x), N.ptr(g), N.ptr(dw_hwio), H, W, cin, cout, k, pad, N.ptr(ws),
-                                            C.c_size_t(ws.numel()), N.stream_ptr()), "piso_conv2d_wgrad")
+            if geom is None:
+                N.check(N.lib.piso_conv2d_wgrad(N.ptr(x), N.ptr(g), N.ptr(dw_hwio), H, W, cin, cout, k, pad, N.ptr(ws),
+                                                C.c_size_t(ws.numel()), N.stream_ptr()), "piso_conv2d_wgrad")
+            else:
+                N.check(N.lib.piso_conv2d_wgrad_ex(N.ptr(x), N.ptr(g), N.ptr(dw_hwio), H, W, cin, cout, k, geom[0], geom[1], geom[2], geom[3], N.ptr(ws),
+                                                   C.c_size_t(ws.numel()), N.stream_ptr()), "piso_conv2d_wgrad_ex")
             dw = dw_hwio.permute(3, 2, 0, 1).contiguous()
-        return dx, dw, None, None
+        return dx, dw, None, None, None
 
 
-def conv2d_leaky(x_nhwc, w_oihw, pad, leaky):
+def conv2d_leaky(x_nhwc, w_oihw, pad, leaky, wrap=(False, False)):
     """NHWC convolution (+ leaky ReLU 0.2) of the closure.  Device tensors: the MFMA kernels (float32, batch 1 - what the
-    reference's training feeds, one simulation per step) or an error; host tensors: torch's CPU convolution (tests / fixtures)."""
+    reference's training feeds, one simulation per step) or an error; host tensors: torch's CPU convolution (tests / fixtures).
+    pad: an int or (pad_y, pad_x).  wrap = (wrap_y, wrap_x): a wrapped axis is periodic - a tap that leaves the image reads the other side
+    instead of zero padding; its pad must be k // 2 (it keeps its extent) and its extent at least that.  With no wrapped axis and an int pad the
+    call is piso_conv2d_forward / piso_conv2d_wgrad as ever; otherwise the *_ex entries (include/piso_hip.h).  Host tensors: a circular
+    F.pad on the wrapped axes, zero padding on the others, then torch's convolution."""
+    pad_y, pad_x = _pad2(pad)
+    wrap_y, wrap_x = _wrap2(wrap)
+    general = wrap_y or wrap_x or isinstance(pad, (tuple, list))
     if x_nhwc.is_cuda or w_oihw.is_cuda:
         if not (x_nhwc.is_cuda and w_oihw.is_cuda and x_nhwc.dtype == torch.float32 and w_oihw.dtype == torch.float32 and x_nhwc.shape[0] == 1):
             from ._native import PisoNativeError
             raise PisoNativeError("conv2d_leaky: the MFMA convolution kernels take float32 NHWC device tensors of batch 1 (got %s %s, weights %s on %s); "
                                   "there is no other convolution path on the GPU" % (tuple(x_nhwc.shape), x_nhwc.dtype, w_oihw.dtype, w_oihw.device))
-        return _Conv2dLeaky.apply(x_nhwc, w_oihw, int(pad), bool(leaky))
-    y = F.conv2d(x_nhwc.permute(0, 3, 1, 2), w_oihw, padding=int(pad))
+        if not general:
+            return _Conv2dLeaky.apply(x_nhwc, w_oihw, int(pad), bool(leaky))
+        return _Conv2dLeaky.apply(x_nhwc, w_oihw, pad_y, bool(leaky), (pad_y, pad_x, int(wrap_y), int(wrap_x)))
+    if not general:
+        y = F.conv2d(x_nhwc.permute(0, 3, 1, 2), w_oihw, padding=int(pad))
+    else:
+        k = w_oihw.shape[-1]
+        for name, wrapped, p, n in (("y", wrap_y, pad_y, x_nhwc.shape[1]), ("x", wrap_x, pad_x, x_nhwc.shape[2])):
+            if wrapped and (p != k // 2 or n < p):
+                raise ValueError("conv2d_leaky: the wrapped %s axis needs pad == k // 2 and an extent >= pad (pad %d, k %d, extent %d)" % (name, p, k, n))
+        xc = x_nhwc.permute(0, 3, 1, 2)
+        if wrap_y or wrap_x:
+            xc = F.pad(xc, (pad_x if wrap_x else 0, pad_x if wrap_x else 0, pad_y if wrap_y else 0, pad_y if wrap_y else 0), mode="circular")
+        y = F.conv2d(xc, w_oihw, padding=(0 if wrap_y else pad_y, 0 if wrap_x else pad_x))
     if leaky:
         y = F.leaky_relu(y, 0.2)
     return y.permute(0, 2, 3, 1)
@@ -121,10 +176,20 @@ _KERNELS = [(7, 4, 16), (5, 16, 16), (5, 16, 32), (3, 32, 64), (3, 64, 64), (1, 
 
 class FullyConvNetwork(torch.nn.Module):
     """7-layer fully convolutional network 4 -> 16 -> 16 -> 32 -> 64 -> 64 -> 64 -> 2, kernels 7,5,5,3,3,1,1, leaky ReLU (0.2)
-    after all but the last layer (networks.py:3-57).  Tensors are NHWC like the reference's."""
+    after all but the last layer (networks.py:3-57).  Tensors are NHWC like the reference's.
+    wrap = (wrap_y, wrap_x): the periodic axes of the domain.  A wrapped axis keeps its extent in every layer (pad k // 2, wrap-around),
+    whatever `padding` says: `padding="VALID"` shrinks - and `restore_shape` pads back - only the other axis.  A non-zero `buffer_width`
+    on a wrapped axis is refused: a cropped axis has no seam.  A periodic simulation wants the network and its coupling
+    (centered_to_staggered / make_forcing_fn) wrapped on the same axes."""
 
-    def __init__(self, buffer_width=None, padding="SAME", restore_shape=False, in_channels=4, seed=None, initialiser=None):
+    def __init__(self, buffer_width=None, padding="SAME", restore_shape=False, in_channels=4, seed=None, initialiser=None, wrap=(False, False)):
         super().__init__()
+        self.wrap = _wrap2(wrap)
+        if buffer_width is not None:
+            for axis, name in ((0, "y"), (1, "x")):
+                if self.wrap[axis] and any(int(b) != 0 for b in buffer_width[axis]):
+                    raise ValueError("FullyConvNetwork: buffer_width %s crops the wrapped %s axis: a cropped axis has no seam to wrap across"
+                                     % (list(buffer_width[axis]), name))
         gen = torch.Generator().manual_seed(seed) if seed is not None else None
         self.weights = torch.nn.ParameterList()
         for i, (k, cin, cout) in enumerate(_KERNELS):
@@ -157,20 +222,26 @@ class FullyConvNetwork(torch.nn.Module):
         target = fields.shape
         x = fields
         same = self.padding == "SAME"
+        wrap_y, wrap_x = self.wrap
         for i, w in enumerate(self.weights):
-            x = conv2d_leaky(x, w, w.shape[-1] // 2 if same else 0, leaky=i < len(self.weights) - 1)
+            k = w.shape[-1]
+            if not (wrap_y or wrap_x):
+                x = conv2d_leaky(x, w, k // 2 if same else 0, leaky=i < len(self.weights) - 1)
+            else:
+                x = conv2d_leaky(x, w, (k // 2 if same or wrap_y else 0, k // 2 if same or wrap_x else 0), leaky=i < len(self.weights) - 1, wrap=self.wrap)
         out = x
         if not same and bw is not None and self.restore_shape:
             pn = self.reduced_buffer_width
-            out = F.pad(out, (0, 0, pn, target[2] - out.shape[2] - pn, pn, target[1] - out.shape[1] - pn))
+            pn_y, pn_x = (0 if wrap_y else pn), (0 if wrap_x else pn)
+            out = F.pad(out, (0, 0, pn_x, target[2] - out.shape[2] - pn_x, pn_y, target[1] - out.shape[1] - pn_y))
         if bw is not None:
             out = F.pad(out, (0, 0, bw[1][0], bw[1][1], bw[0][0], bw[0][1]))
         return out
 
 
-def initialise_fullyconv_network(buffer_width, padding="SAME", restore_shape=False, initialiser=None, seed=None):
-    """networks.py:59-77 -> (callable, weights, reduced_buffer_width)."""
-    net = FullyConvNetwork(buffer_width, padding, restore_shape, seed=seed, initialiser=initialiser)
+def initialise_fullyconv_network(buffer_width, padding="SAME", restore_shape=False, initialiser=None, seed=None, wrap=(False, False)):
+    """networks.py:59-77 -> (callable, weights, reduced_buffer_width).  wrap: the periodic axes (FullyConvNetwork)."""
+    net = FullyConvNetwork(buffer_width, padding, restore_shape, seed=seed, initialiser=initialiser, wrap=wrap)
     rbw = net.reduced_buffer_width
     if buffer_width is not None:
         rbw = [[i + rbw for i in j] for j in buffer_width]
@@ -192,12 +263,15 @@ def centered_gradient(field):
     return torch.cat([dy, dx], dim=-1)
 
 
-def centered_to_staggered(nn_out):
+def centered_to_staggered(nn_out, wrap=(False, False)):
     """StaggeredGrid([CenteredGrid(c0).at(v faces), CenteredGrid(c1).at(u faces)]) with the default 'boundary' extrapolation
-    (combined_training_integrated.py:405-409): linear interpolation to the faces, edge values replicated."""
+    (combined_training_integrated.py:405-409): linear interpolation to the faces, edge values replicated.
+    wrap = (wrap_y, wrap_x): on a wrapped (periodic) axis the faces average across the seam instead - face 0 and face n are both
+    (cell n - 1 + cell 0) / 2."""
+    wrap_y, wrap_x = _wrap2(wrap)
     c0, c1 = nn_out[..., 0:1], nn_out[..., 1:2]
-    p0 = pad_axis(c0, 1, 1, 1, "replicate")
-    p1 = pad_axis(c1, 2, 1, 1, "replicate")
+    p0 = pad_axis(c0, 1, 1, 1, "circular" if wrap_y else "replicate")
+    p1 = pad_axis(c1, 2, 1, 1, "circular" if wrap_x else "replicate")
     v = 0.5 * (p0[:, 1:] + p0[:, :-1])
     u = 0.5 * (p1[:, :, 1:] + p1[:, :, :-1])
     return stack_staggered_components([v, u])
@@ -211,10 +285,12 @@ def network_input(velocity, pressure, pressure_included=True):
     return nn_in
 
 
-def make_forcing_fn(network, pressure_included=True, wrapper=None):
-    """forcing_fn for run_piso_steps: the residual force of the closure at every unrolled step (:443-454)."""
+def make_forcing_fn(network, pressure_included=True, wrapper=None, wrap=None):
+    """forcing_fn for run_piso_steps: the residual force of the closure at every unrolled step (:443-454).
+    wrap = (wrap_y, wrap_x): the centre -> face resampling averages across the seam of a periodic axis (centered_to_staggered); None:
+    edge values replicated.  A periodic simulation wants the network (FullyConvNetwork(wrap=...)) and this coupling wrapped on the same axes."""
     def forcing(i, velocity, pressure):
         nn_in = network_input(velocity, pressure, pressure_included)
         nn_out = wrapper(network, nn_in) if wrapper is not None else network(nn_in)
-        return centered_to_staggered(nn_out)
+        return centered_to_staggered(nn_out, _wrap2(wrap))
     return forcing

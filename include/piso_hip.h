@@ -544,6 +544,30 @@ int piso_leaky_relu_backward(const float* grad_out, const float* out, float* gra
  *   14 Wo              output columns */
 int piso_conv_last_dispatch(int* out, int capacity);
 
+/* The same convolutions with a GENERAL GEOMETRY: padding per axis (pad_y, pad_x) and wrap-around per axis (wrap_y, wrap_x != 0: the axis is
+ * periodic) - the closure on a periodic domain sees cell n - 1 and cell 0 as the neighbours they are.  Definition:
+ *     out[y][x][co] = sum over (ky, kx, ci) of in[Y][X][ci] w[ky][kx][ci][co],   Y = y + ky - pad_y,  X = x + kx - pad_x
+ *   on an axis that is not wrapped a coordinate outside the image contributes nothing (zero padding, as above); on a wrapped axis it is taken
+ *   modulo the extent.  Output extents as above: Ho = H + 2 pad_y - ks + 1, Wo = W + 2 pad_x - ks + 1.
+ *   piso_conv2d_wgrad_ex: dw[ky][kx][ci][co] = sum over output pixels (y, x) of in[Y][X][ci] grad_out[y][x][co], Y and X as above.
+ * Two rules for a wrapped axis (checked, PISO_ERR_INVALID_ARG, the message states the rule):
+ *   - its pad is ks / 2: the axis keeps its extent, and the adjoint is again such a convolution - the input gradient is
+ *     piso_conv2d_forward_ex(grad of the pre-activation output, flipped + transposed weights, pad' = ks - 1 - pad per axis, the same wrap);
+ *   - its extent is at least its pad: an index wraps at most once (one conditional add or subtract in the kernels, no division).
+ * Weight layout, alignment rules, workspace size, the refusals and the treatment of non-finite values are those of the entries above; the kernel
+ * instance is chosen by the same rules (option conv_lds included) and piso_conv_last_dispatch reports it with the same 15 fields (entry 1 for
+ * piso_conv2d_forward_ex, 2 for piso_conv2d_wgrad_ex: the *_ex_kernel twin of the instance named there).  The order of the terms of every sum
+ * is the instance's: with wrap (0, 0) and pad_y == pad_x the results are those of the entries above bit for bit, and with both axes wrapped
+ * every output pixel adds the same sequence of terms (the result of a circularly shifted input is the shifted result, bit for bit). */
+int piso_conv2d_forward_ex(const float* in, const float* w_laid_out, float* out, int H, int W, int cin, int cout, int ks, int pad_y, int pad_x,
+                           int wrap_y, int wrap_x, int leaky_out, piso_stream_t stream);
+int piso_conv2d_wgrad_ex(const float* in, const float* grad_out, float* dw, int H, int W, int cin, int cout, int ks, int pad_y, int pad_x,
+                         int wrap_y, int wrap_x, void* workspace, size_t workspace_bytes, piso_stream_t stream);
+/* The geometry of the calling thread's last convolution, written with the dispatch record: out[0 .. min(return value, capacity)) = pad_y,
+ * pad_x, wrap_y (0 | 1), wrap_x (0 | 1); returns the number of fields: 4 after piso_conv2d_forward_ex / piso_conv2d_wgrad_ex, 0 after
+ * piso_conv2d_forward / piso_conv2d_wgrad (their one `pad` is an argument of the call) or before any convolution. */
+int piso_conv_last_geometry(int* out, int capacity);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Slab-decomposed pressure CG (no counterpart in the reference, which is single-GPU).
  * The grid is cut along y into `world` slabs of ny_local rows, one rank (process) per GPU.  Two transports:
