@@ -32,10 +32,12 @@
 // beta and the sums stay on the device; the host queues check_every iterations, then reads the state through a pinned word; kernels of
 // iterations queued after convergence see the device flag and return at once, so neither x nor the count depends on the cadence.
 //
+// Host: one driver over the type of the cycle's values (mg_grid.h: set-up, V-cycle, PCG iteration, single cycle, the ordinary entries).
 // Opt-in: the same iteration around a float32 cycle (mg_f32.h, piso_mg_*_c32_f64); this file's kernels are its fp64 outer iteration.
 // Opt-in: a start from a guess x0 instead of x = 0 where its residual is below the right-hand side (mg_guess.h, piso_mg_*_guess_*).
 #include <vector>
 
+#include "mg_prepared_carve.h"
 #include "mg_slab_carve.h"
 #include "mg_slab_plan.h"
 #include "options.h"
@@ -222,41 +224,23 @@ __global__ __launch_bounds__(kBlock) void mg_sum_x(Lv L, const double* __restric
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-struct MgPlan {
-  int nlev = 0, tail_first = -1;          // tail_first: first level of the one-workgroup tail (-1: none fits)
-  Lv lv[kMgMaxLevels];
-  double *r[kMgMaxLevels], *z[kMgMaxLevels], *t[kMgMaxLevels];
-  double *p[2], *q, *parts, *part_rz, *part_pq, *part_max, *scal;
-  MgState* st;
-};
 static int mg_grid(int n) { return grid_for(n, kBlock, kMgGrid); }
-
-// carves the workspace (the same walk sizes it: piso_mg_workspace_bytes)
-static bool mg_plan(int nx, int ny, int per_x, int per_y, Arena& ar, MgPlan& P) {
-  const MgDims d = mg_dims(nx, ny);                        // (mg_slab_plan.h: the one statement of the hierarchy's shape)
-  for (int l = 0; l < d.nlev; ++l) {
-    Lv& L = P.lv[l];
-    L.nx = d.nx[l]; L.ny = d.ny[l]; L.n = L.nx * L.ny; L.per_x = per_x; L.per_y = per_y;
-    for (int s = 0; s < 5; ++s) L.c[s] = ar.take<double>(L.n);
-    L.dinv = ar.take<double>(L.n);
-    P.r[l] = ar.take<double>(L.n); P.z[l] = ar.take<double>(L.n); P.t[l] = ar.take<double>(L.n);
-  }
-  P.nlev = d.nlev;
-  P.tail_first = d.tail_first;
-  const int n0 = P.lv[0].n;
-  P.p[0] = ar.take<double>(n0); P.p[1] = ar.take<double>(n0); P.q = ar.take<double>(n0);
-  P.parts = ar.take<double>(4 * kMgGrid);
-  P.part_rz = ar.take<double>(kMgGrid); P.part_pq = ar.take<double>(kMgGrid); P.part_max = ar.take<double>(kMgGrid);
-  P.scal = ar.take<double>(SC_COUNT_MG);
-  P.st = ar.take<MgState>(1);
-  return ar.ok();
-}
-static bool mg_dims_ok(int nx, int ny) { return nx >= kMinDim && ny >= kMinDim && (long long)nx * ny <= (1ll << 30); }
 
 // which shape the calling thread's last solve / cycle had (piso_mg_last_dispatch)
 enum { MD_LEVELS = 0, MD_TAIL_FIRST, MD_SWEEPS, MD_ITERATIONS, MD_CYCLES, MD_RESIDUAL_RECOMPUTATIONS, MD_CYCLE_ELEM, MD_VEC_MASK, MD_COUNT };
 static thread_local int tl_mg_dispatch[MD_COUNT];
 static thread_local int tl_mg_dispatch_n = 0;
+static void mg_record(int nlev, int tail_first, int sweeps, int iterations, int cycles, int recomputed, int elem, int vec_mask) {
+  int* d = tl_mg_dispatch;
+  d[MD_LEVELS] = nlev; d[MD_TAIL_FIRST] = tail_first; d[MD_SWEEPS] = sweeps; d[MD_ITERATIONS] = iterations;
+  d[MD_CYCLES] = cycles; d[MD_RESIDUAL_RECOMPUTATIONS] = recomputed; d[MD_CYCLE_ELEM] = elem; d[MD_VEC_MASK] = vec_mask;
+  tl_mg_dispatch_n = MD_COUNT;
+}
+static int mg_recomputations(int iterations, int residual_reset) {
+  int recomputed = 0;
+  for (int k = 1; k < iterations; ++k) recomputed += (k + 1) % residual_reset == 0;
+  return recomputed;
+}
 
 struct MgPoll { MgState* pinned = nullptr; };
 constexpr int kMgPollDevices = 16;
@@ -271,7 +255,7 @@ static int mg_pinned(MgState** out) {
 }
 
 // builds every level from the caller's matrix and refuses what the solver does not solve (one host look, as the plain CG's set-up has):
-// level 0 and the sums (begin), the coarser levels (the caller's), the look (end)
+// level 0 and the sums (begin), the coarser levels (MgGridT::build of mg_grid.h, MgSlabT::build of mg_slab.h), the look (end)
 static int mg_build_begin(const Lv& L0, const double* laplace, const double* b, int rank_deficient, double* parts, double* scal, MgState* st, hipStream_t stream) {
   PISO_HIP_CHECK(hipMemsetAsync(st, 0, sizeof(MgState), stream));
   const int g0 = mg_grid(L0.n);
@@ -279,103 +263,45 @@ static int mg_build_begin(const Lv& L0, const double* laplace, const double* b, 
   mg_setup_fin<<<1, kBlock, 0, stream>>>(parts, g0, scal, rank_deficient, L0.n, st);
   return PISO_OK;
 }
+// what the set-up's flags refuse (the slab set-up decides on all-reduced flags: mg_slab.h)
+static int mg_refusal(int flags) {
+  const char* why = nullptr;
+  if (flags & MG_FLAG_BORDER) why = "piso_mg: non-zero border entry in a non-periodic direction (the reference stencil reads the neighbouring row there); use the plain CG";
+  else if (flags & MG_FLAG_ZERO_DIAG_ROW) why = "piso_mg: a row with a zero diagonal has non-zero entries; use the plain CG";
+  else if (flags & MG_FLAG_NOT_SINGULAR) why = "piso_mg: rank_deficient = 1 but the rows of the matrix do not sum to zero; use the plain CG";
+  if (!why) return PISO_OK;
+  set_error_msg(why);
+  return PISO_ERR_UNSUPPORTED_PATTERN;
+}
 static int mg_build_end(const MgState* st, hipStream_t stream) {
   MgState* pinned = nullptr;
   if (int rc = mg_pinned(&pinned)) return rc;
   PISO_HIP_CHECK(hipMemcpyAsync(pinned, st, sizeof(MgState), hipMemcpyDeviceToHost, stream));
   PISO_HIP_CHECK(hipStreamSynchronize(stream));
-  if (pinned->flags & MG_FLAG_BORDER) {
-    set_error_msg("piso_mg: non-zero border entry in a non-periodic direction (the reference stencil reads the neighbouring row there); use the plain CG");
-    return PISO_ERR_UNSUPPORTED_PATTERN;
-  }
-  if (pinned->flags & MG_FLAG_ZERO_DIAG_ROW) {
-    set_error_msg("piso_mg: a row with a zero diagonal has non-zero entries; use the plain CG");
-    return PISO_ERR_UNSUPPORTED_PATTERN;
-  }
-  if (pinned->flags & MG_FLAG_NOT_SINGULAR) {
-    set_error_msg("piso_mg: rank_deficient = 1 but the rows of the matrix do not sum to zero; use the plain CG");
-    return PISO_ERR_UNSUPPORTED_PATTERN;
-  }
-  return PISO_OK;
+  return mg_refusal(pinned->flags);
 }
-static int mg_build(const MgPlan& P, const double* laplace, const double* b, int rank_deficient, hipStream_t stream) {
-  PISO_TRY(mg_build_begin(P.lv[0], laplace, b, rank_deficient, P.parts, P.scal, P.st, stream));
-  for (int l = 0; l + 1 < P.nlev; ++l) mg_coarsen<<<mg_grid(P.lv[l + 1].n), kBlock, 0, stream>>>(P.lv[l], P.lv[l + 1]);
-  PISO_LAUNCH_CHECK();
-  return mg_build_end(P.st, stream);
-}
-
-// nu sweeps from a zero guess on level l; returns where the result is
-static double* mg_first_sweeps(const MgPlan& P, int l, const double* r, int nu, hipStream_t stream) {
-  const Lv& L = P.lv[l];
-  const int g = mg_grid(L.n);
-  double* cur = P.z[l];
-  if (nu >= 2) mg_pre2<<<g, kBlock, 0, stream>>>(L, r, cur, P.st); else mg_pre1<<<g, kBlock, 0, stream>>>(L, r, cur, P.st);
-  for (int s = 2; s < nu; ++s) {
-    double* nxt = cur == P.z[l] ? P.t[l] : P.z[l];
-    mg_jacobi<<<g, kBlock, 0, stream>>>(L, r, cur, nxt, nullptr, 0, nullptr, P.st);
-    cur = nxt;
-  }
-  return cur;
-}
-// z = M^-1 r0: returns where z of level 0 is; the last kernel leaves the partials of (r0, z) in P.part_rz (*n_rz of them)
-// (l0: the level r0 lives on - 0, or the first replicated level of a slab solve, which runs levels l0 .. coarsest exactly like this)
-static double* mg_cycle(const MgPlan& P, const double* r0, int nu, bool use_tail, int* n_rz, hipStream_t stream, int l0 = 0) {
-  const int end = use_tail ? P.tail_first : P.nlev - 1;      // levels [l0, end) have a coarser level and run as kernels of their own
-  double* zc[kMgMaxLevels];
-  for (int l = l0; l < end; ++l) {
-    const double* r = l == l0 ? r0 : P.r[l];
-    zc[l] = mg_first_sweeps(P, l, r, nu, stream);
-    mg_restrict<<<mg_grid(P.lv[l + 1].n), kBlock, 0, stream>>>(P.lv[l], r, zc[l], P.r[l + 1], P.lv[l + 1].nx, P.lv[l + 1].ny, P.st);
-  }
-  const double* rend = end == l0 ? r0 : P.r[end];
-  if (use_tail) {
-    MgTail T;
-    T.nlev = P.nlev - end;
-    int off = 0;
-    for (int k = 0; k < T.nlev; ++k) { T.lv[k] = P.lv[end + k]; T.off[k] = off; off += T.lv[k].n; }
-    mg_tail<<<1, kTailThreads, 0, stream>>>(T, rend, P.z[end], end == l0 ? P.part_rz : nullptr, nu, P.st);
-    zc[end] = P.z[end];
-    *n_rz = 1;
-  } else {
-    double* cur = mg_first_sweeps(P, end, rend, kCoarsestSweeps - 1, stream);
-    double* nxt = cur == P.z[end] ? P.t[end] : P.z[end];
-    const int g = mg_grid(P.lv[end].n);
-    mg_jacobi<<<g, kBlock, 0, stream>>>(P.lv[end], rend, cur, nxt, nullptr, 0, end == l0 ? P.part_rz : nullptr, P.st);
-    zc[end] = nxt;
-    *n_rz = g;
-  }
-  for (int l = end - 1; l >= l0; --l) {
-    const Lv& L = P.lv[l];
-    const double* r = l == l0 ? r0 : P.r[l];
-    const int g = mg_grid(L.n);
-    double* cur = zc[l];
-    for (int s = 0; s < nu; ++s) {
-      double* nxt = cur == P.z[l] ? P.t[l] : P.z[l];
-      mg_jacobi<<<g, kBlock, 0, stream>>>(L, r, cur, nxt, s == 0 ? zc[l + 1] : nullptr, P.lv[l + 1].nx, (l == l0 && s == nu - 1) ? P.part_rz : nullptr, P.st);
-      cur = nxt;
-    }
-    zc[l] = cur;
-    if (l == l0) *n_rz = g;
-  }
-  return zc[l0];
-}
-static bool mg_use_tail(const MgPlan& P) { return P.tail_first >= 0 && opt(OPT_MG_TAIL) != 0; }
-
 static int mg_common_args(const char* who, int nx, int ny, const void* a, const void* b, const void* c, const void* ws, int sweeps) {
   char msg[160];
-  if (!mg_dims_ok(nx, ny)) { snprintf(msg, sizeof(msg), "%s: needs at least %d cells in each dimension", who, kMinDim); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
+  if (!mg_prepared_dims_ok(nx, ny)) { snprintf(msg, sizeof(msg), "%s: needs at least %d cells in each dimension", who, kMinDim); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
   if (!a || !b || !c || !ws) { snprintf(msg, sizeof(msg), "%s: NULL pointer", who); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
   if (sweeps < 1 || sweeps > 8) { snprintf(msg, sizeof(msg), "%s: sweeps must be 1 .. 8", who); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
   return PISO_OK;
 }
+static int mg_iteration_args(const char* who, int max_iterations, int residual_reset) {
+  if (max_iterations >= 1 && residual_reset >= 1) return PISO_OK;
+  char msg[128];
+  snprintf(msg, sizeof(msg), "%s: max_iterations and residual_reset must be positive", who);
+  set_error_msg(msg);
+  return PISO_ERR_INVALID_ARG;
+}
 
 }  // namespace piso
 
-#include "mg_slab.h"
 #include "mg_f32.h"
-#include "mg_slab_f32.h"
 #include "mg_guess.h"
+#include "mg_grid.h"
+#include "mg_slab.h"
+#include "mg_slab_f32.h"
 #include "mg_prepared.h"
 
 namespace piso {
@@ -417,8 +343,7 @@ static int mg_slab_solve_comm(const char* who, void* comm, int nx, int ny_local,
                               int* iterations_out, void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
   const OptScope knobs;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  char msg[128];
-  if (max_iterations < 1 || residual_reset < 1) { snprintf(msg, sizeof(msg), "%s: max_iterations and residual_reset must be positive", who); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
+  PISO_TRY(mg_iteration_args(who, max_iterations, residual_reset));
   tl_mg_last_guess = 0;                                       // (a slab solve takes no guess)
   MgSlabT<C> M;
   PISO_TRY(mg_slab_comm_begin(M, who, comm, nx, ny_local, periodic_x, periodic_y, laplace_local, divergence_local, x_out_local, workspace, workspace_bytes, sweeps, stream));
@@ -434,8 +359,7 @@ static int mg_slab_solve_emulated(const char* who, int slabs, int nx, int ny, in
                                   void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
   const OptScope knobs;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  char msg[128];
-  if (max_iterations < 1 || residual_reset < 1) { snprintf(msg, sizeof(msg), "%s: max_iterations and residual_reset must be positive", who); set_error_msg(msg); return PISO_ERR_INVALID_ARG; }
+  PISO_TRY(mg_iteration_args(who, max_iterations, residual_reset));
   tl_mg_last_guess = 0;
   MgSlabT<C> M;
   PISO_TRY(mg_slab_emulated_begin(M, who, slabs, nx, ny, periodic_x, periodic_y, laplace, divergence, x_out, workspace, workspace_bytes, sweeps, stream));
@@ -512,141 +436,36 @@ static int mg_slab_level_emulated(const char* who, int slabs, int rank, int nx, 
 
 using namespace piso;
 
-// the ordinary solve entries, with and without a guess (x0 NULL: none)
-static int mg_solve_entry_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence, double* x_out,
-                              float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps, int* iterations_out,
-                              void* workspace, size_t workspace_bytes, piso_stream_t stream_, const double* x0) {
-  const OptScope knobs;
-  tl_mg_last_guess = 0;                                       // (until the solve returns: a refused call reports no guess)
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (int rc = mg_common_args("piso_mg_pcg_solve", nx, ny, laplace, divergence, x_out, workspace, sweeps)) return rc;
-  if (max_iterations < 1 || residual_reset < 1) { set_error_msg("piso_mg_pcg_solve: max_iterations and residual_reset must be positive"); return PISO_ERR_INVALID_ARG; }
-  Arena ar(workspace, workspace_bytes);
-  MgPlan P;
-  if (!mg_plan(nx, ny, periodic_x ? 1 : 0, periodic_y ? 1 : 0, ar, P)) { set_error_msg("piso_mg_pcg_solve: workspace too small"); return PISO_ERR_INVALID_ARG; }
-  if (int rc = mg_build(P, laplace, divergence, rank_deficient ? 1 : 0, stream)) return rc;
-  return mg_pcg_run(P, divergence, x_out, accuracy, max_iterations, rank_deficient ? 1 : 0, residual_reset, sweeps, iterations_out, stream, x0);
-}
-static int mg_solve_entry_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence, double* x_out,
-                                  float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps, int* iterations_out,
-                                  void* workspace, size_t workspace_bytes, piso_stream_t stream_, const double* x0) {
-  const OptScope knobs;
-  tl_mg_last_guess = 0;                                       // (until the solve returns: a refused call reports no guess)
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (int rc = mg_common_args("piso_mg_pcg_solve", nx, ny, laplace, divergence, x_out, workspace, sweeps)) return rc;
-  if (max_iterations < 1 || residual_reset < 1) { set_error_msg("piso_mg_pcg_solve: max_iterations and residual_reset must be positive"); return PISO_ERR_INVALID_ARG; }
-  Arena ar(workspace, workspace_bytes);
-  MgPlanF P;
-  if (!mg_plan_f32(nx, ny, periodic_x ? 1 : 0, periodic_y ? 1 : 0, ar, P)) { set_error_msg("piso_mg_pcg_solve: workspace too small"); return PISO_ERR_INVALID_ARG; }
-  if (int rc = mg_build_f32(P, laplace, divergence, rank_deficient ? 1 : 0, stream)) return rc;
-  return mg_pcg_run(P, divergence, x_out, accuracy, max_iterations, rank_deficient ? 1 : 0, residual_reset, sweeps, iterations_out, stream, x0);
-}
-
 extern "C" {
 
-size_t piso_mg_workspace_bytes(int nx, int ny) {
-  if (!mg_dims_ok(nx, ny)) return 0;
-  Arena ar(reinterpret_cast<void*>(256), ~(size_t)0);
-  MgPlan P;
-  mg_plan(nx, ny, 0, 0, ar, P);
-  return ar.used;
-}
+size_t piso_mg_workspace_bytes(int nx, int ny) { return mg_plan_bytes(nx, ny, 8); }
+size_t piso_mg_workspace_bytes_cycle(int nx, int ny, int cycle_elem_size) { return mg_plan_bytes(nx, ny, cycle_elem_size); }
 
-int piso_mg_pcg_solve_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence, double* x_out,
-                          float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps, int* iterations_out,
-                          void* workspace, size_t workspace_bytes, piso_stream_t stream) {
-  return mg_solve_entry_f64(nx, ny, periodic_x, periodic_y, laplace, divergence, x_out, accuracy, max_iterations, rank_deficient, residual_reset, sweeps,
-                            iterations_out, workspace, workspace_bytes, stream, nullptr);
-}
-int piso_mg_pcg_solve_guess_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence, const double* x0,
-                                double* x_out, float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps,
-                                int* iterations_out, void* workspace, size_t workspace_bytes, piso_stream_t stream) {
-  return mg_solve_entry_f64(nx, ny, periodic_x, periodic_y, laplace, divergence, x_out, accuracy, max_iterations, rank_deficient, residual_reset, sweeps,
-                            iterations_out, workspace, workspace_bytes, stream, x0);
-}
-
-int piso_mg_vcycle_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* r_in, double* z_out, int sweeps,
-                       void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
-  const piso::OptScope knobs;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (int rc = mg_common_args("piso_mg_vcycle", nx, ny, laplace, r_in, z_out, workspace, sweeps)) return rc;
-  Arena ar(workspace, workspace_bytes);
-  MgPlan P;
-  if (!mg_plan(nx, ny, periodic_x ? 1 : 0, periodic_y ? 1 : 0, ar, P)) { set_error_msg("piso_mg_vcycle: workspace too small"); return PISO_ERR_INVALID_ARG; }
-  if (int rc = mg_build(P, laplace, nullptr, 0, stream)) return rc;
-  return mg_vcycle_run(P, r_in, z_out, sweeps, false, stream);
-}
-
-int piso_mg_level_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, int level, int* nx_out, int* ny_out,
-                      double* laplace_level_out, void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
-  const piso::OptScope knobs;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (int rc = mg_common_args("piso_mg_level", nx, ny, laplace, nx_out, ny_out, workspace, 1)) return rc;
-  Arena ar(workspace, workspace_bytes);
-  MgPlan P;
-  if (!mg_plan(nx, ny, periodic_x ? 1 : 0, periodic_y ? 1 : 0, ar, P)) { set_error_msg("piso_mg_level: workspace too small"); return PISO_ERR_INVALID_ARG; }
-  if (level < 0 || level >= P.nlev) { *nx_out = 0; *ny_out = 0; set_error_msg("piso_mg_level: no such level"); return PISO_ERR_INVALID_ARG; }
-  *nx_out = P.lv[level].nx; *ny_out = P.lv[level].ny;
-  if (!laplace_level_out) return PISO_OK;                     // (sizes only)
-  if (int rc = mg_build(P, laplace, nullptr, 0, stream)) return rc;
-  mg_export<<<mg_grid(P.lv[level].n), kBlock, 0, stream>>>(P.lv[level], laplace_level_out);
-  PISO_LAUNCH_CHECK();
-  PISO_HIP_CHECK(hipStreamSynchronize(stream));
-  return PISO_OK;
-}
-
-// ---- the float32 cycle under the same fp64 PCG (mg_f32.h) ----------------------------------------------------------------------------------
-size_t piso_mg_workspace_bytes_cycle(int nx, int ny, int cycle_elem_size) {
-  if (cycle_elem_size == 8) return piso_mg_workspace_bytes(nx, ny);
-  if (cycle_elem_size != 4 || !mg_dims_ok(nx, ny)) return 0;
-  Arena ar(reinterpret_cast<void*>(256), ~(size_t)0);
-  MgPlanF P;
-  mg_plan_f32(nx, ny, 0, 0, ar, P);
-  return ar.used;
-}
-
-int piso_mg_pcg_solve_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence, double* x_out,
-                              float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps, int* iterations_out,
-                              void* workspace, size_t workspace_bytes, piso_stream_t stream) {
-  return mg_solve_entry_c32_f64(nx, ny, periodic_x, periodic_y, laplace, divergence, x_out, accuracy, max_iterations, rank_deficient, residual_reset, sweeps,
-                                iterations_out, workspace, workspace_bytes, stream, nullptr);
-}
-int piso_mg_pcg_solve_guess_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence, const double* x0,
-                                    double* x_out, float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps,
-                                    int* iterations_out, void* workspace, size_t workspace_bytes, piso_stream_t stream) {
-  return mg_solve_entry_c32_f64(nx, ny, periodic_x, periodic_y, laplace, divergence, x_out, accuracy, max_iterations, rank_deficient, residual_reset, sweeps,
-                                iterations_out, workspace, workspace_bytes, stream, x0);
-}
-
-int piso_mg_vcycle_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* r_in, double* z_out, int sweeps,
-                           void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
-  const piso::OptScope knobs;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (int rc = mg_common_args("piso_mg_vcycle", nx, ny, laplace, r_in, z_out, workspace, sweeps)) return rc;
-  Arena ar(workspace, workspace_bytes);
-  MgPlanF P;
-  if (!mg_plan_f32(nx, ny, periodic_x ? 1 : 0, periodic_y ? 1 : 0, ar, P)) { set_error_msg("piso_mg_vcycle: workspace too small"); return PISO_ERR_INVALID_ARG; }
-  if (int rc = mg_build_f32(P, laplace, nullptr, 0, stream)) return rc;
-  return mg_vcycle_run(P, r_in, z_out, sweeps, false, stream);
-}
-
-int piso_mg_level_c32_f64(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, int level, int* nx_out, int* ny_out,
-                          double* laplace_level_out, void* workspace, size_t workspace_bytes, piso_stream_t stream_) {
-  const piso::OptScope knobs;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (int rc = mg_common_args("piso_mg_level", nx, ny, laplace, nx_out, ny_out, workspace, 1)) return rc;
-  Arena ar(workspace, workspace_bytes);
-  MgPlanF P;
-  if (!mg_plan_f32(nx, ny, periodic_x ? 1 : 0, periodic_y ? 1 : 0, ar, P)) { set_error_msg("piso_mg_level: workspace too small"); return PISO_ERR_INVALID_ARG; }
-  if (level < 0 || level >= P.nlev) { *nx_out = 0; *ny_out = 0; set_error_msg("piso_mg_level: no such level"); return PISO_ERR_INVALID_ARG; }
-  *nx_out = P.lv[level].nx; *ny_out = P.lv[level].ny;
-  if (!laplace_level_out) return PISO_OK;                     // (sizes only)
-  if (int rc = mg_build_f32(P, laplace, nullptr, 0, stream)) return rc;
-  mg_export_f32<<<mg_grid(P.lv[level].n), kBlock, 0, stream>>>(P.lv[level], laplace_level_out);
-  PISO_LAUNCH_CHECK();
-  PISO_HIP_CHECK(hipStreamSynchronize(stream));
-  return PISO_OK;
-}
+// the ordinary entries (mg_grid.h), once per type of the cycle's values
+#define PISO_MG_ENTRIES(SUFFIX, C)                                                                                                                               \
+  int piso_mg_pcg_solve##SUFFIX(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence, double* x_out, float accuracy,  \
+                                int max_iterations, int rank_deficient, int residual_reset, int sweeps, int* iterations_out, void* workspace,                    \
+                                size_t workspace_bytes, piso_stream_t stream) {                                                                                  \
+    return mg_solve_entry<C>(nx, ny, periodic_x, periodic_y, laplace, divergence, x_out, accuracy, max_iterations, rank_deficient, residual_reset, sweeps,       \
+                             iterations_out, workspace, workspace_bytes, stream, nullptr);                                                                       \
+  }                                                                                                                                                              \
+  int piso_mg_pcg_solve_guess##SUFFIX(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* divergence, const double* x0,         \
+                                      double* x_out, float accuracy, int max_iterations, int rank_deficient, int residual_reset, int sweeps,                     \
+                                      int* iterations_out, void* workspace, size_t workspace_bytes, piso_stream_t stream) {                                      \
+    return mg_solve_entry<C>(nx, ny, periodic_x, periodic_y, laplace, divergence, x_out, accuracy, max_iterations, rank_deficient, residual_reset, sweeps,       \
+                             iterations_out, workspace, workspace_bytes, stream, x0);                                                                            \
+  }                                                                                                                                                              \
+  int piso_mg_vcycle##SUFFIX(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, const double* r_in, double* z_out, int sweeps,               \
+                             void* workspace, size_t workspace_bytes, piso_stream_t stream) {                                                                    \
+    return mg_vcycle_entry<C>(nx, ny, periodic_x, periodic_y, laplace, r_in, z_out, sweeps, workspace, workspace_bytes, stream);                                 \
+  }                                                                                                                                                              \
+  int piso_mg_level##SUFFIX(int nx, int ny, int periodic_x, int periodic_y, const double* laplace, int level, int* nx_out, int* ny_out,                          \
+                            double* laplace_level_out, void* workspace, size_t workspace_bytes, piso_stream_t stream) {                                          \
+    return mg_level_entry<C>(nx, ny, periodic_x, periodic_y, laplace, level, nx_out, ny_out, laplace_level_out, workspace, workspace_bytes, stream);             \
+  }
+PISO_MG_ENTRIES(_f64, double)
+PISO_MG_ENTRIES(_c32_f64, float)
+#undef PISO_MG_ENTRIES
 
 // ---- the same solver on y-slabs (mg_slab.h; the float32 cycle on them: mg_slab_f32.h) ---------------------------------------------------------
 size_t piso_mg_slab_workspace_bytes_cycle(int nx, int ny_local, int world, int local_ranks, int cycle_elem_size) {

@@ -130,127 +130,6 @@ __device__ __forceinline__ Quad quad_at(int row, int iq, int nx, int ny) {
 #include "mg_quads.inc"
 #include "mg_cells_undef.inc"
 
-// ---- host -----------------------------------------------------------------------------------------------------------------------------------
-struct MgPlanF {
-  int nlev = 0, tail_first = -1;
-  Lv L0;                                   // the fp64 level 0 of the outer iteration
-  LvF lv[kMgMaxLevels];
-  float *r[kMgMaxLevels], *z[kMgMaxLevels], *t[kMgMaxLevels];
-  double *r64, *p[2], *q, *parts, *part_rz, *part_pq, *part_max, *scal;
-  MgState* st;
-};
-static bool mg_plan_f32(int nx, int ny, int per_x, int per_y, Arena& ar, MgPlanF& P) {
-  const MgDims d = mg_dims(nx, ny);
-  const int n0 = d.nx[0] * d.ny[0];
-  Lv& D = P.L0;
-  D.nx = d.nx[0]; D.ny = d.ny[0]; D.n = n0; D.per_x = per_x; D.per_y = per_y;
-  for (int s = 0; s < 5; ++s) D.c[s] = ar.take<double>(n0);
-  D.dinv = ar.take<double>(n0);
-  for (int l = 0; l < d.nlev; ++l) {
-    LvF& L = P.lv[l];
-    L.nx = d.nx[l]; L.ny = d.ny[l]; L.n = L.nx * L.ny; L.per_x = per_x; L.per_y = per_y;
-    for (int s = 0; s < 5; ++s) L.c[s] = ar.take<float>(L.n);
-    L.dinv = ar.take<float>(L.n);
-    P.r[l] = ar.take<float>(L.n); P.z[l] = ar.take<float>(L.n); P.t[l] = ar.take<float>(L.n);
-  }
-  P.nlev = d.nlev;
-  P.tail_first = d.tail_first;
-  P.r64 = ar.take<double>(n0);
-  P.p[0] = ar.take<double>(n0); P.p[1] = ar.take<double>(n0); P.q = ar.take<double>(n0);
-  P.parts = ar.take<double>(4 * kMgGrid);
-  P.part_rz = ar.take<double>(kMgGrid); P.part_pq = ar.take<double>(kMgGrid); P.part_max = ar.take<double>(kMgGrid);
-  P.scal = ar.take<double>(SC_COUNT_MG);
-  P.st = ar.take<MgState>(1);
-  return ar.ok();
-}
-
-// the fp64 set-up and its refusals (mg_build_begin / mg_build_end of mg.hip), then the float32 levels
-static int mg_build_f32(const MgPlanF& P, const double* laplace, const double* b, int rank_deficient, hipStream_t stream) {
-  PISO_TRY(mg_build_begin(P.L0, laplace, b, rank_deficient, P.parts, P.scal, P.st, stream));
-  mg_level0_f32<<<mg_grid(P.L0.n), kBlock, 0, stream>>>(P.L0, P.lv[0]);
-  for (int l = 0; l + 1 < P.nlev; ++l) mg_coarsen_f32<<<mg_grid(P.lv[l + 1].n), kBlock, 0, stream>>>(P.lv[l], P.lv[l + 1]);
-  PISO_LAUNCH_CHECK();
-  return mg_build_end(P.st, stream);
-}
-
-struct MgRunF {
-  const MgPlanF& P;
-  int nu;
-  bool use_tail, vec;
-  hipStream_t stream;
-  int vec_mask = 0;
-  bool quads(int l) const { return vec && (P.lv[l].nx & 3) == 0; }
-  int grid(int l, bool x4) const { return x4 ? mg_grid((P.lv[l].nx >> 2) * P.lv[l].ny) : mg_grid(P.lv[l].n); }
-  // one sweep on level l; returns the number of (r, z) partials it left (rd given)
-  int jacobi(int l, bool x4, const float* r, const float* zin, float* zout, const float* e, const double* rd) const {
-    const LvF& L = P.lv[l];
-    const int g = grid(l, x4), nxc = e ? P.lv[l + 1].nx : 0;
-    double* part = rd ? P.part_rz : nullptr;
-    if (!x4) mg_jacobi_f32<<<g, kBlock, 0, stream>>>(L, r, zin, zout, e, nxc, part, P.st, rd);
-    else if (e && rd) mg_jacobi_f32x4<true, true><<<g, kBlock, 0, stream>>>(L, r, zin, zout, e, nxc, part, P.st, rd);
-    else if (e) mg_jacobi_f32x4<true, false><<<g, kBlock, 0, stream>>>(L, r, zin, zout, e, nxc, part, P.st, rd);
-    else if (rd) mg_jacobi_f32x4<false, true><<<g, kBlock, 0, stream>>>(L, r, zin, zout, e, nxc, part, P.st, rd);
-    else mg_jacobi_f32x4<false, false><<<g, kBlock, 0, stream>>>(L, r, zin, zout, e, nxc, part, P.st, rd);
-    return g;
-  }
-  float* first_sweeps(int l, bool x4, const float* r, int sweeps) const {
-    const LvF& L = P.lv[l];
-    float* cur = P.z[l];
-    if (sweeps >= 2 && x4) mg_pre2_f32x4<<<grid(l, true), kBlock, 0, stream>>>(L, r, cur, P.st);
-    else if (sweeps >= 2) mg_pre2_f32<<<grid(l, false), kBlock, 0, stream>>>(L, r, cur, P.st);
-    else mg_pre1_f32<<<grid(l, false), kBlock, 0, stream>>>(L, r, cur, P.st);
-    for (int s = 2; s < sweeps; ++s) {
-      float* nxt = cur == P.z[l] ? P.t[l] : P.z[l];
-      jacobi(l, x4, r, cur, nxt, nullptr, nullptr);
-      cur = nxt;
-    }
-    return cur;
-  }
-  // z = M^-1 r0 (mg_cycle of mg.hip in float32); rd: the outer residual in double - the partials of (rd, z) are left in P.part_rz
-  // (l0: the level r0 lives on - 0, or the first replicated level of a slab solve, as mg_cycle has it)
-  float* cycle(const float* r0, const double* rd, int* n_rz, int l0 = 0) {
-    const int end = use_tail ? P.tail_first : P.nlev - 1;
-    float* zc[kMgMaxLevels];
-    vec_mask = 0;
-    for (int l = l0; l < end; ++l) {
-      const float* r = l == l0 ? r0 : P.r[l];
-      const bool x4 = quads(l);
-      if (x4) vec_mask |= 1 << l;
-      zc[l] = first_sweeps(l, x4, r, nu);
-      const LvF& C = P.lv[l + 1];
-      if (x4) mg_restrict_f32x4<<<mg_grid((P.lv[l].nx >> 2) * C.ny), kBlock, 0, stream>>>(P.lv[l], r, zc[l], P.r[l + 1], C.nx, C.ny, P.st);
-      else mg_restrict_f32<<<mg_grid(C.n), kBlock, 0, stream>>>(P.lv[l], r, zc[l], P.r[l + 1], C.nx, C.ny, P.st);
-    }
-    const float* rend = end == l0 ? r0 : P.r[end];
-    const double* rd_end = end == l0 ? rd : nullptr;
-    if (use_tail) {
-      MgTail_f32 T;
-      T.nlev = P.nlev - end;
-      int off = 0;
-      for (int k = 0; k < T.nlev; ++k) { T.lv[k] = P.lv[end + k]; T.off[k] = off; off += T.lv[k].n; }
-      mg_tail_f32<<<1, kTailThreads, 0, stream>>>(T, rend, P.z[end], rd_end ? P.part_rz : nullptr, nu, P.st, rd_end);
-      zc[end] = P.z[end];
-      *n_rz = 1;
-    } else {
-      float* cur = first_sweeps(end, false, rend, kCoarsestSweeps - 1);
-      float* nxt = cur == P.z[end] ? P.t[end] : P.z[end];
-      *n_rz = jacobi(end, false, rend, cur, nxt, nullptr, rd_end);
-      zc[end] = nxt;
-    }
-    for (int l = end - 1; l >= l0; --l) {
-      const float* r = l == l0 ? r0 : P.r[l];
-      const bool x4 = quads(l);
-      float* cur = zc[l];
-      for (int s = 0; s < nu; ++s) {
-        float* nxt = cur == P.z[l] ? P.t[l] : P.z[l];
-        const int g = jacobi(l, x4, r, cur, nxt, s == 0 ? zc[l + 1] : nullptr, (l == l0 && s == nu - 1) ? rd : nullptr);
-        if (l == l0) *n_rz = g;
-        cur = nxt;
-      }
-      zc[l] = cur;
-    }
-    return zc[l0];
-  }
-};
+// (what the host launches of these, MgGridOps<float>, and the driver over them: mg_grid.h)
 
 }  // namespace piso

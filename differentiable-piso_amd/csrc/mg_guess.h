@@ -89,21 +89,18 @@ __global__ __launch_bounds__(kBlock) void mg_guess_apply_f32(Lv L, const double*
 // what the calling thread's last multigrid solve did with its guess (piso_mg_last_guess): 0 none given, 1 accepted, 2 rejected
 static thread_local int tl_mg_last_guess = 0;
 
-// the start of a solve: mg_init's launch without a guess, the three launches above with one (r32: the float32 cycle's fl32(r), or NULL)
+// the start of a solve: mg_init's launch without a guess, the three launches above with one (Ops: MgGridOps<C> of mg_grid.h, which picks the
+// kernel that also writes rc = fl32(r) under the float32 cycle)
 // (the partial maxima use slots no kernel has pending then: part_max, which iteration 1 overwrites, and the fourth quarter of `parts`)
-static void mg_start(const Lv& L0, const double* divergence, const double* x0, double* x, double* r, float* r32, const double* scal, double* parts,
+template <typename Ops, typename C>
+static void mg_start(const Lv& L0, const double* divergence, const double* x0, double* x, double* r, C* rc, const double* scal, double* parts,
                      double* part_max, float accuracy, MgState* st, hipStream_t stream) {
   const int g0 = grid_for(L0.n, kBlock, kMgGrid);
-  if (!x0) {
-    if (r32) mg_init_f32<<<g0, kBlock, 0, stream>>>(L0, divergence, x, r, scal, r32);
-    else mg_init<<<g0, kBlock, 0, stream>>>(L0, divergence, x, r, scal);
-    return;
-  }
+  if (!x0) { Ops::init(L0, divergence, x, r, scal, rc, g0, stream); return; }
   double* part_b = parts + 3 * kMgGrid;
   mg_guess_residual<<<g0, kBlock, 0, stream>>>(L0, divergence, x0, r, scal, part_max, part_b, st);
   mg_guess_pick<<<1, kBlock, 0, stream>>>(part_max, part_b, g0, accuracy, st);
-  if (r32) mg_guess_apply_f32<<<g0, kBlock, 0, stream>>>(L0, divergence, x0, x, r, scal, st, r32);
-  else mg_guess_apply<<<g0, kBlock, 0, stream>>>(L0, divergence, x0, x, r, scal, st);
+  Ops::guess_apply(L0, divergence, x0, x, r, scal, st, rc, g0, stream);
 }
 // ... and what the host's last look says the device did with the guess
 static void mg_guess_record(const double* x0, const MgState* pinned) {

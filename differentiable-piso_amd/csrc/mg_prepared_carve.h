@@ -1,8 +1,10 @@
-// The two buffers of a PREPARED multigrid solve (mg_prepared.h) and how they are carved - pure host code, no HIP calls, like mg_slab_carve.h:
-// a host compiler builds a driver over it (tests/mg_prepared_carve_driver.cpp) that walks both carves against arenas without memory.
-//   hierarchy  everything that depends on the matrix only, owned by the caller and kept between solves: a header, SC_SUM_DIAG / SC_NPRESENT,
-//              the five coefficient arrays and dinv of every level (float32 cycle: the fp64 level 0 of the outer iteration AND the float32 levels)
+// What a one-GPU multigrid solve works on, MgPlanT<C>, and how it is carved - pure host code, no HIP calls, like mg_slab_carve.h: a host
+// compiler builds a driver over it (tests/mg_prepared_carve_driver.cpp) that walks every carve against arenas without memory.
+//   hierarchy  everything that depends on the matrix only: a header, SC_SUM_DIAG / SC_NPRESENT, the five coefficient arrays and dinv of
+//              every level (float32 cycle: the fp64 level 0 of the outer iteration AND the float32 levels)
 //   scratch    what one solve writes: r, z, t of every level, p, q, the partials, `scal`, MgState (float32 cycle: the fp64 r beside fl32(r))
+// A PREPARED solve (mg_prepared.h) keeps the two in buffers of their own - the hierarchy is the caller's, kept between solves (mg_hier_carve,
+// mg_scratch_carve); the ordinary solve carves both out of its one workspace, without a header and with one `scal` (mg_plan_carve).
 // C is the type of the cycle's values, as in mg_slab_carve.h.
 #pragma once
 #include <stddef.h>
@@ -32,12 +34,39 @@ struct MgScratchT {
   MgState* st;
 };
 
+template <typename C>
+struct MgPlanT {
+  MgHierT<C> H;
+  MgScratchT<C> S;
+};
+
 inline bool mg_prepared_dims_ok(int nx, int ny) { return nx >= kPlanMinDim && ny >= kPlanMinDim && (long long)nx * ny <= (1ll << 30); }
 
 inline void mg_hier_level0(MgHierT<double>& H) { H.L0 = H.lv[0]; }
 inline void mg_hier_level0(MgHierT<float>&) {}
 inline void mg_scratch_outer_r(MgScratchT<double>& S) { S.r64 = S.r[0]; }
 inline void mg_scratch_outer_r(MgScratchT<float>&) {}
+
+// the pieces the carves share: a level's dimensions and its six arrays; the fp64 vectors, partials, sums and state behind the cycle's vectors
+template <typename LV>
+inline void mg_level_dims(const MgDims& d, int l, int per_x, int per_y, LV& L) {
+  L.nx = d.nx[l]; L.ny = d.ny[l]; L.n = L.nx * L.ny; L.per_x = per_x; L.per_y = per_y;
+}
+template <typename T, typename LV, typename AR>
+inline void mg_level_take(AR& ar, LV& L) {
+  for (int s = 0; s < 5; ++s) L.c[s] = ar.template take<T>(L.n);
+  L.dinv = ar.template take<T>(L.n);
+}
+template <typename C, typename AR>
+inline void mg_scratch_outer(size_t n0, AR& ar, MgScratchT<C>& S) {
+  if (sizeof(C) == 4) S.r64 = ar.template take<double>(n0);
+  mg_scratch_outer_r(S);
+  S.p[0] = ar.template take<double>(n0); S.p[1] = ar.template take<double>(n0); S.q = ar.template take<double>(n0);
+  S.parts = ar.template take<double>(4 * kMgGrid);
+  S.part_rz = ar.template take<double>(kMgGrid); S.part_pq = ar.template take<double>(kMgGrid); S.part_max = ar.template take<double>(kMgGrid);
+  S.scal = ar.template take<double>(SC_COUNT_MG);
+  S.st = ar.template take<MgState>(1);
+}
 
 // AR: Arena of piso_common.h, or the driver's.  Every array starts on the arena's 256-byte boundary, so a float row stays 16-byte aligned where
 // nx % 4 == 0 - the levels the four-cell kernels run on.
@@ -47,17 +76,11 @@ inline bool mg_hier_carve(int nx, int ny, int per_x, int per_y, AR& ar, MgHierT<
   H.nlev = d.nlev; H.tail_first = d.tail_first;
   H.hdr = ar.template take<MgHierHeader>(1);
   H.scal = ar.template take<double>(SC_COUNT_MG);
-  if (sizeof(C) == 4) {
-    Lv& D = H.L0;
-    D.nx = d.nx[0]; D.ny = d.ny[0]; D.n = D.nx * D.ny; D.per_x = per_x; D.per_y = per_y;
-    for (int s = 0; s < 5; ++s) D.c[s] = ar.template take<double>(D.n);
-    D.dinv = ar.template take<double>(D.n);
-  }
+  mg_level_dims(d, 0, per_x, per_y, H.L0);
+  if (sizeof(C) == 4) mg_level_take<double>(ar, H.L0);
   for (int l = 0; l < d.nlev; ++l) {
-    typename MgHierT<C>::Level& L = H.lv[l];
-    L.nx = d.nx[l]; L.ny = d.ny[l]; L.n = L.nx * L.ny; L.per_x = per_x; L.per_y = per_y;
-    for (int s = 0; s < 5; ++s) L.c[s] = ar.template take<C>(L.n);
-    L.dinv = ar.template take<C>(L.n);
+    mg_level_dims(d, l, per_x, per_y, H.lv[l]);
+    mg_level_take<C>(ar, H.lv[l]);
   }
   mg_hier_level0(H);
   return ar.ok();
@@ -69,18 +92,31 @@ inline bool mg_scratch_carve(int nx, int ny, AR& ar, MgScratchT<C>& S) {
     const size_t n = (size_t)d.nx[l] * d.ny[l];
     S.r[l] = ar.template take<C>(n); S.z[l] = ar.template take<C>(n); S.t[l] = ar.template take<C>(n);
   }
-  const size_t n0 = (size_t)d.nx[0] * d.ny[0];
-  if (sizeof(C) == 4) S.r64 = ar.template take<double>(n0);
-  mg_scratch_outer_r(S);
-  S.p[0] = ar.template take<double>(n0); S.p[1] = ar.template take<double>(n0); S.q = ar.template take<double>(n0);
-  S.parts = ar.template take<double>(4 * kMgGrid);
-  S.part_rz = ar.template take<double>(kMgGrid); S.part_pq = ar.template take<double>(kMgGrid); S.part_max = ar.template take<double>(kMgGrid);
-  S.scal = ar.template take<double>(SC_COUNT_MG);
-  S.st = ar.template take<MgState>(1);
+  mg_scratch_outer((size_t)d.nx[0] * d.ny[0], ar, S);
+  return ar.ok();
+}
+// the one workspace of the ordinary solve: a level's arrays and its vectors side by side, no header, the set-up's sums in the solve's `scal`
+template <typename C, typename AR>
+inline bool mg_plan_carve(int nx, int ny, int per_x, int per_y, AR& ar, MgPlanT<C>& P) {
+  const MgDims d = mg_dims(nx, ny);
+  MgHierT<C>& H = P.H;
+  MgScratchT<C>& S = P.S;
+  H.nlev = d.nlev; H.tail_first = d.tail_first;
+  H.hdr = nullptr;
+  mg_level_dims(d, 0, per_x, per_y, H.L0);
+  if (sizeof(C) == 4) mg_level_take<double>(ar, H.L0);
+  for (int l = 0; l < d.nlev; ++l) {
+    mg_level_dims(d, l, per_x, per_y, H.lv[l]);
+    mg_level_take<C>(ar, H.lv[l]);
+    S.r[l] = ar.template take<C>(H.lv[l].n); S.z[l] = ar.template take<C>(H.lv[l].n); S.t[l] = ar.template take<C>(H.lv[l].n);
+  }
+  mg_hier_level0(H);
+  mg_scratch_outer((size_t)H.L0.n, ar, S);
+  H.scal = S.scal;
   return ar.ok();
 }
 
-// the sizes the two carves need (0: not a grid the solver takes, or not a cycle precision)
+// the sizes the carves need (0: not a grid the solver takes, or not a cycle precision)
 struct CountingArena {
   size_t used = 0;
   template <typename T>
@@ -92,19 +128,22 @@ struct CountingArena {
   }
   bool ok() const { return true; }
 };
-inline size_t mg_hier_bytes(int nx, int ny, int cycle_elem_size) {
-  if (!mg_prepared_dims_ok(nx, ny) || (cycle_elem_size != 4 && cycle_elem_size != 8)) return 0;
+enum MgBuffer { MG_BUF_HIERARCHY, MG_BUF_SCRATCH, MG_BUF_WORKSPACE };
+template <typename C>
+inline size_t mg_carved_bytes(int nx, int ny, MgBuffer what) {
   CountingArena ar;
-  if (cycle_elem_size == 8) { MgHierT<double> H; mg_hier_carve(nx, ny, 0, 0, ar, H); }
-  else { MgHierT<float> H; mg_hier_carve(nx, ny, 0, 0, ar, H); }
+  MgPlanT<C> P;
+  if (what == MG_BUF_HIERARCHY) mg_hier_carve(nx, ny, 0, 0, ar, P.H);
+  else if (what == MG_BUF_SCRATCH) mg_scratch_carve(nx, ny, ar, P.S);
+  else mg_plan_carve(nx, ny, 0, 0, ar, P);
   return ar.used;
 }
-inline size_t mg_scratch_bytes(int nx, int ny, int cycle_elem_size) {
+inline size_t mg_buffer_bytes(int nx, int ny, int cycle_elem_size, MgBuffer what) {
   if (!mg_prepared_dims_ok(nx, ny) || (cycle_elem_size != 4 && cycle_elem_size != 8)) return 0;
-  CountingArena ar;
-  if (cycle_elem_size == 8) { MgScratchT<double> S; mg_scratch_carve(nx, ny, ar, S); }
-  else { MgScratchT<float> S; mg_scratch_carve(nx, ny, ar, S); }
-  return ar.used;
+  return cycle_elem_size == 8 ? mg_carved_bytes<double>(nx, ny, what) : mg_carved_bytes<float>(nx, ny, what);
 }
+inline size_t mg_hier_bytes(int nx, int ny, int cycle_elem_size) { return mg_buffer_bytes(nx, ny, cycle_elem_size, MG_BUF_HIERARCHY); }
+inline size_t mg_scratch_bytes(int nx, int ny, int cycle_elem_size) { return mg_buffer_bytes(nx, ny, cycle_elem_size, MG_BUF_SCRATCH); }
+inline size_t mg_plan_bytes(int nx, int ny, int cycle_elem_size) { return mg_buffer_bytes(nx, ny, cycle_elem_size, MG_BUF_WORKSPACE); }
 
 }  // namespace piso

@@ -1,4 +1,4 @@
-// The multigrid PCG of mg.hip on y-slabs (part of that translation unit: the per-cell code, the whole-grid kernels and mg_cycle are its).
+// The multigrid PCG of mg.hip on y-slabs (part of that translation unit: the per-cell code, the whole-grid kernels and the driver MgGridT are its).
 // The algorithm, its constants, the hierarchy's dimensions, the stopping rule, the constant-mode treatment and the device-side
 // alpha / beta are the one-GPU solver's; only where rows live and how sums are formed differ.  mg_slab_plan.h is the plan:
 //   * levels [0, g) are SHARDED: a rank holds its nyl >> l rows of every array plus one halo row below and one above (zero where the
@@ -6,7 +6,7 @@
 //     below and above in storage, coarse indices are the rank's own (2 x 2 aggregates never straddle a cut);
 //   * level g and everything coarser is REPLICATED: a rank forms its rows of level g from its rows of level g - 1 (the coefficients
 //     once per solve, the restricted residual once per cycle), the rows are all-gathered, and every rank runs levels g .. coarsest
-//     with the whole-grid kernels / mg_tail (mg_cycle from level g).  A rank reads its part of the correction e_g directly;
+//     with the whole-grid kernels / mg_tail (MgGridT::cycle from level g).  A rank reads its part of the correction e_g directly;
 //   * g = 0: the cycle is replicated altogether; the outer iteration (x, r, p, q) is always sharded at level 0.
 // What crosses a cut goes through the host collectives of slab_comm.h only (both transports carry it): halo rows by comm_exchange_rows,
 // every global sum from per-rank fixed-order partials by comm_allreduce_f64 (bitwise the same on every rank: every rank takes the same
@@ -245,15 +245,6 @@ struct MgSlabOps<double> {
   static void restrict_to(const Lv& L, const double* r, const double* z, double* rc, int nxc, int nyc, const MgState* st, const GeoSlab& g, bool, hipStream_t s) {
     mg_restrict_slab<<<mg_grid(nxc * nyc), kBlock, 0, s>>>(L, r, z, rc, nxc, nyc, st, g);
   }
-  // levels g .. coarsest on a rank's replicated copy, as the one-GPU plan runs them
-  static double* replicated(const MgSlabPlan& sp, bool use_tail, bool, RK& k, int nu, int*, hipStream_t s) {
-    MgPlan P;
-    P.nlev = sp.d.nlev; P.tail_first = sp.tail_first;
-    for (int l = 0; l < P.nlev; ++l) { P.lv[l] = k.lv[l]; P.r[l] = k.r[l]; P.z[l] = k.z[l]; P.t[l] = k.t[l]; }
-    P.part_rz = k.part_rz; P.st = k.st;
-    int n_rz = 0;
-    return mg_cycle(P, k.r[sp.g], nu, use_tail, &n_rz, s, sp.g);
-  }
   static const double* gather_src(RK& k, int g) { return g > 0 ? k.rchunk : k.ro; }
   static void init(const Lv& L0, RK& k, int g0, hipStream_t s) { mg_init<<<g0, kBlock, 0, s>>>(L0, k.b, k.x, k.ro, k.scal); }
   static void residual(const Lv& L0, RK& k, int g0, const GeoSlab& g, hipStream_t s) { mg_residual_slab<<<g0, kBlock, 0, s>>>(L0, k.b, k.x, k.ro, k.scal, k.st, g); }
@@ -274,6 +265,21 @@ struct MgSlabOps<double> {
     return PISO_OK;
   }
 };
+
+// levels g .. coarsest on a rank's replicated copy, as the one-GPU driver runs them: its plan as a view of the rank's levels (a cycle on its
+// own there - the fp64 cycle leaves partials of (r_g, z_g) nobody reads, the float32 cycle none)
+template <typename C>
+static C* mg_slab_replicated(const MgSlabPlan& sp, bool use_tail, bool vec, MgSlabRankT<C>& k, int nu, int* vec_mask, hipStream_t s) {
+  MgPlanT<C> P;
+  P.H.nlev = sp.d.nlev; P.H.tail_first = sp.tail_first;
+  for (int l = sp.g; l < P.H.nlev; ++l) { P.H.lv[l] = k.lv[l]; P.S.r[l] = k.r[l]; P.S.z[l] = k.z[l]; P.S.t[l] = k.t[l]; }
+  P.S.part_rz = k.part_rz; P.S.st = k.st;
+  MgGridT<C> run(P, nu, use_tail, vec, s);
+  int n_rz = 0;
+  C* z = run.cycle(k.r[sp.g], MgGridOps<C>::own_rd(k.r[sp.g]), &n_rz, sp.g);
+  *vec_mask |= run.vec_mask;
+  return z;
+}
 
 // ---- the driver ------------------------------------------------------------------------------------------------------------------------------
 template <typename C>
@@ -356,19 +362,7 @@ struct MgSlabT {
     PISO_LAUNCH_CHECK();
     PISO_HIP_CHECK(hipMemcpyAsync(pinned, R[0].st, sizeof(MgState), hipMemcpyDeviceToHost, s));
     PISO_HIP_CHECK(hipStreamSynchronize(s));
-    if (pinned->flags & MG_FLAG_BORDER) {
-      set_error_msg("piso_mg: non-zero border entry in a non-periodic direction (the reference stencil reads the neighbouring row there); use the plain CG");
-      return PISO_ERR_UNSUPPORTED_PATTERN;
-    }
-    if (pinned->flags & MG_FLAG_ZERO_DIAG_ROW) {
-      set_error_msg("piso_mg: a row with a zero diagonal has non-zero entries; use the plain CG");
-      return PISO_ERR_UNSUPPORTED_PATTERN;
-    }
-    if (pinned->flags & MG_FLAG_NOT_SINGULAR) {
-      set_error_msg("piso_mg: rank_deficient = 1 but the rows of the matrix do not sum to zero; use the plain CG");
-      return PISO_ERR_UNSUPPORTED_PATTERN;
-    }
-    return PISO_OK;
+    return mg_refusal(pinned->flags);
   }
 
   // halo rows of array `sel` of sharded level l
@@ -409,7 +403,7 @@ struct MgSlabT {
     // level g: the ranks' rows of the residual, all-gathered; levels g .. coarsest on every rank, as the one-GPU plan runs them
     PISO_TRY(link.allgather(R, [G](RK& k) { return Ops::gather_src(k, G); }, [G](RK& k) { return k.r[G]; }, (size_t)R[0].chunk.n));
     std::vector<C*> zg(nloc());
-    for (int q = 0; q < nloc(); ++q) zg[q] = Ops::replicated(sp, use_tail, vec, R[q], nu, &vec_mask, s);
+    for (int q = 0; q < nloc(); ++q) zg[q] = mg_slab_replicated(sp, use_tail, vec, R[q], nu, &vec_mask, s);
     int n_rz = 0;
     if constexpr (Ops::kRunsG0) {
       if (G == 0) {
@@ -491,17 +485,12 @@ struct MgSlabT {
       PISO_LAUNCH_CHECK();
     }
     if (iterations_out) *iterations_out = iterations;
-    int recomputed = 0;
-    for (int k = 1; k < iterations; ++k) recomputed += (k + 1) % residual_reset == 0;
-    record(sweeps, iterations, iterations, recomputed);
+    record(sweeps, iterations, iterations, mg_recomputations(iterations, residual_reset));
     return PISO_OK;
   }
 
   void record(int sweeps, int iterations, int cycles, int recomputed) const {
-    int* d = tl_mg_dispatch;
-    d[MD_LEVELS] = sp.d.nlev; d[MD_TAIL_FIRST] = use_tail ? sp.tail_first : -1; d[MD_SWEEPS] = sweeps; d[MD_ITERATIONS] = iterations;
-    d[MD_CYCLES] = cycles; d[MD_RESIDUAL_RECOMPUTATIONS] = recomputed; d[MD_CYCLE_ELEM] = (int)sizeof(C); d[MD_VEC_MASK] = vec_mask;
-    tl_mg_dispatch_n = MD_COUNT;
+    mg_record(sp.d.nlev, use_tail ? sp.tail_first : -1, sweeps, iterations, cycles, recomputed, (int)sizeof(C), vec_mask);
   }
 
   // copy rank-local results out and make every rank return the same status

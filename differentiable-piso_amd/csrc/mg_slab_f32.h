@@ -6,7 +6,7 @@
 //   * four-cell kernels: the bodies of mg_f32.h with QuadSlab - the quads below / above are the storage rows -1 / +1 (halo rows are real
 //     rows), coarse rows go through GeoSlab::erow.  Rows stay 16-byte aligned: the halo offset is nx floats and these kernels run only where
 //     nx % 4 == 0; other levels run the scalar slab kernels; option mg_f32_vec 0 runs scalar everywhere (the same z);
-//   * levels g .. coarsest: the rank's float rows of level g are all-gathered and every rank runs MgRunF::cycle from level g.
+//   * levels g .. coarsest: the rank's float rows of level g are all-gathered and every rank runs MgGridT<float>::cycle from level g.
 // g = 0 (the whole cycle replicated) is refused: a float32 cycle has nothing to gain there.
 #pragma once
 
@@ -115,18 +115,6 @@ struct MgSlabOps<float> {
   static void restrict_to(const LvF& L, const float* r, const float* z, float* rc, int nxc, int nyc, const MgState* st, const GeoSlab& g, bool x4, hipStream_t s) {
     if (x4) mg_restrict_slab_f32x4<<<mg_grid((L.nx >> 2) * nyc), kBlock, 0, s>>>(L, r, z, rc, nxc, nyc, st, g);
     else mg_restrict_slab_f32<<<mg_grid(nxc * nyc), kBlock, 0, s>>>(L, r, z, rc, nxc, nyc, st, g);
-  }
-  // levels g .. coarsest with the whole-grid float32 kernels and mg_tail_f32 (MgRunF::cycle from level g)
-  static float* replicated(const MgSlabPlan& sp, bool use_tail, bool vec, RK& k, int nu, int* vec_mask, hipStream_t s) {
-    MgPlanF P;
-    P.nlev = sp.d.nlev; P.tail_first = sp.tail_first;
-    for (int l = sp.g; l < P.nlev; ++l) { P.lv[l] = k.lv[l]; P.r[l] = k.r[l]; P.z[l] = k.z[l]; P.t[l] = k.t[l]; }
-    P.part_rz = k.part_rz; P.st = k.st;
-    MgRunF run{P, nu, use_tail, vec, s};
-    int n_rz = 0;
-    float* z = run.cycle(k.r[sp.g], nullptr, &n_rz, sp.g);
-    *vec_mask |= run.vec_mask;
-    return z;
   }
   static const float* gather_src(RK& k, int) { return k.rchunk; }
   static void init(const Lv& L0, RK& k, int g0, hipStream_t s) { mg_init_f32<<<g0, kBlock, 0, s>>>(L0, k.b, k.x, k.ro, k.scal, k.r[0]); }

@@ -310,8 +310,8 @@ def cg_solve_slab_emulated(slabs, nx, ny, per_x, per_y, L, div, accuracy, max_it
 # cycle_dtype=torch.float32: the float32 V-cycle under the same fp64, sharded outer iteration (the *_c32_f64 entries); a plan that replicates
 # the whole cycle (g = 0) is refused there.
 def _mg_slab_fn(stem, cycle_dtype):
-    from .solvers import _mg_cycle_elem
-    return getattr(N.lib, "piso_mg_%s_%s" % (stem, "f64" if _mg_cycle_elem(cycle_dtype) == 8 else "c32_f64"))
+    from .solvers import mg_entry
+    return mg_entry(stem, cycle_dtype)
 
 
 def _mg_slab_workspace(nx, nyl, world, local_ranks, device, tag, cycle_dtype=torch.float64):

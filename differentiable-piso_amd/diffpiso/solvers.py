@@ -620,9 +620,13 @@ def _mg_cycle_elem(cycle_dtype):
     raise ValueError("cycle_dtype must be torch.float64 or torch.float32 (got %r)" % (cycle_dtype,))
 
 
+def mg_entry(stem, cycle_dtype):
+    """The C entry piso_mg_<stem>_f64 / piso_mg_<stem>_c32_f64 for the precision of the cycle (one-GPU, prepared and slab entries alike)."""
+    return getattr(N.lib, "piso_mg_%s%s" % (stem, "_f64" if _mg_cycle_elem(cycle_dtype) == 8 else "_c32_f64"))
+
+
 def mg_workspace(nx, ny, device, cycle_dtype=torch.float64):
-    elem = _mg_cycle_elem(cycle_dtype)
-    nbytes = N.lib.piso_mg_workspace_bytes(nx, ny) if elem == 8 else N.lib.piso_mg_workspace_bytes_cycle(nx, ny, elem)
+    nbytes = N.lib.piso_mg_workspace_bytes_cycle(nx, ny, _mg_cycle_elem(cycle_dtype))
     if nbytes == 0:
         raise N.PisoNativeError("the multigrid pressure solver needs at least 4 cells in each dimension (got %d x %d); "
                                 "use PisoPressureSolverCudaCustom" % (ny, nx))
@@ -658,7 +662,7 @@ def mg_solve_native(nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank
     right-hand side, else from zero (csrc/mg_guess.h; N.mg_last_guess() says which); x_out: where the result goes (x0 itself is allowed)."""
     if L.dtype != torch.float64:
         raise N.PisoNativeError("the multigrid pressure solver is fp64 only; use the plain CG (cg_solve_native) for float32")
-    sfx = "_f64" if _mg_cycle_elem(cycle_dtype) == 8 else "_c32_f64"
+    solve, solve_guess = mg_entry("pcg_solve", cycle_dtype), mg_entry("pcg_solve_guess", cycle_dtype)
     div = div.reshape(-1).to(torch.float64).contiguous()
     guess = None if x0 is None else (x0 if x0 is x_out else _mg_guess(x0, div))
     x = _mg_x_out(x_out, div)
@@ -668,16 +672,16 @@ def mg_solve_native(nx, ny, per_x, per_y, L, div, accuracy, max_iterations, rank
     tail = (N.ptr(x), C.c_float(accuracy), int(max_iterations), int(bool(rank_deficient)), int(residual_reset), int(sweeps), C.byref(it), N.ptr(ws),
             C.c_size_t(ws.numel()), N.stream_ptr())
     if guess is None:
-        st = getattr(N.lib, "piso_mg_pcg_solve" + sfx)(*(head + tail))
+        st = solve(*(head + tail))
     else:
-        st = getattr(N.lib, "piso_mg_pcg_solve_guess" + sfx)(*(head + (N.ptr(guess),) + tail))
+        st = solve_guess(*(head + (N.ptr(guess),) + tail))
     N.check(st, "piso_mg_pcg_solve")
     return x, it.value
 
 
 def mg_vcycle_native(nx, ny, per_x, per_y, L, r, sweeps=2, cycle_dtype=torch.float64):
     """z = M^-1 r: one V-cycle of the multigrid preconditioner (tests, measurements); float64 in and out in either precision of the cycle."""
-    fn = N.lib.piso_mg_vcycle_f64 if _mg_cycle_elem(cycle_dtype) == 8 else N.lib.piso_mg_vcycle_c32_f64
+    fn = mg_entry("vcycle", cycle_dtype)
     r = r.reshape(-1).to(torch.float64).contiguous()
     z = torch.empty_like(r)
     ws = mg_workspace(nx, ny, r.device, cycle_dtype)
@@ -688,7 +692,7 @@ def mg_vcycle_native(nx, ny, per_x, per_y, L, r, sweeps=2, cycle_dtype=torch.flo
 
 def mg_level_native(nx, ny, per_x, per_y, L, level, cycle_dtype=torch.float64):
     """-> (A_level [nyl * nxl, 5], nxl, nyl), or None past the coarsest level (tests); the float32 cycle's entries come widened to float64."""
-    fn = N.lib.piso_mg_level_f64 if _mg_cycle_elem(cycle_dtype) == 8 else N.lib.piso_mg_level_c32_f64
+    fn = mg_entry("level", cycle_dtype)
     ws = mg_workspace(nx, ny, L.device, cycle_dtype)
     nxl, nyl = C.c_int(0), C.c_int(0)
     if fn(nx, ny, int(per_x), int(per_y), N.ptr(L), int(level), C.byref(nxl), C.byref(nyl), None, N.ptr(ws), C.c_size_t(ws.numel()),
@@ -722,9 +726,6 @@ class MgHierarchy(object):
         self.matrix = None
         self.key = None
 
-    def _suffix(self):
-        return "_f64" if self.elem == 8 else "_c32_f64"
-
     def scratch(self):
         return N.workspace(N.lib.piso_mg_solve_workspace_bytes(self.nx, self.ny, self.elem), self.device, "mg_solve")
 
@@ -734,7 +735,7 @@ class MgHierarchy(object):
             raise N.PisoNativeError("the multigrid pressure solver is fp64 only; use the plain CG (cg_solve_native) for float32")
         self.matrix, self.key = None, None
         ws = self.scratch()
-        fn = getattr(N.lib, "piso_mg_prepare" + self._suffix())
+        fn = mg_entry("prepare", self.cycle_dtype)
         N.check(fn(self.nx, self.ny, int(self.per_x), int(self.per_y), N.ptr(L), int(self.rank_deficient), N.ptr(self.buf), C.c_size_t(self.buf.numel()),
                    N.ptr(ws), C.c_size_t(ws.numel()), N.stream_ptr()), "piso_mg_prepare")
         self.matrix = L.detach()
@@ -767,9 +768,9 @@ def mg_solve_prepared_guess_native(h, div, x0, accuracy, max_iterations, residua
     tail = (N.ptr(x), C.c_float(accuracy), int(max_iterations), int(h.rank_deficient), int(residual_reset), int(sweeps), C.byref(it), N.ptr(ws),
             C.c_size_t(ws.numel()), N.stream_ptr())
     if guess is None:
-        st = getattr(N.lib, "piso_mg_pcg_solve_prepared" + h._suffix())(*(head + tail))
+        st = mg_entry("pcg_solve_prepared", h.cycle_dtype)(*(head + tail))
     else:
-        st = getattr(N.lib, "piso_mg_pcg_solve_prepared_guess" + h._suffix())(*(head + (N.ptr(guess),) + tail))
+        st = mg_entry("pcg_solve_prepared_guess", h.cycle_dtype)(*(head + (N.ptr(guess),) + tail))
     N.check(st, "piso_mg_pcg_solve_prepared")
     return x, it.value
 
@@ -779,7 +780,7 @@ def mg_vcycle_prepared_native(h, r, sweeps=2):
     r = r.reshape(-1).to(torch.float64).contiguous()
     z = torch.empty_like(r)
     ws = h.scratch()
-    fn = getattr(N.lib, "piso_mg_vcycle_prepared" + h._suffix())
+    fn = mg_entry("vcycle_prepared", h.cycle_dtype)
     N.check(fn(h.nx, h.ny, int(h.per_x), int(h.per_y), N.ptr(h.buf), C.c_size_t(h.buf.numel()), N.ptr(r), N.ptr(z), int(sweeps), N.ptr(ws),
                C.c_size_t(ws.numel()), N.stream_ptr()), "piso_mg_vcycle_prepared")
     return z

@@ -1,13 +1,15 @@
-// Host driver of tests/test_mg_prepared_cpu.py: the two carves of a prepared multigrid solve (csrc/mg_prepared_carve.h) are pure C++, so both
-// can be walked without a card - against arenas WITHOUT memory (nothing is dereferenced).  Built with -fsanitize=address,undefined.
+// Host driver of tests/test_mg_prepared_cpu.py: the two carves of a prepared multigrid solve and the one carve of the ordinary solve's
+// workspace (csrc/mg_prepared_carve.h) are pure C++, so all can be walked without a card - against arenas WITHOUT memory (nothing is
+// dereferenced).  Built with -fsanitize=address,undefined.
 // Reads one query per line from stdin
 //     nx ny elem            (elem 4: the float32 cycle, 8: the fp64 cycle)
 // and prints: status (0 ok, 1 not a grid / precision the solver takes, 2 a check failed), the bytes of the hierarchy, the bytes of the scratch,
-// and the first failed check (- if none).  Checks, for each carve: every array starts on a 256-byte boundary; the arrays do not overlap and end
+// the first failed check (- if none), and the bytes of the ordinary workspace.  Checks, for each carve: every array starts on a 256-byte boundary; the arrays do not overlap and end
 // at the counted size; the counted size is mg_hier_bytes / mg_scratch_bytes; an arena of exactly that size is accepted and one byte less is
 // refused; the levels have the dimensions of mg_dims; every float row of a level with nx % 4 == 0 is 16-byte aligned.  Across the two: laid out
 // one after the other in one address space, no array of the scratch touches the hierarchy; the fp64 cycle's level 0 and outer r are lv[0] and
-// r[0], the float32 cycle's are arrays of their own.
+// r[0], the float32 cycle's are arrays of their own.  The ordinary workspace: the same checks of its one carve against mg_plan_bytes, no header,
+// the hierarchy's sums in the solve's `scal`, the same aliasing of level 0 and the outer r.
 #include <stdint.h>
 #include <stdio.h>
 
@@ -113,18 +115,54 @@ int walk(int nx, int ny, size_t* hier_bytes, size_t* scratch_bytes, std::string*
   return 0;
 }
 
+// the one workspace of the ordinary solve
+template <typename C>
+int walk_plan(int nx, int ny, size_t* bytes, std::string* why) {
+  const uintptr_t base = 256;
+  CheckedArena aw(base, ~(size_t)0);
+  piso::MgPlanT<C> P;
+  if (!piso::mg_plan_carve(nx, ny, 1, 0, aw, P)) { *why = "the counting walk of the workspace failed"; return 2; }
+  *bytes = aw.used;
+  if (!tidy(aw, why)) return 2;
+  if (aw.used != piso::mg_plan_bytes(nx, ny, (int)sizeof(C))) { *why = "the workspace's walk and mg_plan_bytes disagree"; return 2; }
+  const piso::MgDims d = piso::mg_dims(nx, ny);
+  if (P.H.nlev != d.nlev || P.H.tail_first != d.tail_first) { *why = "the workspace's levels are not mg_dims'"; return 2; }
+  if (P.H.L0.nx != nx || P.H.L0.ny != ny || P.H.L0.n != nx * ny || P.H.L0.per_x != 1 || P.H.L0.per_y != 0) { *why = "the workspace's fp64 level 0 has other dimensions"; return 2; }
+  for (int l = 0; l < d.nlev; ++l) {
+    const auto& L = P.H.lv[l];
+    if (L.nx != d.nx[l] || L.ny != d.ny[l] || L.n != L.nx * L.ny || L.per_x != 1 || L.per_y != 0) { *why = "a level of the workspace has not the plan's dimensions"; return 2; }
+    const C* arr[9] = {L.c[0], L.c[1], L.c[2], L.c[3], L.c[4], L.dinv, P.S.r[l], P.S.z[l], P.S.t[l]};
+    if (sizeof(C) == 4 && L.nx % 4 == 0)
+      for (int j = 0; j < L.ny; ++j)
+        for (const C* a : arr)
+          if ((reinterpret_cast<uintptr_t>(a) + (size_t)j * L.nx * sizeof(C)) % 16) { *why = "a float row of a quad level of the workspace is not 16-byte aligned"; return 2; }
+  }
+  if (P.H.hdr != nullptr || P.H.scal != P.S.scal) { *why = "the ordinary workspace has a header or a second copy of the sums"; return 2; }
+  const bool aliased = reinterpret_cast<const void*>(P.H.L0.c[2]) == reinterpret_cast<const void*>(P.H.lv[0].c[2]);
+  const bool r_aliased = reinterpret_cast<const void*>(P.S.r64) == reinterpret_cast<const void*>(P.S.r[0]);
+  if (sizeof(C) == 8 && (!aliased || !r_aliased)) { *why = "the fp64 cycle's level 0 / outer r are not lv[0] / r[0] in the workspace"; return 2; }
+  if (sizeof(C) == 4 && (aliased || r_aliased)) { *why = "the float32 cycle's fp64 level 0 / outer r share storage with the float32 arrays in the workspace"; return 2; }
+  piso::MgPlanT<C> P2;
+  CheckedArena we(base, aw.used), wshort(base, aw.used - 1);
+  if (!piso::mg_plan_carve(nx, ny, 0, 0, we, P2)) { *why = "a workspace of the counted size is refused"; return 2; }
+  if (piso::mg_plan_carve(nx, ny, 0, 0, wshort, P2)) { *why = "a workspace one byte short is accepted"; return 2; }
+  return 0;
+}
+
 }  // namespace
 
 int main() {
   int nx, ny, elem;
   while (scanf("%d %d %d", &nx, &ny, &elem) == 3) {
-    size_t hb = 0, sb = 0;
+    size_t hb = 0, sb = 0, wb = 0;
     int status = 1;
     std::string why = "-";
     if (piso::mg_hier_bytes(nx, ny, elem) != 0 && piso::mg_scratch_bytes(nx, ny, elem) != 0)
       status = elem == 4 ? walk<float>(nx, ny, &hb, &sb, &why) : walk<double>(nx, ny, &hb, &sb, &why);
+    if (status == 0) status = elem == 4 ? walk_plan<float>(nx, ny, &wb, &why) : walk_plan<double>(nx, ny, &wb, &why);
     else if ((piso::mg_hier_bytes(nx, ny, elem) != 0) != (piso::mg_scratch_bytes(nx, ny, elem) != 0)) { status = 2; why = "one size is zero and the other is not"; }
-    printf("%d\t%zu\t%zu\t%s\n", status, hb, sb, why.c_str());
+    if ((status == 1) != (piso::mg_plan_bytes(nx, ny, elem) == 0)) { status = 2; why = "mg_plan_bytes and the prepared sizes disagree about what the solver takes"; }
+    printf("%d\t%zu\t%zu\t%s\t%zu\n", status, hb, sb, why.c_str(), wb);
   }
   return 0;
 }

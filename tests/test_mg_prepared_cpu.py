@@ -1,7 +1,7 @@
 """What the prepared multigrid hierarchy (csrc/mg_prepared.h) promises without a GPU: the two size entries, the exported and declared C
 entries in both precisions of the cycle, the reuse_hierarchy option's surface and its refusal next to a slab communicator, and the host-side
-carves of the two buffers (csrc/mg_prepared_carve.h) walked by a stand-alone program built with -fsanitize=address,undefined against arenas
-without memory."""
+carves of the two buffers and of the ordinary solve's one workspace (csrc/mg_prepared_carve.h) walked by a stand-alone program built with
+-fsanitize=address,undefined against arenas without memory."""
 import inspect
 import os
 import re
@@ -15,6 +15,11 @@ ROOT = os.path.dirname(HERE)
 GRIDS = ((12, 10), (64, 64), (96, 80), (70, 66), (520, 516), (1024, 256), (2048, 2048))      # (nx, ny)
 NO_GRIDS = ((3, 40), (40, 3), (0, 0), (-4, 64), (1 << 16, 1 << 15))                          # below 4 cells a dimension, or above 2^30 cells
 STEMS = ("prepare", "pcg_solve_prepared", "vcycle_prepared")
+# piso_mg_workspace_bytes_cycle(nx, ny, elem) as the library returned it before the ordinary workspace got one carve over the cycle's type
+# (two hand-written walks then): every array keeps its offset, so every size stays
+WORKSPACE_BYTES = {(12, 10, 4): 74768, (12, 10, 8): 72208, (64, 64, 4): 583440, (64, 64, 8): 549904, (96, 80, 4): 1042960, (96, 80, 8): 979216,
+                   (70, 66, 4): 659216, (70, 66, 8): 620560, (520, 516, 4): 34421008, (520, 516, 8): 32276752, (1024, 256, 4): 33611280,
+                   (1024, 256, 8): 31513360, (2048, 2048, 4): 536930064, (2048, 2048, 8): 503374864}
 
 
 def test_size_entries():
@@ -22,10 +27,12 @@ def test_size_entries():
     hier, solve, whole = N.lib.piso_mg_hierarchy_bytes, N.lib.piso_mg_solve_workspace_bytes, N.lib.piso_mg_workspace_bytes_cycle
     for nx, ny in GRIDS:
         for elem in (4, 8):
+            assert whole(nx, ny, elem) == WORKSPACE_BYTES[nx, ny, elem]
             assert whole(nx, ny, elem) > 0 and hier(nx, ny, elem) > 0 and solve(nx, ny, elem) > 0
             # the two buffers hold what the one workspace of the ordinary solve holds, plus the header and the second copy of the sums
             assert whole(nx, ny, elem) < hier(nx, ny, elem) + solve(nx, ny, elem) <= whole(nx, ny, elem) + 2 * 256
             assert hier(nx, ny, elem) >= 6 * 8 * nx * ny                   # at least the fp64 level 0
+        assert N.lib.piso_mg_workspace_bytes(nx, ny) == WORKSPACE_BYTES[nx, ny, 8]
         assert hier(nx, ny, 4) > hier(nx, ny, 8)                           # (the float32 mode keeps the fp64 level 0 AND the float32 levels)
         for elem in (0, 2, 16, -4):
             assert whole(nx, ny, elem) == hier(nx, ny, elem) == solve(nx, ny, elem) == 0
@@ -95,9 +102,10 @@ def test_the_carves_walk_clean_under_the_sanitizers(tmp_path):
     lines = run.stdout.strip("\n").split("\n")
     assert len(lines) == len(queries)
     for (nx, ny, elem), line in zip(queries, lines):
-        status, hb, sb, why = line.split("\t")
+        status, hb, sb, why, wb = line.split("\t")
         if (nx, ny) in NO_GRIDS or elem == 2:
-            assert (int(status), int(hb), int(sb)) == (1, 0, 0), (nx, ny, elem, why)
+            assert (int(status), int(hb), int(sb), int(wb)) == (1, 0, 0, 0), (nx, ny, elem, why)
             continue
         assert int(status) == 0, (nx, ny, elem, why)
         assert int(hb) == N.lib.piso_mg_hierarchy_bytes(nx, ny, elem) and int(sb) == N.lib.piso_mg_solve_workspace_bytes(nx, ny, elem), (nx, ny, elem)
+        assert int(wb) == N.lib.piso_mg_workspace_bytes_cycle(nx, ny, elem) == WORKSPACE_BYTES[nx, ny, elem], (nx, ny, elem)
