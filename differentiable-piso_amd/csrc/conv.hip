@@ -17,10 +17,13 @@
 //                  partials in a fixed order (deterministic, no atomics)
 //
 // Which instance a call runs, with what launch shape, and what it refuses: conv_dispatch.h (conv_plan, the instance table).  Here: the kernels (their text:
-// conv_kernels.inc, compiled for the two geometries), and conv_launch - the only host code that names one.
+// conv_kernels.inc, compiled for the two geometries), and conv_launch - the only host code that names one.  Shapes without a fixed instance:
+// the run-time-shaped family of conv_any.hip (piso_conv2d_forward_any / piso_conv2d_wgrad_any; conv_any.h: its launcher) - the entries, the
+// thread-local record and the reducers of its weight gradient are here.
 #include "piso_common.h"
 #include "options.h"
 #include "conv_dispatch.h"
+#include "conv_any.h"
 
 namespace piso {
 
@@ -194,7 +197,18 @@ static int conv_launch_as(const ConvPlan& p, const float* in, const float* b, fl
   PISO_LAUNCH_CHECK();
   return PISO_OK;
 }
+// the run-time-shaped family: its main kernel (conv_any.hip), then - weight gradient - the reducers above on [band][ks][ks][CINP16][COUTP]
+static int conv_launch_any(const ConvPlan& p, const float* in, const float* b, float* out, float* part, hipStream_t stream) {
+  const int st = conv_any_launch(p, in, b, p.entry == CE_FORWARD ? out : part, stream);
+  if (st != PISO_OK || p.entry == CE_FORWARD) return st;
+  const int taps = p.KS * p.KS, cinp16 = 16 * p.C, coutp = round_up(p.gx.cout, 16);
+  if (p.reducer == 4) conv_wgrad_reduce4_kernel<<<p.reduce_grid, kBlock, 0, stream>>>(part, out, p.nblocks, taps, cinp16, coutp, p.gx.cin, p.gx.cout);
+  else conv_wgrad_reduce_kernel<<<p.reduce_grid, kBlock, 0, stream>>>(part, out, p.nblocks, taps, cinp16, coutp, p.gx.cin, p.gx.cout);
+  PISO_LAUNCH_CHECK();
+  return PISO_OK;
+}
 static int conv_launch(const ConvPlan& p, const float* in, const float* b, float* out, float* part, hipStream_t stream) {
+  if (p.family == CF_FWD_ANY || p.family == CF_WG_ANY) return conv_launch_any(p, in, b, out, part, stream);
   return p.ex ? conv_launch_as<true>(p, in, b, out, part, stream) : conv_launch_as<false>(p, in, b, out, part, stream);
 }
 
@@ -288,6 +302,30 @@ int piso_conv2d_wgrad_ex(const float* in, const float* grad_out, float* dw, int 
   const piso::OptScope knobs;
   const ConvQuery q{CE_WGRAD, H, W, cin, cout, ks, pad_y, 0, opt(OPT_CONV_LDS), !in || !grad_out || !dw || !workspace, misaligned16(in, grad_out),
                     misaligned16(dw, workspace), workspace_bytes, true, pad_x, wrap_y, wrap_x};
+  return conv_run(q, in, grad_out, dw, workspace, stream);
+}
+
+// The run-time-shaped family (conv_any.hip), whatever the instance tables hold.  Weight layout of piso_conv2d_forward_any:
+//   [ks][ks][CINP4][COUTP], CINP4 = round_up(cin, 4), COUTP = round_up(cout, 16): element [ky][kx][ci][co] = W[ky][kx][ci][co], zero beyond
+size_t piso_conv2d_weight_elems_any(int ks, int cin, int cout) { return conv_weight_elems_any(ks, cin, cout); }
+
+size_t piso_conv2d_wgrad_any_workspace_bytes(int ks, int cin, int cout, int Ho) { return conv_wgrad_any_workspace_bytes(ks, cin, cout, Ho); }
+
+int piso_conv2d_instantiated(int entry, int ks, int cin, int cout) { return conv_instantiated(entry, ks, cin, cout); }
+
+int piso_conv2d_forward_any(const float* in, const float* w_laid_out, float* out, int H, int W, int cin, int cout, int ks, int pad_y, int pad_x,
+                            int wrap_y, int wrap_x, int leaky_out, piso_stream_t stream) {
+  const piso::OptScope knobs;
+  const ConvQuery q{CE_FORWARD, H, W, cin, cout, ks, pad_y, leaky_out, opt(OPT_CONV_LDS), !in || !w_laid_out || !out, misaligned16(in, w_laid_out), false, 0,
+                    true, pad_x, wrap_y, wrap_x, true};
+  return conv_run(q, in, w_laid_out, out, nullptr, stream);
+}
+
+int piso_conv2d_wgrad_any(const float* in, const float* grad_out, float* dw, int H, int W, int cin, int cout, int ks, int pad_y, int pad_x, int wrap_y,
+                          int wrap_x, void* workspace, size_t workspace_bytes, piso_stream_t stream) {
+  const piso::OptScope knobs;
+  const ConvQuery q{CE_WGRAD, H, W, cin, cout, ks, pad_y, 0, opt(OPT_CONV_LDS), !in || !grad_out || !dw || !workspace, misaligned16(in, grad_out),
+                    misaligned16(dw, workspace), workspace_bytes, true, pad_x, wrap_y, wrap_x, true};
   return conv_run(q, in, grad_out, dw, workspace, stream);
 }
 

@@ -2,6 +2,9 @@
 // the PACK4 and 64 -> 64 rows, conv_fwd_has_lds: the one statement of it - the planner asks at run time, conv_launch at compile time) and the
 // plan of a call (conv_plan: pure, no HIP calls - every refusal of both entry points, the family, every launch dimension, the bands, the
 // reducer, i.e. the whole dispatch record).  Plain C++: a host compiler can include this file and walk every plan without a card.
+// Beside the instances: the run-time-shaped family of conv_any.hip (ConvQuery::any, conv_plan_any - its own rules: odd kernel sizes up to 9, up to 256
+// channels, no alignment rule; the same record with the families CF_FWD_ANY / CF_WG_ANY), reached only through the *_any entries, and
+// conv_instantiated: which shapes the instance tables serve, asked of conv_plan itself.
 #pragma once
 #include <stddef.h>
 
@@ -47,6 +50,22 @@ inline size_t conv_wgrad_workspace_bytes(int ks, int cin, int cout) {
   return (size_t)kWgradMaxBlocks * ks * ks * round_up(cin, 16) * round_up(cout, 16) * sizeof(float);
 }
 
+// ---- the run-time-shaped family (conv_any.hip: conv_forward_any_kernel<NT, LEAKY>, conv_wgrad_any_kernel<NT>; piso_conv2d_forward_any /
+// piso_conv2d_wgrad_any): any odd kernel size up to kConvAnyMaxKs, any channel counts up to kConvAnyMaxChannels.  Output channels are served in
+// GROUPS of up to 4 tiles of 16 - the groups are balanced: cout 80 is 5 tiles = 2 groups of NT 3 (the last one partly beyond COUTP, guarded).
+constexpr int kConvAnyMaxKs = 9, kConvAnyMaxChannels = 256;
+constexpr int kWgradAnyMaxBlocks = 64;   // row bands of conv_wgrad_any_kernel: the workspace of a wide layer stays small (5 x 5, 128 -> 128: 105 MB)
+constexpr int conv_any_groups(int cout) { return ceil_div(ceil_div(cout, 16), 4); }
+constexpr int conv_any_nt(int cout) { return ceil_div(ceil_div(cout, 16), conv_any_groups(cout)); }
+constexpr int conv_any_rows_per_block(int Ho) { return Ho < 1 ? 1 : ceil_div(Ho, kWgradAnyMaxBlocks); }
+constexpr int conv_any_nblocks(int Ho) { return Ho < 1 ? 1 : ceil_div(Ho, conv_any_rows_per_block(Ho)); }
+// weights of piso_conv2d_forward_any: [ks][ks][CINP4][COUTP], CINP4 = round_up(cin, 4), COUTP = round_up(cout, 16), zero filled
+inline size_t conv_weight_elems_any(int ks, int cin, int cout) { return (size_t)ks * ks * round_up(cin, 4) * round_up(cout, 16); }
+// partials of piso_conv2d_wgrad_any: [band][ks][ks][CINP16][COUTP], band < conv_any_nblocks(Ho)
+inline size_t conv_wgrad_any_workspace_bytes(int ks, int cin, int cout, int Ho) {
+  return (size_t)conv_any_nblocks(Ho) * ks * ks * round_up(cin, 16) * round_up(cout, 16) * sizeof(float);
+}
+
 // ---- the instances.  A shape is the record's (KS, C, NT, IPW): C = CINP forward (input channels rounded up to 4 or to 16), MTI = CINP16 / 16
 // for the weight gradient; NT output-channel tiles of 16; IPW items per wave (weight gradient: enough waves to fill the chip, few enough
 // registers for the 4 x 4-pixel prefetch).  Forward: the layers of the closure and of its input-gradient pass (channel roles swapped).
@@ -82,7 +101,7 @@ constexpr int conv_wg_reducer(int cout) { return cout % 4 == 0 ? 4 : 1; }
 
 // ---- the plan: everything an entry point decides before it launches
 enum { CE_FORWARD = 1, CE_WGRAD = 2 };
-enum { CF_FWD_DIRECT = 0, CF_FWD_LDS, CF_WG_GENERIC, CF_WG_GENERIC_LDS, CF_WG_PACK4, CF_WG_64, CF_WG_64_LDS };
+enum { CF_FWD_DIRECT = 0, CF_FWD_LDS, CF_WG_GENERIC, CF_WG_GENERIC_LDS, CF_WG_PACK4, CF_WG_64, CF_WG_64_LDS, CF_FWD_ANY, CF_WG_ANY };
 struct ConvQuery {
   int entry;                         // CE_FORWARD (piso_conv2d_forward) | CE_WGRAD (piso_conv2d_wgrad)
   int H, W, cin, cout, ks, pad;
@@ -95,6 +114,8 @@ struct ConvQuery {
   bool ex = false;
   int pad_x = 0;
   int wrap_y = 0, wrap_x = 0;        // != 0: the axis is periodic
+  // the *_any entries (always with the fields of `ex`): the run-time-shaped family, whatever the instance tables hold
+  bool any = false;
 };
 constexpr int kConvRecordFields = 15;
 struct ConvPlan {
@@ -106,6 +127,9 @@ struct ConvPlan {
   // the dispatch record (include/piso_hip.h: piso_conv_last_dispatch; with g.Ho, g.Wo) = the launch of the main kernel: grid (grid_x, grid_y), block
   int entry, KS, C, NT, IPW, family, leaky, grid_x, grid_y, block, rows_per_block, nblocks, reducer;
   int reduce_grid;                   // gridDim.x of the reducer
+  // family CF_FWD_ANY / CF_WG_ANY: groups of NT output-channel tiles.  grid_y: forward - the groups;  wgrad - item_groups x groups, item_groups
+  // workgroups of four waves over the work items (tap, 16-channel tile of ci), one item per wave: blockIdx.y = group * item_groups + item group
+  int groups = 1, item_groups = 1;
 };
 inline void conv_record(const ConvPlan& p, int (&r)[kConvRecordFields]) {
   const int v[kConvRecordFields] = {p.entry, p.KS, p.C, p.NT, p.IPW, p.family, p.leaky, p.grid_x, p.grid_y, p.block, p.rows_per_block, p.nblocks, p.reducer,
@@ -113,7 +137,57 @@ inline void conv_record(const ConvPlan& p, int (&r)[kConvRecordFields]) {
   for (int i = 0; i < kConvRecordFields; ++i) r[i] = v[i];
 }
 
+// the plan of a *_any call: its own rules (no instance table, no alignment rule), the same record
+inline ConvPlan conv_plan_any(const ConvQuery& q) {
+  ConvPlan p{};
+  const bool fwd = q.entry == CE_FORWARD;
+  const auto refuse = [&p, fwd](const char* f, const char* w) { p.status = PISO_ERR_INVALID_ARG; p.msg = fwd ? f : w; return p; };
+  const int cin = q.cin, cout = q.cout, ks = q.ks;
+  p.g = conv_geom(q.H, q.W, cin, cout, ks, q.pad);
+  p.g.Wo = q.W + 2 * q.pad_x - ks + 1;
+  p.ex = true;
+  p.gx = ConvGeomEx{q.H, q.W, p.g.Ho, p.g.Wo, q.pad, q.pad_x, q.wrap_y ? q.H : 0, q.wrap_x ? q.W : 0, cin, cout};
+  if (q.null_ptr) return refuse("piso_conv2d_forward_any: invalid argument (a pointer is NULL)", "piso_conv2d_wgrad_any: invalid argument (a pointer is NULL)");
+  if (ks < 1 || ks > kConvAnyMaxKs || ks % 2 == 0)
+    return refuse("piso_conv2d_forward_any: invalid argument (kernel size: odd, 1 .. 9)", "piso_conv2d_wgrad_any: invalid argument (kernel size: odd, 1 .. 9)");
+  if (cin < 1 || cin > kConvAnyMaxChannels || cout < 1 || cout > kConvAnyMaxChannels)
+    return refuse("piso_conv2d_forward_any: invalid argument (channels: 1 .. 256 in, 1 .. 256 out)", "piso_conv2d_wgrad_any: invalid argument (channels: 1 .. 256 in, 1 .. 256 out)");
+  if (q.H < 1 || q.W < 1 || q.pad < 0 || q.pad_x < 0 || p.g.Ho < 1 || p.g.Wo < 1)
+    return refuse("piso_conv2d_forward_any: invalid argument (the output needs at least one row and one column: H + 2 pad_y - ks + 1 >= 1, W + 2 pad_x - ks + 1 >= 1)",
+                  "piso_conv2d_wgrad_any: invalid argument (the output needs at least one row and one column: H + 2 pad_y - ks + 1 >= 1, W + 2 pad_x - ks + 1 >= 1)");
+  if (!fwd && q.workspace_bytes < conv_wgrad_any_workspace_bytes(ks, cin, cout, p.g.Ho))
+    return refuse("", "piso_conv2d_wgrad_any: invalid argument (workspace_bytes is below piso_conv2d_wgrad_any_workspace_bytes(ks, cin, cout, Ho))");
+  if ((q.wrap_y && q.pad != ks / 2) || (q.wrap_x && q.pad_x != ks / 2))
+    return refuse("piso_conv2d_forward_any: invalid argument (a wrapped axis must have pad == ks / 2: it keeps its extent, and the adjoint is again such a convolution)",
+                  "piso_conv2d_wgrad_any: invalid argument (a wrapped axis must have pad == ks / 2: it keeps its extent, and the adjoint is again such a convolution)");
+  if ((q.wrap_y && q.H < q.pad) || (q.wrap_x && q.W < q.pad_x))
+    return refuse("piso_conv2d_forward_any: invalid argument (a wrapped axis must have an extent >= its pad: an index wraps at most once)",
+                  "piso_conv2d_wgrad_any: invalid argument (a wrapped axis must have an extent >= its pad: an index wraps at most once)");
+  p.entry = q.entry; p.KS = ks; p.block = kConvBlock;
+  p.groups = conv_any_groups(cout); p.NT = conv_any_nt(cout);
+  if (fwd) {
+    p.C = round_up(cin, 4);
+    p.family = CF_FWD_ANY;
+    p.leaky = q.leaky != 0;
+    p.grid_x = ceil_div(ceil_div(p.g.Wo, 64) * p.g.Ho, kConvBlock / 64);
+    p.grid_y = p.groups;
+    return p;
+  }
+  p.C = ceil_div(cin, 16);
+  p.IPW = 1; p.family = CF_WG_ANY;
+  p.item_groups = ceil_div(ks * ks * p.C, kConvBlock / 64);
+  p.grid_y = p.item_groups * p.groups;
+  p.rows_per_block = conv_any_rows_per_block(p.g.Ho);
+  p.grid_x = p.nblocks = conv_any_nblocks(p.g.Ho);
+  // (the 4-wide reducer needs `dw` and `workspace` 16-byte aligned; the scalar one adds the same bands in the same order: no alignment rule)
+  p.reducer = q.result_off16 ? 1 : conv_wg_reducer(cout);
+  const int n = ks * ks * cin * cout;
+  p.reduce_grid = p.reducer == 4 ? ceil_div(n / 4, 64) : ceil_div(n, 64);
+  return p;
+}
+
 inline ConvPlan conv_plan(const ConvQuery& q) {
+  if (q.any) return conv_plan_any(q);
   ConvPlan p{};
   const auto refuse = [&p](const char* msg) { p.status = PISO_ERR_INVALID_ARG; p.msg = msg; return p; };
   p.g = conv_geom(q.H, q.W, q.cin, q.cout, q.ks, q.pad);
@@ -176,6 +250,14 @@ inline ConvPlan conv_plan(const ConvQuery& q) {
   const int n = ks * ks * cin * cout;                        // the reducers: 64 weights (scalar) or 64 x 4 (4-wide) per workgroup
   p.reduce_grid = p.reducer == 4 ? ceil_div(n / 4, 64) : ceil_div(n, 64);
   return p;
+}
+
+// piso_conv2d_instantiated: do the fixed tables serve (entry, ks, cin, cout)?  The answer of conv_plan itself, for a call of the old entry that
+// nothing else could refuse: the smallest image, aligned pointers, enough workspace
+inline int conv_instantiated(int entry, int ks, int cin, int cout) {
+  if ((entry != CE_FORWARD && entry != CE_WGRAD) || ks < 1 || cin < 1 || cout < 1 || cin > 64 || cout > 64) return 0;
+  const ConvQuery q{entry, ks, ks, cin, cout, ks, 0, 0, -1, false, false, false, conv_wgrad_workspace_bytes(ks, cin, cout)};
+  return conv_plan(q).status == PISO_OK ? 1 : 0;
 }
 
 }  // namespace piso

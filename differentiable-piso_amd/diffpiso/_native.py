@@ -163,6 +163,16 @@ lib.piso_conv2d_forward_ex.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i
 lib.piso_conv2d_forward_ex.restype = _i
 lib.piso_conv2d_wgrad_ex.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]
 lib.piso_conv2d_wgrad_ex.restype = _i
+lib.piso_conv2d_weight_elems_any.argtypes = [_i, _i, _i]
+lib.piso_conv2d_weight_elems_any.restype = _sz
+lib.piso_conv2d_wgrad_any_workspace_bytes.argtypes = [_i, _i, _i, _i]
+lib.piso_conv2d_wgrad_any_workspace_bytes.restype = _sz
+lib.piso_conv2d_instantiated.argtypes = [_i, _i, _i, _i]
+lib.piso_conv2d_instantiated.restype = _i
+lib.piso_conv2d_forward_any.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]
+lib.piso_conv2d_forward_any.restype = _i
+lib.piso_conv2d_wgrad_any.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]
+lib.piso_conv2d_wgrad_any.restype = _i
 lib.piso_conv_last_geometry.argtypes = [_ip, _i]
 lib.piso_conv_last_geometry.restype = _i
 lib.piso_leaky_relu_backward.argtypes = [_vp, _vp, _vp, _sz, _vp]
@@ -328,9 +338,15 @@ CONV_DISPATCH_FIELDS = ("entry", "KS", "C", "NT", "IPW", "family", "leaky", "gri
 
 
 def conv_last_dispatch():
-    """Which kernel instance this thread's last piso_conv2d_forward / piso_conv2d_wgrad ran (include/piso_hip.h: piso_conv_last_dispatch),
-    as a dict; {} if the thread has not run a convolution."""
+    """Which kernel instance this thread's last piso_conv2d_forward / piso_conv2d_wgrad (or their *_ex / *_any forms) ran (include/piso_hip.h:
+    piso_conv_last_dispatch), as a dict; {} if the thread has not run a convolution."""
     return _last_dispatch(lib.piso_conv_last_dispatch, "piso_conv_last_dispatch", CONV_DISPATCH_FIELDS)
+
+
+def conv2d_instantiated(entry, ks, cin, cout):
+    """Do the fixed instance tables serve (entry 1 forward | 2 weight gradient, ks, cin, cout)?  (include/piso_hip.h: piso_conv2d_instantiated;
+    pure host code.)  False: the shape runs the run-time-shaped family of the *_any entries."""
+    return bool(lib.piso_conv2d_instantiated(int(entry), int(ks), int(cin), int(cout)))
 
 
 CONV_GEOMETRY_FIELDS = ("pad_y", "pad_x", "wrap_y", "wrap_x")

@@ -4,8 +4,10 @@ Mirror of diffpiso/networks.py (fullyconv_network / initialise_fullyconv_network
 diffpiso/combined_training_integrated.py:399-411, 443-454: network input = cell-centred velocity (+ central pressure gradient),
 network output (2 channels at cell centres) resampled to the faces as the forcing term of piso_step.
 On the GPU the convolutions run on hand-written MFMA kernels (csrc/conv.hip: exact fp32 v_mfma_f32_16x16x4_f32, NHWC, fused
-leaky ReLU, forward / input gradient / weight gradient) behind `conv2d_leaky`: a device tensor the kernels cannot serve raises
-- nothing on the GPU ever goes to another convolution library.  HOST tensors (the CPU tests of the network's shape logic, the
+leaky ReLU, forward / input gradient / weight gradient) behind `conv2d_leaky`: the tuned, fixed instances for the shapes of the
+reference's network, the run-time-shaped family of csrc/conv_any.hip for every other odd kernel size up to 9 and channel counts up
+to 256 (`FullyConvNetwork(layers=...)`).  A device tensor the kernels cannot serve raises - nothing on the GPU ever goes to another
+convolution library.  HOST tensors (the CPU tests of the network's shape logic, the
 oracle chain of the GPU tests, the offline fixture generator) go through torch's CPU conv2d.
 The field-algebra pieces (at_centers, gradient, centre -> face resampling) are pinned by tests/golden (PhiFlow numpy backend).
 """
@@ -33,8 +35,31 @@ def _laid_out(w_hwio):
     return out.view(k, k, cin // 16, 4, 4, cop).permute(0, 1, 2, 3, 5, 4).contiguous()
 
 
+def _laid_out_any(w_hwio):
+    """HWIO weights -> the operand layout of piso_conv2d_forward_any (include/piso_hip.h): [k][k][CINP4][COUTP], zero padded."""
+    k, _, cin, cout = w_hwio.shape
+    out = torch.zeros((k, k, -(-cin // 4) * 4, -(-cout // 16) * 16), dtype=torch.float32, device=w_hwio.device)
+    out[:, :, :cin, :cout] = w_hwio
+    return out
+
+
+_ROUTES = {}
+
+
+def _routes(k, cin, cout):
+    """(forward, input gradient, weight gradient) of a layer: True where the fixed instance tables serve the pass (piso_conv2d_instantiated: the
+    call is then exactly the one made before the run-time-shaped family existed), False where it goes through the *_any entries."""
+    key = (int(k), int(cin), int(cout))
+    hit = _ROUTES.get(key)
+    if hit is None:
+        from . import _native as N
+        inst = N.lib.piso_conv2d_instantiated
+        hit = _ROUTES[key] = (bool(inst(1, *key)), bool(inst(1, key[0], key[2], key[1])), bool(inst(2, *key)))
+    return hit
+
+
 def _cached_layouts(w_oihw):
-    """(forward layout, input-gradient layout) of a weight tensor, recomputed only when the parameter changes (an unrolled
+    """(forward layout, input-gradient layout) of a weight tensor - each in the layout of the entry its pass takes (_routes) -, recomputed only when the parameter changes (an unrolled
     training iteration evaluates the network 2 x step_count times with the same weights).  The layouts live ON the tensor
     object (attribute `_piso_layouts`): they die with it, and another tensor that later reuses its id() or its storage can never
     see them; `_version` / data_ptr / shape still invalidate them after in-place updates, `.data` swaps and checkpoint loads."""
@@ -42,7 +67,10 @@ def _cached_layouts(w_oihw):
     hit = getattr(w_oihw, "_piso_layouts", None)
     if hit is None or hit[0] != key:
         wd = w_oihw.detach()
-        hit = (key, _laid_out(wd.permute(2, 3, 1, 0)), _laid_out(wd.flip(2, 3).permute(2, 3, 0, 1)))
+        cout, cin, k, _ = wd.shape
+        fwd_fixed, dgrad_fixed, _ = _routes(k, cin, cout)
+        hit = (key, (_laid_out if fwd_fixed else _laid_out_any)(wd.permute(2, 3, 1, 0)),
+               (_laid_out if dgrad_fixed else _laid_out_any)(wd.flip(2, 3).permute(2, 3, 0, 1)))
         w_oihw._piso_layouts = hit
     return hit[1], hit[2]
 
@@ -86,7 +114,11 @@ class _Conv2dLeaky(torch.autograd.Function):
         pad_y, pad_x = (pad, pad) if geom is None else geom[:2]
         Ho, Wo = H + 2 * pad_y - k + 1, W + 2 * pad_x - k + 1
         out = torch.empty((1, Ho, Wo, cout), dtype=torch.float32, device=x.device)
-        if geom is None:
+        if not _routes(k, cin, cout)[0]:
+            gy, gx, wy, wx = (pad, pad, 0, 0) if geom is None else geom
+            N.check(N.lib.piso_conv2d_forward_any(N.ptr(x), N.ptr(wl), N.ptr(out), H, W, cin, cout, k, gy, gx, wy, wx, int(leaky), N.stream_ptr()),
+                    "piso_conv2d_forward_any")
+        elif geom is None:
             N.check(N.lib.piso_conv2d_forward(N.ptr(x), N.ptr(wl), N.ptr(out), H, W, cin, cout, k, pad, int(leaky), N.stream_ptr()),
                     "piso_conv2d_forward")
         else:
@@ -114,20 +146,28 @@ class _Conv2dLeaky(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             # dx = conv(g', Wd), Wd[ky][kx][co][ci] = W[k-1-ky][k-1-kx][ci][co], zero padding k - 1 - pad
             gp, cop = g, cout
-            if cout > 4 and cout % 16 != 0:
-                raise N.PisoNativeError("conv2d input gradient: output channels must be <= 4 or a multiple of 16")
             _, wd = _cached_layouts(w_oihw)
             dx = torch.empty_like(x)
-            if geom is None:
+            if not _routes(k, cin, cout)[1]:
+                gy, gx, wy, wx = (pad, pad, 0, 0) if geom is None else geom
+                N.check(N.lib.piso_conv2d_forward_any(N.ptr(gp), N.ptr(wd), N.ptr(dx), Ho, Wo, cop, cin, k, k - 1 - gy, k - 1 - gx, wy, wx, 0, N.stream_ptr()),
+                        "piso_conv2d_forward_any (input gradient)")
+            elif geom is None:
                 N.check(N.lib.piso_conv2d_forward(N.ptr(gp), N.ptr(wd), N.ptr(dx), Ho, Wo, cop, cin, k, k - 1 - pad, 0, N.stream_ptr()),
                         "piso_conv2d_forward (input gradient)")
             else:                                            # (a wrapped axis: pad = k // 2 = k - 1 - pad and Ho = H - the adjoint wraps the same way)
                 N.check(N.lib.piso_conv2d_forward_ex(N.ptr(gp), N.ptr(wd), N.ptr(dx), Ho, Wo, cop, cin, k, k - 1 - geom[0], k - 1 - geom[1], geom[2], geom[3], 0,
                                                      N.stream_ptr()), "piso_conv2d_forward_ex (input gradient)")
         if ctx.needs_input_grad[1]:
-            ws = N.workspace(N.lib.piso_conv2d_wgrad_workspace_bytes(k, cin, cout), x.device, "conv_wgrad")
+            fixed = _routes(k, cin, cout)[2]
+            ws = N.workspace(N.lib.piso_conv2d_wgrad_workspace_bytes(k, cin, cout) if fixed else N.lib.piso_conv2d_wgrad_any_workspace_bytes(k, cin, cout, Ho),
+                             x.device, "conv_wgrad")
             dw_hwio = torch.empty((k, k, cin, cout), dtype=torch.float32, device=x.device)
-            if geom is None:
+            if not fixed:
+                gy, gx, wy, wx = (pad, pad, 0, 0) if geom is None else geom
+                N.check(N.lib.piso_conv2d_wgrad_any(N.ptr(x), N.ptr(g), N.ptr(dw_hwio), H, W, cin, cout, k, gy, gx, wy, wx, N.ptr(ws),
+                                                    C.c_size_t(ws.numel()), N.stream_ptr()), "piso_conv2d_wgrad_any")
+            elif geom is None:
                 N.check(N.lib.piso_conv2d_wgrad(N.ptr(x), N.ptr(g), N.ptr(dw_hwio), H, W, cin, cout, k, pad, N.ptr(ws),
                                                 C.c_size_t(ws.numel()), N.stream_ptr()), "piso_conv2d_wgrad")
             else:
@@ -150,8 +190,15 @@ def conv2d_leaky(x_nhwc, w_oihw, pad, leaky, wrap=(False, False)):
     if x_nhwc.is_cuda or w_oihw.is_cuda:
         if not (x_nhwc.is_cuda and w_oihw.is_cuda and x_nhwc.dtype == torch.float32 and w_oihw.dtype == torch.float32 and x_nhwc.shape[0] == 1):
             from ._native import PisoNativeError
-            raise PisoNativeError("conv2d_leaky: the MFMA convolution kernels take float32 NHWC device tensors of batch 1 (got %s %s, weights %s on %s); "
+            raise PisoNativeError("conv2d_leaky: the MFMA convolution kernels take float32 NHWC device tensors of batch 1, odd kernel sizes 1 .. 9 and 1 .. 256 "
+                                  "channels (got %s %s, weights %s on %s); "
                                   "there is no other convolution path on the GPU" % (tuple(x_nhwc.shape), x_nhwc.dtype, w_oihw.dtype, w_oihw.device))
+        k, cin, cout = w_oihw.shape[-1], w_oihw.shape[1], w_oihw.shape[0]
+        if w_oihw.shape[-2] != k or k % 2 == 0 or k > 9 or not (1 <= cin <= 256 and 1 <= cout <= 256) or x_nhwc.shape[-1] != cin:
+            from ._native import PisoNativeError
+            raise PisoNativeError("conv2d_leaky: the MFMA convolution kernels take square kernels of odd size 1 .. 9 and 1 .. 256 channels on either side, the input's "
+                                  "channels equal to the weights' (got weights %s, input %s); there is no other convolution path on the GPU"
+                                  % (tuple(w_oihw.shape), tuple(x_nhwc.shape)))
         if not general:
             return _Conv2dLeaky.apply(x_nhwc, w_oihw, int(pad), bool(leaky))
         return _Conv2dLeaky.apply(x_nhwc, w_oihw, pad_y, bool(leaky), (pad_y, pad_x, int(wrap_y), int(wrap_x)))
@@ -177,13 +224,31 @@ _KERNELS = [(7, 4, 16), (5, 16, 16), (5, 16, 32), (3, 32, 64), (3, 64, 64), (1, 
 class FullyConvNetwork(torch.nn.Module):
     """7-layer fully convolutional network 4 -> 16 -> 16 -> 32 -> 64 -> 64 -> 64 -> 2, kernels 7,5,5,3,3,1,1, leaky ReLU (0.2)
     after all but the last layer (networks.py:3-57).  Tensors are NHWC like the reference's.
+    layers: a list of (k, cin, cout) - another architecture: odd kernel sizes up to 9, up to 256 channels, each layer's cin the cout before it;
+    None: the reference's seven layers.  `in_channels` overrides the first cin; the leaky ReLU follows all but the last layer;
+    `reduced_buffer_width` is the sum of k // 2 over the layers.  On the GPU a layer shape outside the reference's runs the run-time-shaped
+    kernels (csrc/conv_any.hip), the reference's shapes their tuned instances as ever.
     wrap = (wrap_y, wrap_x): the periodic axes of the domain.  A wrapped axis keeps its extent in every layer (pad k // 2, wrap-around),
     whatever `padding` says: `padding="VALID"` shrinks - and `restore_shape` pads back - only the other axis.  A non-zero `buffer_width`
     on a wrapped axis is refused: a cropped axis has no seam.  A periodic simulation wants the network and its coupling
     (centered_to_staggered / make_forcing_fn) wrapped on the same axes."""
 
-    def __init__(self, buffer_width=None, padding="SAME", restore_shape=False, in_channels=4, seed=None, initialiser=None, wrap=(False, False)):
+    def __init__(self, buffer_width=None, padding="SAME", restore_shape=False, in_channels=None, seed=None, initialiser=None, wrap=(False, False),
+                 layers=None):
         super().__init__()
+        if layers is None:
+            layers, in_channels = _KERNELS, 4 if in_channels is None else in_channels
+        layers = [tuple(int(v) for v in layer) for layer in layers]
+        if not layers or any(len(layer) != 3 for layer in layers):
+            raise ValueError("FullyConvNetwork: layers is a non-empty list of (k, cin, cout)")
+        if in_channels is not None:
+            layers[0] = (layers[0][0], int(in_channels), layers[0][2])
+        for i, (k, cin, cout) in enumerate(layers):
+            if k < 1 or k > 9 or k % 2 == 0 or not (1 <= cin <= 256 and 1 <= cout <= 256):
+                raise ValueError("FullyConvNetwork: layer %d = %s: odd kernel sizes 1 .. 9 and 1 .. 256 channels" % (i, (k, cin, cout)))
+            if i > 0 and cin != layers[i - 1][2]:
+                raise ValueError("FullyConvNetwork: layer %d takes %d channels, layer %d gives %d" % (i, cin, i - 1, layers[i - 1][2]))
+        self.layers = layers
         self.wrap = _wrap2(wrap)
         if buffer_width is not None:
             for axis, name in ((0, "y"), (1, "x")):
@@ -192,8 +257,7 @@ class FullyConvNetwork(torch.nn.Module):
                                      % (list(buffer_width[axis]), name))
         gen = torch.Generator().manual_seed(seed) if seed is not None else None
         self.weights = torch.nn.ParameterList()
-        for i, (k, cin, cout) in enumerate(_KERNELS):
-            cin = in_channels if i == 0 else cin
+        for k, cin, cout in layers:
             # tf.glorot_normal_initializer (networks.py:57) = VarianceScaling(1.0, "fan_avg", "truncated_normal"): a normal distribution
             # truncated at two standard deviations whose standard deviation AFTER the truncation is sqrt(2 / (fan_in + fan_out)) -
             # TensorFlow samples with sigma / 0.87962566103423978 for that
@@ -210,7 +274,7 @@ class FullyConvNetwork(torch.nn.Module):
         self.buffer_width = buffer_width
         self.padding = padding
         self.restore_shape = restore_shape
-        self.reduced_buffer_width = int(np.sum([k // 2 for k in (7, 5, 5, 3, 3)]))     # networks.py:72
+        self.reduced_buffer_width = int(np.sum([k // 2 for k, _, _ in layers]))         # networks.py:72 (the reference's layers: 3 + 2 + 2 + 1 + 1)
 
     def forward(self, fields):
         if isinstance(fields, StaggeredGrid):
@@ -239,9 +303,9 @@ class FullyConvNetwork(torch.nn.Module):
         return out
 
 
-def initialise_fullyconv_network(buffer_width, padding="SAME", restore_shape=False, initialiser=None, seed=None, wrap=(False, False)):
-    """networks.py:59-77 -> (callable, weights, reduced_buffer_width).  wrap: the periodic axes (FullyConvNetwork)."""
-    net = FullyConvNetwork(buffer_width, padding, restore_shape, seed=seed, initialiser=initialiser, wrap=wrap)
+def initialise_fullyconv_network(buffer_width, padding="SAME", restore_shape=False, initialiser=None, seed=None, wrap=(False, False), layers=None):
+    """networks.py:59-77 -> (callable, weights, reduced_buffer_width).  wrap: the periodic axes; layers: a list of (k, cin, cout) (FullyConvNetwork)."""
+    net = FullyConvNetwork(buffer_width, padding, restore_shape, seed=seed, initialiser=initialiser, wrap=wrap, layers=layers)
     rbw = net.reduced_buffer_width
     if buffer_width is not None:
         rbw = [[i + rbw for i in j] for j in buffer_width]

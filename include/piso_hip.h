@@ -500,7 +500,7 @@ int piso_mg_last_dispatch(int* out, int capacity);
  * Convolutions of the CNN turbulence closure on the matrix cores (csrc/conv.hip; exact fp32 MFMA).  Replaces the
  * tf.nn.conv2d / tf.nn.leaky_relu calls of diffpiso/networks.py:3-57 (NHWC activations, batch 1, stride 1, no bias, kernel
  * sizes and channel counts of the closure: 7x7 4->16, 5x5 16->16, 5x5 16->32, 3x3 32->64, 3x3 64->64, 1x1 64->64, 1x1 64->2 and
- * the transposed shapes of the input-gradient pass).
+ * the transposed shapes of the input-gradient pass; every other odd kernel size up to 9 and channel count up to 256: the *_any entries below).
  *   in [H][W][cin], out [Ho][Wo][cout] with Ho = H + 2 pad - ks + 1; leaky_out != 0: leaky ReLU (slope 0.2) on the output.
  *   w_laid_out: the HWIO weights in the kernel's operand layout, zero filled beyond the true channel counts
  *   (piso_conv2d_weight_elems floats, COUTP = round_up(cout, 16)):
@@ -567,6 +567,39 @@ int piso_conv2d_wgrad_ex(const float* in, const float* grad_out, float* dw, int 
  * pad_x, wrap_y (0 | 1), wrap_x (0 | 1); returns the number of fields: 4 after piso_conv2d_forward_ex / piso_conv2d_wgrad_ex, 0 after
  * piso_conv2d_forward / piso_conv2d_wgrad (their one `pad` is an argument of the call) or before any convolution. */
 int piso_conv_last_geometry(int* out, int capacity);
+
+/* ANY channel counts and odd kernel sizes: a second kernel family (csrc/conv_any.hip) whose kernel size and channel counts are run-time values, for
+ * the shapes the tuned instances above do not hold (they refuse 5 .. 15 input channels, more than 64 channels, 9 x 9, 5 x 5 on 64 -> 64, ...).
+ * Definition, geometry (pad per axis, wrap per axis), the two rules of a wrapped axis and the treatment of non-finite values: those of the *_ex
+ * entries above.  Accepted: ks odd, 1 .. 9;  1 <= cin, cout <= 256;  Ho, Wo >= 1.  NO alignment rule: every access of the main kernels is 4 bytes
+ * (the 4-wide reducer runs only where cout % 4 == 0 AND `dw` and `workspace` are 16-byte aligned; the scalar one adds the same bands in the same
+ * order).  Everything else is PISO_ERR_INVALID_ARG before any launch, with a message that starts with the entry's name.
+ * These entries ALWAYS run the new family, also for a shape that has a fixed instance (that holds one family to the other in the tests); which
+ * shapes the fixed tables serve: piso_conv2d_instantiated(entry, ks, cin, cout) - entry 1 forward, 2 weight gradient; 1 where piso_conv2d_forward /
+ * piso_conv2d_wgrad have an instance for the shape, 0 otherwise.  Pure host code: it asks the plan the old entries ask.
+ *   w_laid_out of piso_conv2d_forward_any (piso_conv2d_weight_elems_any floats): [ks][ks][CINP4][COUTP], CINP4 = round_up(cin, 4), COUTP =
+ *     round_up(cout, 16):  element ((ky ks + kx) CINP4 + ci) COUTP + co = W[ky][kx][ci][co], zero where ci >= cin or co >= cout
+ *     (the cin <= 4 layout above with more channel rows).  K order of every output's sum: tap row, tap column, input channel.
+ *   workspace of piso_conv2d_wgrad_any: piso_conv2d_wgrad_any_workspace_bytes(ks, cin, cout, Ho) bytes, Ho = H + 2 pad_y - ks + 1: at most 64 row
+ *     bands of partials [band][ks][ks][round_up(cin, 16)][COUTP], added in a fixed order (deterministic, no atomics).
+ * piso_conv_last_dispatch reports these calls with the same 15 fields: entry 1 / 2, and
+ *    2 C               forward: CINP4;  wgrad: tiles of 16 input channels, ceil(cin / 16)
+ *    3 NT              tiles of 16 output channels PER GROUP: the ceil(cout / 16) tiles are split evenly over groups = ceil(tiles / 4) groups
+ *    4 IPW             wgrad: 1;  forward: 0
+ *    5 family          7 conv_forward_any_kernel<NT, leaky>, 8 conv_wgrad_any_kernel<NT>
+ *    8 grid_y          forward: the groups;  wgrad: ceil(ks ks C / 4) x groups - workgroups of four waves over the work items (tap, tile of 16
+ *                      input channels), one item per wave, times the groups
+ *   10 rows_per_block  wgrad: ceil(Ho / 64)
+ *   11 nblocks         wgrad: ceil(Ho / rows_per_block) <= 64
+ *   12 reducer         wgrad: 4 if cout % 4 == 0 and `dw`, `workspace` are 16-byte aligned, else 1
+ * the other fields as above.  piso_conv_last_geometry: always 4 fields.  A refused call leaves both records untouched. */
+size_t piso_conv2d_weight_elems_any(int ks, int cin, int cout);
+size_t piso_conv2d_wgrad_any_workspace_bytes(int ks, int cin, int cout, int Ho);
+int piso_conv2d_instantiated(int entry, int ks, int cin, int cout);
+int piso_conv2d_forward_any(const float* in, const float* w_laid_out, float* out, int H, int W, int cin, int cout, int ks, int pad_y, int pad_x,
+                            int wrap_y, int wrap_x, int leaky_out, piso_stream_t stream);
+int piso_conv2d_wgrad_any(const float* in, const float* grad_out, float* dw, int H, int W, int cin, int cout, int ks, int pad_y, int pad_x,
+                          int wrap_y, int wrap_x, void* workspace, size_t workspace_bytes, piso_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Slab-decomposed pressure CG (no counterpart in the reference, which is single-GPU).
