@@ -212,6 +212,16 @@ for _n in ("piso_laplace_matrix_f64", "piso_laplace_matrix_f32", "piso_pad_veloc
            "piso_divergence", "piso_divergence_adjoint", "piso_h_contribution", "piso_h_contribution_adjoint"):
     getattr(lib, _n + "_slab").argtypes = getattr(lib, _n).argtypes + [_sp]
     getattr(lib, _n + "_slab").restype = _i
+lib.piso_closure_input.argtypes = [_vp, _vp, _vp, _i, _i, _i, _ip, C.c_double, _vp]
+lib.piso_closure_input_adjoint.argtypes = [_vp, _vp, _vp, _i, _i, _i, _ip, C.c_double, _vp]
+lib.piso_closure_force.argtypes = [_vp, _vp, _i, _i, _i, _i, _vp]
+lib.piso_closure_force_adjoint.argtypes = [_vp, _vp, _i, _i, _i, _i, _vp]
+for _n in ("piso_closure_input", "piso_closure_input_adjoint", "piso_closure_force", "piso_closure_force_adjoint"):
+    getattr(lib, _n).restype = _i
+    getattr(lib, _n + "_slab").argtypes = getattr(lib, _n).argtypes + [_sp, _i, _i]        # (slab, ext_lo, ext_hi)
+    getattr(lib, _n + "_slab").restype = _i
+lib.piso_closure_halo_add.argtypes = [_vp, _vp, _sz, _vp]
+lib.piso_closure_halo_add.restype = _i
 lib.piso_csr_matvec_f32_slab.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sp]
 lib.piso_csr_matvec_f32_slab.restype = _i
 lib.piso_bicgstab_slab_workspace_bytes.argtypes = [_i, _i, _i, _sp]

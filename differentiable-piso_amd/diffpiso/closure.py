@@ -276,7 +276,9 @@ class FullyConvNetwork(torch.nn.Module):
         self.restore_shape = restore_shape
         self.reduced_buffer_width = int(np.sum([k // 2 for k, _, _ in layers]))         # networks.py:72 (the reference's layers: 3 + 2 + 2 + 1 + 1)
 
-    def forward(self, fields):
+    def forward(self, fields, wrap=None):
+        """wrap: None - the network's own periodic axes (self.wrap); (wrap_y, wrap_x) - this call's instead.  The slab-decomposed closure
+        (sharding.make_slab_forcing_fn) runs a y-wrapped network as wrap=(False, wrap_x) on rows that carry the ring halo."""
         if isinstance(fields, StaggeredGrid):
             fields = fields.at_centers().data
         bw = self.buffer_width
@@ -286,13 +288,14 @@ class FullyConvNetwork(torch.nn.Module):
         target = fields.shape
         x = fields
         same = self.padding == "SAME"
-        wrap_y, wrap_x = self.wrap
+        call_wrap = self.wrap if wrap is None else _wrap2(wrap)
+        wrap_y, wrap_x = call_wrap
         for i, w in enumerate(self.weights):
             k = w.shape[-1]
             if not (wrap_y or wrap_x):
                 x = conv2d_leaky(x, w, k // 2 if same else 0, leaky=i < len(self.weights) - 1)
             else:
-                x = conv2d_leaky(x, w, (k // 2 if same or wrap_y else 0, k // 2 if same or wrap_x else 0), leaky=i < len(self.weights) - 1, wrap=self.wrap)
+                x = conv2d_leaky(x, w, (k // 2 if same or wrap_y else 0, k // 2 if same or wrap_x else 0), leaky=i < len(self.weights) - 1, wrap=call_wrap)
         out = x
         if not same and bw is not None and self.restore_shape:
             pn = self.reduced_buffer_width
@@ -352,8 +355,18 @@ def network_input(velocity, pressure, pressure_included=True):
 def make_forcing_fn(network, pressure_included=True, wrapper=None, wrap=None):
     """forcing_fn for run_piso_steps: the residual force of the closure at every unrolled step (:443-454).
     wrap = (wrap_y, wrap_x): the centre -> face resampling averages across the seam of a periodic axis (centered_to_staggered); None:
-    edge values replicated.  A periodic simulation wants the network (FullyConvNetwork(wrap=...)) and this coupling wrapped on the same axes."""
+    edge values replicated.  A periodic simulation wants the network (FullyConvNetwork(wrap=...)) and this coupling wrapped on the same axes.
+    Slab fields (a slab-decomposed simulation, sharding.py) take the sharded closure: sharding.make_slab_forcing_fn, built on first use;
+    there `wrapper` is called as wrapper(network, nn_in) on the rank's extended rows."""
+    slab = {}
+
     def forcing(i, velocity, pressure):
+        if hasattr(velocity, "rewrap"):
+            sh = velocity.sharding
+            if slab.get("sharding") is not sh:
+                from .sharding import make_slab_forcing_fn
+                slab["sharding"], slab["fn"] = sh, make_slab_forcing_fn(network, sh, pressure_included, wrap=wrap, wrapper=wrapper)
+            return slab["fn"](i, velocity, pressure)
         nn_in = network_input(velocity, pressure, pressure_included)
         nn_out = wrapper(network, nn_in) if wrapper is not None else network(nn_in)
         return centered_to_staggered(nn_out, _wrap2(wrap))

@@ -20,6 +20,9 @@ so a halo exchange never needs an adjoint of its own.
 Fields of a sharded simulation are `SlabStaggered` / `SlabCentered` (this module): what `piso_step` / `unroll_piso_steps` take and
 return instead of StaggeredGrid / CenteredGrid when `simulation_physics.sharding` is set.  `StepSharding.scatter_*` cut a whole-grid
 array (host or device) into the rank's stored rows, `owned_*` pick the rows a rank owns out of a stored array.
+
+The CNN closure runs on the slabs as well (`make_slab_forcing_fn`, at the end of this module): its NHWC buffers hold the rank's rows plus
+E = R + 1 halo rows either side (`ClosureHalo`; R = the network's reduced_buffer_width), filled by one wide exchange per step and direction.
 """
 import ctypes as C
 import zlib
@@ -96,6 +99,7 @@ class StepSharding(object):
         self._sim_cache = {}
         self._scatter_cache = {}
         self._patterns = {}                          # (per_x, per_y) -> (pattern, msgs_csr, nnz)
+        self._closure_halos = {}                     # (R, channels, periodic_y) -> ClosureHalo
         self.periodic_xy = (False, False)            # (x, y) periodicity of the velocity: set by the step (the CSR numbering needs it)
         comm.sharded = True
         comm.step_sharding = self                    # the solvers reach the row map through their communicator
@@ -279,6 +283,32 @@ class StepSharding(object):
     def centered_grid(self, data, box, extrapolation):
         return SlabCentered(data, self, box, extrapolation)
 
+    # ------------------------------------------------------------------------------------------------ the CNN closure on slabs
+    def closure_halo(self, R, channels, periodic_y=False):
+        """The wide halo of an NHWC buffer of the closure (ClosureHalo): R = the network's reduced_buffer_width."""
+        key = (int(R), int(channels), bool(periodic_y))
+        hit = self._closure_halos.get(key)
+        if hit is None:
+            hit = self._closure_halos[key] = ClosureHalo(self, *key)
+        return hit
+
+    def allreduce_gradients(self, params):
+        """Sum `.grad` of the parameters over the ranks, in place: a rank's weight gradients of a sharded closure are the part that belongs to
+        its owned outputs.  Through torch.distributed (host tensors for gloo, like mg_solve_slab(gather=True))."""
+        import torch.distributed as dist
+        from .distributed import _comm_device
+        grads = [p.grad for p in params if p.grad is not None]
+        if not grads or self.world < 2:
+            return
+        flat = torch.cat([g.reshape(-1) for g in grads])
+        moved = flat.to(_comm_device(flat.device))
+        dist.all_reduce(moved, op=dist.ReduceOp.SUM)
+        flat = moved.to(flat.device)
+        at = 0
+        for g in grads:
+            g.copy_(flat[at:at + g.numel()].view_as(g))
+            at += g.numel()
+
     def check(self):
         """Raise if a wait on a peer gave up since the last check (agreed over the ranks; synchronises the stream)."""
         N.check(N.lib.piso_comm_check(self.comm.handle, N.stream_ptr()), "piso_comm_check")
@@ -359,3 +389,257 @@ class SlabCentered(object):
 
     def __add__(self, other):
         return self.rewrap(self.data + (other.data if isinstance(other, SlabCentered) else other))
+
+
+# ---------------------------------------------------------------------------------------------------- the CNN closure on slabs
+_PAD_MODE = {"constant": 0, "boundary": 1, "periodic": 2}
+
+
+class ClosureHalo(object):
+    """The wide halo of one NHWC buffer [rows][nx][channels] of the closure on a rank's slab.
+
+    R = the network's reduced_buffer_width (the sum of k // 2 over its layers), E = R + 1: the extra row is the one the centre -> face
+    resampling reads across the cut.  The buffer's EXTENDED ROWS are the whole-grid rows [j0 - lo, j1 + hi): lo / hi = E on a side with a
+    ring neighbour (the seam of a periodic y axis included), 0 on a side that ends at a border of the domain - there the network's own SAME
+    zero padding has to act, layer by layer.  Behind the extended rows the buffer carries 2 E SCRATCH rows: [A: E rows that arrive from the
+    lower neighbour][B: E rows that arrive from the upper neighbour].
+    Three exchanges, each a list of message tables in the 7-int format of piso_comm_exchange, chunked by whole rows so that no message is
+    longer than the communicator's row_capacity (elements):
+      forward   every rank's E edge rows -> its ring neighbours' halo rows
+      reverse   every rank's halo rows (a cotangent's partial sums) -> their owner's scratch rows; `reverse_add` then adds A into the owner's
+                first and B into its last E rows (piso_closure_halo_add)
+      narrow    forward with one row (the adjoint of the network input gathers from one row either side)
+    The exchange is always a ring with messages of full length (what piso_comm_exchange's other users send): where a side has no halo rows
+    the rows that arrive land in the scratch rows and nobody reads them, and what is sent from there is not added by its receiver."""
+
+    def __init__(self, sharding, R, channels, periodic_y=False):
+        sh = self.sharding = sharding
+        self.R, self.E, self.channels, self.periodic_y = int(R), int(R) + 1, int(channels), bool(periodic_y)
+        E = self.E
+        if R < 0 or channels < 1:
+            raise ValueError("closure halo: R >= 0 and at least one channel")
+        if sh.nyl < E:
+            raise ValueError("closure on slabs: a slab needs at least E = R + 1 = %d rows (the network reads R = %d rows beyond a cut and the "
+                             "resampling one more; with fewer a halo would span two neighbours), ny = %d on %d ranks gives %d"
+                             % (E, R, sh.ny, sh.world, sh.nyl))
+        self.lo = E if (sh.rank > 0 or self.periodic_y) else 0
+        self.hi = E if (sh.rank < sh.world - 1 or self.periodic_y) else 0
+        self.rows = sh.nyl + self.lo + self.hi
+        self.L = L = sh.nx * self.channels                     # elements of one row
+        self.numel = (self.rows + 2 * E) * L
+        cap = int(getattr(sh.comm, "row_capacity", 8192))
+        if L > cap:
+            raise ValueError("closure on slabs: one NHWC row (nx %d x %d channels = %d elements) is longer than the communicator's row_capacity "
+                             "(%d): the halo is chunked by whole rows" % (sh.nx, self.channels, L, cap))
+        self.rows_per_message = cap // L
+        self.tables_forward = self._tables(E, False)
+        self.tables_reverse = self._tables(E, True)
+        self.tables_narrow = self._tables(1, False)
+
+    def _tables(self, w, reverse):
+        lo, hi, nyl, rows, E, L = self.lo, self.hi, self.sharding.nyl, self.rows, self.E, self.L
+        a_row, b_row = rows, rows + E                          # scratch A (from the lower neighbour), scratch B (from the upper)
+        if not reverse:
+            first = dict(to_upper=lo + nyl - w, to_lower=lo, from_lower=lo - w if lo else a_row, from_upper=lo + nyl if hi else b_row)
+        else:
+            first = dict(to_upper=lo + nyl if hi else b_row, to_lower=0 if lo else a_row, from_lower=a_row, from_upper=b_row)
+        out = []
+        for a in range(0, w, self.rows_per_message):
+            n = min(w, a + self.rows_per_message) - a
+            flat = []
+            for key in ("to_upper", "to_lower", "from_lower", "from_upper"):
+                flat += _msg([((first[key] + a) * L, n * L)])
+            out.append((C.c_int * 28)(*flat))
+        return out
+
+    # ---- buffers
+    def alloc(self, device, zero=False):
+        return (torch.zeros if zero else torch.empty)(self.numel, dtype=torch.float32, device=device)
+
+    def extended(self, buf):
+        """The extended rows of a buffer as the NHWC tensor the network takes: [1, rows, nx, channels] (a view)."""
+        return buf[:self.rows * self.L].view(1, self.rows, self.sharding.nx, self.channels)
+
+    def _run(self, buf, tables):
+        if buf.numel() != self.numel or buf.dtype != torch.float32:
+            raise N.PisoNativeError("closure halo: the buffer holds %d float32 elements, the exchange needs %d" % (buf.numel(), self.numel))
+        for t in tables:
+            self.sharding._exchange(buf, t)
+        return buf
+
+    def forward(self, buf):
+        return self._run(buf, self.tables_forward)
+
+    def narrow(self, buf):
+        return self._run(buf, self.tables_narrow)
+
+    def reverse_add(self, buf):
+        """Halo rows back to their owners, added into the owners' edge rows.  The halo rows themselves keep their (now stale) partial sums."""
+        self._run(buf, self.tables_reverse)
+        return self.add_received(buf)
+
+    def add_received(self, buf):
+        """The second half of `reverse_add`: scratch A into the first E owned rows, scratch B into the last E (sides with a neighbour)."""
+        lo, hi, nyl, rows, E, L = self.lo, self.hi, self.sharding.nyl, self.rows, self.E, self.L
+        for have, dst_row, src_row in ((lo, lo, rows), (hi, lo + nyl - E, rows + E)):
+            if have:
+                N.check(N.lib.piso_closure_halo_add(N.ptr(buf[dst_row * L:(dst_row + E) * L]), N.ptr(buf[src_row * L:(src_row + E) * L]),
+                                                    C.c_size_t(E * L), N.stream_ptr()), "piso_closure_halo_add")
+        return buf
+
+
+class _SlabCoupling(object):
+    """What the two autograd functions of a sharded closure share: the sharding, the halos of the network's input and output, the pressure's
+    pad modes and 2 dx."""
+
+    def __init__(self, sharding, halo_in, halo_out, pad_modes, two_dx, wrap):
+        self.sh, self.halo_in, self.halo_out, self.wrap = sharding, halo_in, halo_out, wrap
+        self.pad_modes = (C.c_int * 4)(*pad_modes)
+        self.two_dx = C.c_double(float(two_dx))
+
+
+class _SlabClosureInput(torch.autograd.Function):
+    """Stored face rows, stored pressure rows -> the network input on the rank's extended rows (piso_closure_input_slab + the wide halo).
+    Reverse: the cotangent that arrives holds, on every extended row, the part of d nn_in that belongs to THIS rank's owned outputs; the
+    reverse exchange + add completes the owned rows, a one-row halo fill follows, piso_closure_input_adjoint_slab gathers."""
+
+    @staticmethod
+    def forward(ctx, faces, pressure, cp):
+        sh, H = cp.sh, cp.halo_in
+        sh.halo_faces(faces.detach())                          # (centre row j1 - 1 reads face row v[j1]; in place, as the step itself does next)
+        if pressure is not None:
+            sh.halo_cells(pressure.detach())
+        buf = H.alloc(faces.device)
+        N.check(N.lib.piso_closure_input_slab(N.ptr(faces), N.ptr(pressure), N.ptr(buf), sh.nx, sh.ny, H.channels, cp.pad_modes, cp.two_dx,
+                                              N.stream_ptr(), sh.slab_ptr, H.lo, H.hi), "piso_closure_input_slab")
+        H.forward(buf)
+        ctx.cp, ctx.p_shape = cp, None if pressure is None else pressure.shape
+        return H.extended(buf)
+
+    @staticmethod
+    def backward(ctx, g):
+        cp = ctx.cp
+        sh, H = cp.sh, cp.halo_in
+        buf = H.alloc(g.device)
+        H.extended(buf).copy_(g)
+        H.reverse_add(buf)
+        H.narrow(buf)
+        d_faces = torch.zeros(sh.n_faces, dtype=torch.float32, device=g.device)
+        d_p = torch.zeros(sh.n_cells, dtype=torch.float32, device=g.device) if H.channels == 4 else None
+        N.check(N.lib.piso_closure_input_adjoint_slab(N.ptr(buf), N.ptr(d_faces), N.ptr(d_p), sh.nx, sh.ny, H.channels, cp.pad_modes, cp.two_dx,
+                                                      N.stream_ptr(), sh.slab_ptr, H.lo, H.hi), "piso_closure_input_adjoint_slab")
+        return d_faces, None if d_p is None or ctx.p_shape is None else d_p.view(ctx.p_shape), None
+
+
+class _SlabClosureForce(torch.autograd.Function):
+    """The network output on the extended rows -> the forcing on the rank's owned face rows (piso_closure_force_slab).  Reverse: the
+    cotangent of the faces is halo-filled (halo_faces), the gather-form adjoint then completes d nn_out on the OWNED rows - every other
+    extended row stays exactly zero, so that what the convolution backward makes of it is the part of d nn_in, and of the weight gradients,
+    that belongs to this rank's owned outputs."""
+
+    @staticmethod
+    def forward(ctx, nn_out, cp):
+        sh, H = cp.sh, cp.halo_out
+        nn_out = nn_out.contiguous()
+        if tuple(nn_out.shape) != (1, H.rows, sh.nx, 2):
+            raise ValueError("closure on slabs: the network returned %s for the extended rows %s" % (tuple(nn_out.shape), (1, H.rows, sh.nx, 2)))
+        faces = torch.zeros(sh.n_faces, dtype=torch.float32, device=nn_out.device)
+        N.check(N.lib.piso_closure_force_slab(N.ptr(nn_out), N.ptr(faces), sh.nx, sh.ny, int(cp.wrap[1]), int(cp.wrap[0]), N.stream_ptr(),
+                                              sh.slab_ptr, H.lo, H.hi), "piso_closure_force_slab")
+        ctx.cp = cp
+        return faces
+
+    @staticmethod
+    def backward(ctx, g):
+        cp = ctx.cp
+        sh, H = cp.sh, cp.halo_out
+        g = sh.halo_faces(g.contiguous().clone())
+        d_out = torch.zeros((1, H.rows, sh.nx, 2), dtype=torch.float32, device=g.device)
+        N.check(N.lib.piso_closure_force_adjoint_slab(N.ptr(g), N.ptr(d_out), sh.nx, sh.ny, int(cp.wrap[1]), int(cp.wrap[0]), N.stream_ptr(),
+                                                      sh.slab_ptr, H.lo, H.hi), "piso_closure_force_adjoint_slab")
+        return d_out, None
+
+
+class _WrappedOnSlabs(object):
+    """The network as a wrapper sees it on slabs: called without `wrap`, it runs with the slab path's (False, wrap_x) - the ring halo is the
+    y wrap."""
+
+    def __init__(self, network, wrap):
+        self.network, self.wrap = network, wrap
+
+    def __call__(self, fields, wrap=None):
+        return self.network(fields, wrap=self.wrap if wrap is None else wrap)
+
+    def __getattr__(self, name):
+        return getattr(self.network, name)
+
+
+def check_slab_network(network):
+    """What a network must be to run on y-slabs; raises ValueError naming the rule.  -> its reduced_buffer_width."""
+    R = getattr(network, "reduced_buffer_width", None)
+    if R is None or isinstance(R, (list, tuple)):
+        raise ValueError("closure on slabs: the network must state its `reduced_buffer_width` (the sum of k // 2 over its layers, an int): it is "
+                         "the width of the halo its receptive field needs")
+    if getattr(network, "padding", "SAME") != "SAME":
+        raise ValueError("closure on slabs: padding must be 'SAME' (got %r): a VALID network shrinks the rows of every slab" % (network.padding,))
+    bw = getattr(network, "buffer_width", None)
+    if bw is not None and any(int(b) != 0 for b in bw[0]):
+        raise ValueError("closure on slabs: the y entries of buffer_width must be 0 (got %s): a crop of the whole grid's first and last rows is not "
+                         "a crop of every slab's; x entries are local and stay allowed" % (list(bw[0]),))
+    return int(R)
+
+
+def make_slab_forcing_fn(network, sharding, pressure_included=True, wrap=None, wrapper=None):
+    """closure.make_forcing_fn for a slab-decomposed simulation: forcing_fn(i, velocity, pressure) takes SlabStaggered / SlabCentered fields
+    and returns the SlabStaggered forcing of the rank's rows.
+      1. piso_closure_input_slab writes the owned rows of the network input, 2. the wide halo exchange (ClosureHalo, E = R + 1 rows) fills
+      the halo rows, 3. the network runs on the extended rows as network(x, wrap=(False, wrap_x)), 4. piso_closure_force_slab reads the
+      owned rows and one row either side of its output.
+    Why 3. is right: a SAME convolution of kernel size k lets the zero padding of an ARTIFICIAL end (a cut) into k // 2 rows per layer.
+    After all layers the wrong values have advanced R = sum k // 2 rows: rows [0, R) and [rows - R, rows) of the output, which are halo rows;
+    row R (the one the resampling reads across the cut) and every owned row saw whole-grid data only - with one wavefront per 64 pixels of
+    an output row and a K loop that does not depend on the image height (csrc/conv.hip) bit for bit what the whole grid computes.  At a
+    border of the domain there is no halo (lo / hi = 0) and the padding is the network's own.
+    Reverse mode runs the same count backwards: d nn_out is non-zero on the owned rows only, so the gradient w.r.t. the output of layer l
+    is non-zero within sum_{m > l} k_m // 2 rows of the owned ones - and the saved activations of layer l are valid within
+    1 + sum_{m > l} k_m // 2 rows: every product of the input and weight gradients pairs a non-zero cotangent with a valid activation
+    (garbage activations are finite - sums of whole-grid data and zeros - and meet exact zeros).  Each rank ends with the part of d nn_in
+    that belongs to its owned outputs, on owned + R rows; the reverse exchange adds the parts across the cuts (one more rounding than on
+    one GPU).  Weight gradients: the part that belongs to the rank's owned outputs - StepSharding.allreduce_gradients sums them.
+    wrap = (wrap_y, wrap_x) of the resampling (None: edges replicated).  wrap_y must equal the network's: on a y-periodic domain the ring
+    halo IS the wrap of both.  wrapper(network, nn_in_ext): the network it is handed runs with (False, wrap_x) unless told otherwise.
+    Refused before any launch: VALID padding, a y buffer_width, a network without reduced_buffer_width, slabs thinner than E rows."""
+    from .closure import _wrap2
+    from .grids import axis_extrapolation
+    R = check_slab_network(network)
+    wrap = _wrap2(wrap)
+    net_wrap = _wrap2(getattr(network, "wrap", None))
+    if net_wrap[0] != wrap[0]:
+        raise ValueError("closure on slabs: the network (wrap_y %s) and the centre -> face resampling (wrap_y %s) must wrap y together: the ring "
+                         "halo is the wrap of both" % (net_wrap[0], wrap[0]))
+    channels = 4 if pressure_included else 2
+    halo_in = sharding.closure_halo(R, channels, wrap[0])
+    halo_out = sharding.closure_halo(R, 2, wrap[0])
+    slab_wrap = (False, net_wrap[1])
+
+    def forcing(i, velocity, pressure):
+        if not (hasattr(velocity, "rewrap") and velocity.sharding is sharding):
+            raise ValueError("closure on slabs: the forcing function of a sharded closure takes the SlabStaggered / SlabCentered fields of its sharding")
+        modes, two_dx = (1, 1, 1, 1), 1.0
+        if pressure_included:
+            assert np.allclose(pressure.dx, np.mean(pressure.dx)), "Only cubic cells supported."
+            ext = axis_extrapolation(pressure.extrapolation, 2)
+            modes = []
+            for axis in (1, 0):                                # (x lower, x upper, y lower, y upper)
+                e = ext[axis]
+                lo_mode, hi_mode = (e, e) if isinstance(e, str) else e
+                modes += [_PAD_MODE[lo_mode], _PAD_MODE[hi_mode]]
+            two_dx = 2 * float(np.mean(pressure.dx))
+        cp = _SlabCoupling(sharding, halo_in, halo_out, modes, two_dx, wrap)
+        nn_in = _SlabClosureInput.apply(velocity.flat, pressure.data if pressure_included else None, cp)
+        if wrapper is not None:
+            nn_out = wrapper(_WrappedOnSlabs(network, slab_wrap), nn_in)
+        else:
+            nn_out = network(nn_in, wrap=slab_wrap)
+        return velocity.rewrap(_SlabClosureForce.apply(nn_out, cp))
+    return forcing

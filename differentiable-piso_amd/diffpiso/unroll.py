@@ -103,9 +103,23 @@ def run_piso_steps(velocity, pressure, domain, physical_parameters, simulation_p
     if neural_network is not None:
         buffer_width = [[i // simulation_parameters["dx_ratio"] for i in j] for j in training_dict["HR_buffer_width"]]
 
+    slab = {}
+
+    def slab_wrapper(net, nn_in_ext):
+        # (slab fields: the network input and output are the rank's EXTENDED rows - sharding.make_slab_forcing_fn - and so is nn_all_steps)
+        nn_out = neural_network_wrapper(net, nn_in_ext, domain, physical_parameters, simulation_parameters, loss_buffer_width, buffer_width)
+        nn_all_steps.append(nn_out)
+        return nn_out
+
     def forcing_fn(i, vel, prs):
         if neural_network is None:
             return None
+        if hasattr(vel, "rewrap"):                                                      # a slab-decomposed simulation: the closure on the rank's rows
+            if slab.get("sharding") is not vel.sharding:
+                from .sharding import make_slab_forcing_fn
+                slab["sharding"] = vel.sharding
+                slab["fn"] = make_slab_forcing_fn(neural_network, vel.sharding, training_dict["pressure_included"], wrapper=slab_wrapper)
+            return slab["fn"](i, vel, prs)
         nn_in = vel.at_centers().data                                                   # :399, :444
         if training_dict["pressure_included"]:
             nn_in = torch.cat([nn_in, centered_gradient(prs)], dim=-1)                   # pressure.gradient().data

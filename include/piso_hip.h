@@ -225,6 +225,43 @@ int piso_h_contribution_adjoint_slab(const float* d_h, const float* d_h_over_bma
                                      float* d_delta, int nx, int ny, piso_stream_t stream, const piso_slab_t* slab);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Coupling of the CNN closure to the step (csrc/closure_glue.hip): what diffpiso/closure.py does with torch ops - network_input
+ * (velocity.at_centers() [+ centered_gradient(pressure)]) and centered_to_staggered - forward and reverse mode.  float32, one thread per
+ * OUTPUT element gathering its inputs (the adjoints as well: no atomics).
+ *   faces      flat u-first face vector          pressure   cells [ny][nx]
+ *   nn_in      NHWC [rows][nx][channels], channels 2 (v, u at the centres) or 4 (+ d/dy, d/dx of the pressure: central differences of the
+ *              pressure padded by one cell with pad_modes = {x lower, x upper, y lower, y upper}, 0 zeros | 1 edge value | 2 periodic -
+ *              both sides of a periodic axis periodic -, times (float)(1.0 / two_dx), the reciprocal of the double rounded to float32
+ *              once: what torch's device kernel makes of centered_gradient's "/ (2 dx)", bit for bit; channels 2: pressure, pad_modes,
+ *              two_dx are not read)
+ *   nn_out     NHWC [rows][nx][2] -> faces: the mean of the two cells of a face; at a border the edge cell twice, on a wrapped axis
+ *              (wrap_x / wrap_y) the cell across the seam, the duplicate face as well
+ * The *_adjoint entries take the cotangent of the forward entry's output and write the cotangents of its inputs (d_pressure may be NULL
+ * with 2 channels).
+ * Slab twins: faces / cells are the rank's stored rows (piso_slab_t); an NHWC buffer holds the whole-grid rows
+ * [row_begin - ext_lo, row_end + ext_hi) around the ring of ny rows (the halo rows of the network's receptive field plus the row the
+ * resampling reads across the cut; 0 on a side that ends at a border, where the network's own zero padding acts).  A launch writes the
+ * OWNED rows of its outputs and reads the rows around them, which the caller fills (piso_comm_exchange); a launch that would read an NHWC
+ * row the extended rows do not hold is refused with PISO_ERR_INVALID_ARG.  Boundary rules are decided on the whole grid's (i, j).
+ * piso_closure_halo_add: dst[k] += src[k], k < n - rows a reverse exchange delivered, added into their owner's edge rows. */
+int piso_closure_input(const float* faces, const float* pressure, float* nn_in, int nx, int ny, int channels, const int* pad_modes,
+                       double two_dx, piso_stream_t stream);
+int piso_closure_input_adjoint(const float* d_nn_in, float* d_faces, float* d_pressure, int nx, int ny, int channels, const int* pad_modes,
+                               double two_dx, piso_stream_t stream);
+int piso_closure_force(const float* nn_out, float* faces, int nx, int ny, int wrap_x, int wrap_y, piso_stream_t stream);
+int piso_closure_force_adjoint(const float* d_faces, float* d_nn_out, int nx, int ny, int wrap_x, int wrap_y, piso_stream_t stream);
+int piso_closure_input_slab(const float* faces, const float* pressure, float* nn_in, int nx, int ny, int channels, const int* pad_modes,
+                            double two_dx, piso_stream_t stream, const piso_slab_t* slab, int ext_lo, int ext_hi);
+int piso_closure_input_adjoint_slab(const float* d_nn_in, float* d_faces, float* d_pressure, int nx, int ny, int channels,
+                                    const int* pad_modes, double two_dx, piso_stream_t stream, const piso_slab_t* slab, int ext_lo,
+                                    int ext_hi);
+int piso_closure_force_slab(const float* nn_out, float* faces, int nx, int ny, int wrap_x, int wrap_y, piso_stream_t stream,
+                            const piso_slab_t* slab, int ext_lo, int ext_hi);
+int piso_closure_force_adjoint_slab(const float* d_faces, float* d_nn_out, int nx, int ny, int wrap_x, int wrap_y, piso_stream_t stream,
+                                    const piso_slab_t* slab, int ext_lo, int ext_hi);
+int piso_closure_halo_add(float* dst, const float* src, size_t n, piso_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Pressure matrix.  Replaces LaplaceMatrixKernelLauncher (CUDAsrc/pressure_solve_op.cc:78-84,
  * CUDAsrc/laplace_op.cu.cc:79-239).
  * ------------------------------------------------------------------------------------------------------------- */
