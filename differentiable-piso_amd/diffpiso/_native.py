@@ -222,6 +222,17 @@ for _n in ("piso_closure_input", "piso_closure_input_adjoint", "piso_closure_for
     getattr(lib, _n + "_slab").restype = _i
 lib.piso_closure_halo_add.argtypes = [_vp, _vp, _sz, _vp]
 lib.piso_closure_halo_add.restype = _i
+_d = C.c_double
+lib.piso_loss_workspace_bytes.argtypes = []
+lib.piso_loss_workspace_bytes.restype = _sz
+lib.piso_loss_l2.argtypes = [_vp, _vp, _i, _i, _i, _i, _i, _i, _d, _vp, _vp, _sz, _vp]          # (pred, target, nx, ny, y0, y1, x0, x1, factor, value, ws, bytes, stream)
+lib.piso_loss_l2_grad.argtypes = [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]          # (..., factor, upstream, d_pred, stream)
+lib.piso_loss_strain.argtypes = [_vp, _vp, _i, _i, _f, _f, _d, _vp, _vp, _sz, _vp]              # (pred, target, nx, ny, dx, dy, factor, value, ws, bytes, stream)
+lib.piso_loss_strain_grad.argtypes = [_vp, _vp, _i, _i, _f, _f, _d, _vp, _vp, _vp]              # (..., factor, upstream, d_pred, stream)
+for _n in ("piso_loss_l2", "piso_loss_l2_grad", "piso_loss_strain", "piso_loss_strain_grad"):
+    getattr(lib, _n).restype = _i
+    getattr(lib, _n + "_slab").argtypes = getattr(lib, _n).argtypes + [_sp]
+    getattr(lib, _n + "_slab").restype = _i
 lib.piso_csr_matvec_f32_slab.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sp]
 lib.piso_csr_matvec_f32_slab.restype = _i
 lib.piso_bicgstab_slab_workspace_bytes.argtypes = [_i, _i, _i, _sp]

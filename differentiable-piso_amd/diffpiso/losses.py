@@ -1,16 +1,196 @@
 """Training losses of the reference (diffpiso/losses.py): same names, argument meaning and return convention
 (`(loss + contribution, contribution)` when sum_steps, per-step lists otherwise).  `fields` / `velocity_fields` are lists
 (batch) of lists (steps) of StaggeredGrid as returned by the unrolled PISO steps; `ground_truths[i]` is a staggered tensor
-sequence [1, T, Ny+1, Nx+1, 2]."""
+sequence [1, T, Ny+1, Nx+1, 2].
+
+Slab fields (sharding.SlabStaggered, what a step of a slab-decomposed simulation returns): every loss keeps its signature and its return
+convention and returns the RANK'S PART - the parts add up over the ranks to the one-GPU value (the caller all-reduces, training.py).
+`ground_truths[i]` stays the whole-grid sequence on every rank; a step's frame is cut with `scatter_staggered`.
+  L2, strain   the fused kernels of csrc/loss.hip on the rank's stored rows (`piso_loss_*_slab`); the strain loss fills the prediction's
+               halo rows first (one `halo_faces`), its gather-form adjoint needs no exchange
+  multistep    torch ops on the `owned_faces` views, cropped with the window's intersection with the owned rows
+  spectral     every rank gathers the whole face field (`gather_face_rows`), evaluates the unchanged loss on it and contributes
+               value / world; costs ONE whole-grid field per step, transiently (no rocFFT on slabs)
+Whole-grid fields take the torch paths below unchanged; `L2_field_loss(..., fused=True)` / `strain_rate_loss(..., fused=True)` opt into the
+whole-grid instantiation of the same kernels (device tensors only - there is no CPU form of them)."""
+import ctypes as C
+
+import numpy as np
 import torch
 
+from . import _native as N
 from .evaluation_tools import EK_spectrum_2D_tf
 from .grids import StaggeredGrid
 from .les import forward_gradient
+from .sharding import SlabStaggered
 
 
 def _step_range(step_range):
     return step_range if isinstance(step_range, list) else [0, step_range]
+
+
+# ---------------------------------------------------------------------------------------------------- fused kernels (csrc/loss.hip)
+def loss_window(buffer_width, sponge_start, ny, nx):
+    """(y0, y1, x0, x1): the crop of L2_field_loss on the indices of the staggered tensor [ny + 1][nx + 1], exactly the two slices it
+    takes (`None`: the whole tensor; sponge_start 0: the tensor's width), resolved like Python resolves a slice and never inverted."""
+    rows, cols = int(ny) + 1, int(nx) + 1
+    if buffer_width is None:
+        return 0, rows, 0, cols
+    if sponge_start == 0:
+        sponge_start = cols
+    y0, y1, _ = slice(int(buffer_width[0][0]), rows - int(buffer_width[0][1])).indices(rows)
+    x0, x1, _ = slice(int(buffer_width[1][0]), int(sponge_start) - int(buffer_width[1][1])).indices(cols)
+    return y0, max(y1, y0), x0, max(x1, x0)
+
+
+def _loss_entry(name, slab_ptr):
+    """The whole-grid entry point, or its *_slab twin with the rank's piso_slab_t appended."""
+    if slab_ptr is None:
+        return getattr(N.lib, name), ()
+    return getattr(N.lib, name + "_slab"), (slab_ptr,)
+
+
+def _loss_workspace(device):
+    return N.workspace(N.lib.piso_loss_workspace_bytes(), device, "loss")
+
+
+def fused_l2_value(pred, target, nx, ny, window, factor, slab_ptr=None):
+    """piso_loss_l2(_slab): factor / 2 * sum (pred - target)^2 over the window's (owned) faces -> one float64 on the device."""
+    fn, tail = _loss_entry("piso_loss_l2", slab_ptr)
+    out = torch.empty(1, dtype=torch.float64, device=pred.device)
+    ws = _loss_workspace(pred.device)
+    N.check(fn(N.ptr(pred), N.ptr(target), int(nx), int(ny), *[int(w) for w in window], C.c_double(float(factor)), N.ptr(out), N.ptr(ws),
+               C.c_size_t(ws.numel()), N.stream_ptr(), *tail), "piso_loss_l2")
+    return out
+
+
+def fused_l2_grad(pred, target, nx, ny, window, factor, upstream, slab_ptr=None):
+    """piso_loss_l2_grad(_slab): upstream * factor * (pred - target) inside the window on the owned faces, zero everywhere else."""
+    fn, tail = _loss_entry("piso_loss_l2_grad", slab_ptr)
+    out = torch.zeros_like(pred)
+    N.check(fn(N.ptr(pred), N.ptr(target), int(nx), int(ny), *[int(w) for w in window], C.c_float(np.float32(factor)), N.ptr(upstream), N.ptr(out),
+               N.stream_ptr(), *tail), "piso_loss_l2_grad")
+    return out
+
+
+def fused_strain_value(pred, target, nx, ny, dx_yx, factor, slab_ptr=None):
+    """piso_loss_strain(_slab): factor * L1 distance of the unpadded strain entries (of the owned cell rows) -> one float64 on the device."""
+    fn, tail = _loss_entry("piso_loss_strain", slab_ptr)
+    out = torch.empty(1, dtype=torch.float64, device=pred.device)
+    ws = _loss_workspace(pred.device)
+    N.check(fn(N.ptr(pred), N.ptr(target), int(nx), int(ny), C.c_float(np.float32(dx_yx[1])), C.c_float(np.float32(dx_yx[0])),
+               C.c_double(float(factor)), N.ptr(out), N.ptr(ws), C.c_size_t(ws.numel()), N.stream_ptr(), *tail), "piso_loss_strain")
+    return out
+
+
+def fused_strain_grad(pred, target, nx, ny, dx_yx, factor, upstream, slab_ptr=None):
+    fn, tail = _loss_entry("piso_loss_strain_grad", slab_ptr)
+    out = torch.zeros_like(pred)
+    N.check(fn(N.ptr(pred), N.ptr(target), int(nx), int(ny), C.c_float(np.float32(dx_yx[1])), C.c_float(np.float32(dx_yx[0])),
+               C.c_double(float(factor)), N.ptr(upstream), N.ptr(out), N.stream_ptr(), *tail), "piso_loss_strain_grad")
+    return out
+
+
+class _FusedL2(torch.autograd.Function):
+    """cfg = (nx, ny, window, factor, slab_ptr): the value as a float32 scalar; reverse mode is the gradient kernel (no host read)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, cfg):
+        ctx.cfg = cfg
+        ctx.save_for_backward(pred, target)
+        return fused_l2_value(pred, target, *cfg)[0].to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, target = ctx.saved_tensors
+        nx, ny, window, factor, slab_ptr = ctx.cfg
+        return fused_l2_grad(pred, target, nx, ny, window, factor, g.to(torch.float32).reshape(1).contiguous(), slab_ptr), None, None
+
+
+class _FusedStrain(torch.autograd.Function):
+    """cfg = (nx, ny, dx_yx, factor, slab_ptr).  On slabs the caller has filled the halo rows of `pred` (the saved tensor keeps them)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, cfg):
+        ctx.cfg = cfg
+        ctx.save_for_backward(pred, target)
+        return fused_strain_value(pred, target, *cfg)[0].to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, target = ctx.saved_tensors
+        nx, ny, dx_yx, factor, slab_ptr = ctx.cfg
+        return fused_strain_grad(pred, target, nx, ny, dx_yx, factor, g.to(torch.float32).reshape(1).contiguous(), slab_ptr), None, None
+
+
+def _flat_pair(field, truth_frame):
+    """(prediction, target, nx, ny, slab_ptr, sharding) as flat u-first face vectors: the rank's stored rows for a SlabStaggered (the target
+    cut out of the replicated frame, halo rows included), the whole grid's otherwise."""
+    from .fused import flat_faces
+    ny, nx = (int(r) for r in field.resolution)
+    if isinstance(field, SlabStaggered):
+        sh = field.sharding
+        pred = field.flat.contiguous()
+        return pred, sh.scatter_staggered(truth_frame, device=pred.device), nx, ny, sh.slab_ptr, sh
+    pred = flat_faces(field).to(torch.float32).contiguous()
+    target = flat_faces(StaggeredGrid(truth_frame)).to(device=pred.device, dtype=torch.float32).contiguous()
+    return pred, target, nx, ny, None, None
+
+
+def _fused_l2(field, truth_frame, buffer_width, sponge_start, factor):
+    pred, target, nx, ny, slab_ptr, _ = _flat_pair(field, truth_frame)
+    return _FusedL2.apply(pred, target, (nx, ny, loss_window(buffer_width, sponge_start, ny, nx), float(factor), slab_ptr))
+
+
+def _fused_strain(field, truth_frame, factor):
+    pred, target, nx, ny, slab_ptr, sh = _flat_pair(field, truth_frame)
+    if sh is not None:
+        sh.halo_faces(pred.detach())                         # both launches read one row either side of the owned rows (in place, like the step)
+    return _FusedStrain.apply(pred, target, (nx, ny, tuple(float(d) for d in field.dx), float(factor), slab_ptr))
+
+
+class _GatherFaces(torch.autograd.Function):
+    """The rank's stored rows -> the whole grid's flat face vector on every rank (distributed.gather_face_rows).  Every rank then evaluates
+    the SAME function of the replicated field and contributes value / world: the cotangent that arrives is 1 / world of the whole gradient,
+    so the rank's own rows of it are taken `world` times - and nothing has to be summed over the ranks."""
+
+    @staticmethod
+    def forward(ctx, flat, sh):
+        from .distributed import face_rows_of_rank, gather_face_rows
+        nx, ny = sh.nx, sh.ny
+        (u0, u1), (v0, v1) = face_rows_of_rank(sh.rank, sh.world, nx, ny)
+        u, v = sh.owned_faces(flat)
+        whole = torch.zeros((nx + 1) * ny + nx * (ny + 1), dtype=flat.dtype, device=flat.device)
+        whole[u0:u1] = u.reshape(-1)
+        whole[v0:v1] = v.reshape(-1)
+        ctx.sh, ctx.ranges = sh, ((u0, u1), (v0, v1))
+        return gather_face_rows(sh.comm, whole, nx, ny)
+
+    @staticmethod
+    def backward(ctx, g):
+        sh, ((u0, u1), (v0, v1)) = ctx.sh, ctx.ranges
+        d = torch.zeros(sh.n_faces, dtype=g.dtype, device=g.device)
+        u, v = sh.owned_faces(d)
+        u.copy_(g[u0:u1].view_as(u) * sh.world)
+        v.copy_(g[v0:v1].view_as(v) * sh.world)
+        return d, None
+
+
+def _gathered_grid(field):
+    """A SlabStaggered as the whole grid's StaggeredGrid, replicated on every rank (one whole-grid field, alive while its loss term is)."""
+    sh = field.sharding
+    whole = _GatherFaces.apply(field.flat, sh)
+    n_u = (sh.nx + 1) * sh.ny
+    return StaggeredGrid([whole[n_u:].view(1, sh.ny + 1, sh.nx, 1), whole[:n_u].view(1, sh.ny, sh.nx + 1, 1)], field.box,
+                         extrapolation=field.extrapolation)
+
+
+def _owned_crop(rows, row_slice, first, count):
+    """Local row slice of an owned-rows view: the whole-grid `row_slice` of a component of `rows` rows, cut to the owned rows
+    [first, first + count)."""
+    a, b, _ = row_slice.indices(rows)
+    lo, hi = max(a, first), min(b, first + count)
+    return slice(lo - first, max(hi, lo) - first)
 
 
 def _l2(t):                                                   # tf.nn.l2_loss
@@ -31,6 +211,9 @@ def L2_field_loss(loss, fields, ground_truths, step_range, buffer_width, loss_fa
     contrib = [[] for _ in range(step_range[1] - step_range[0])]
     for i in range(len(fields)):
         for s in range(step_range[0], step_range[1]):
+            if isinstance(fields[i][s], SlabStaggered) or kwargs.get("fused", False):
+                contrib[s - step_range[0]].append(_fused_l2(fields[i][s], ground_truths[i][:, s, ...], buffer_width, sponge_start, loss_factor[s]))
+                continue
             data = fields[i][s].staggered_tensor()
             target = StaggeredGrid(ground_truths[i][:, s, ...]).staggered_tensor().to(data.device)
             if buffer_width is not None:
@@ -59,7 +242,10 @@ def spectral_energy_loss(loss, velocity_fields, ground_truths, step_range, buffe
         loss_factor = [loss_factor for _ in range(step_range[1])]
     contrib = []
     for s in range(step_range[0], step_range[1]):
-        central = velocity_fields[0][s].at_centers().data
+        vel, share = velocity_fields[0][s], None
+        if isinstance(vel, SlabStaggered):                   # the replicated whole field; this rank's part is value / world
+            vel, share = _gathered_grid(vel), 1.0 / vel.sharding.world
+        central = vel.at_centers().data
         if sponge_start == 0:
             sponge_start = central.shape[2]
         ys = slice(buffer_width[0][0], int(central.shape[1]) - buffer_width[0][1])
@@ -72,6 +258,8 @@ def spectral_energy_loss(loss, velocity_fields, ground_truths, step_range, buffe
             contrib.append(torch.sqrt(d[1 + start_wavenumber:].sum()) * loss_factor[s])
         else:
             contrib.append((g[:e.shape[0]] - e).abs()[1:].sum() * loss_factor[s])
+        if share is not None:
+            contrib[-1] = contrib[-1] * share
     if sum_steps:
         total = _sum(contrib)
         return loss + total, total
@@ -94,6 +282,9 @@ def strain_rate_loss(loss, velocity_fields, ground_truths, step_range, buffer_wi
     contrib = []
     for s in range(step_range[0], step_range[1]):
         vel = velocity_fields[0][s]
+        if isinstance(vel, SlabStaggered) or kwargs.get("fused", False):
+            contrib.append(_fused_strain(vel, ground_truths[0][:, s, ...], loss_factor[s]))
+            continue
         gt = StaggeredGrid(ground_truths[0][:, s, ...].to(vel.staggered_tensor().device), vel.box)
         a, b = _strain_parts(vel), _strain_parts(gt)
         contrib.append(sum((a[i] - b[i]).abs().sum() for i in range(4)) * loss_factor[s])
@@ -111,6 +302,20 @@ def multistep_averaging_loss(loss, velocity_fields, ground_truths, step_range, b
     n = step_range[1] - step_range[0]
     du, dv, du_gt, dv_gt = [], [], [], []
     for s in range(step_range[0], step_range[1]):
+        if isinstance(velocity_fields[0][s], SlabStaggered):
+            # pointwise in space: the owned rows of prediction and truth, cropped with the window's intersection with the owned rows
+            sh = velocity_fields[0][s].sharding
+            u, v = sh.owned_faces(velocity_fields[0][s].flat)
+            last = 1 if sh.last else 0
+            gt = StaggeredGrid(ground_truths[0][:, s, ...].to(u.device))
+            ru = _owned_crop(sh.ny, slice(buffer_width[0][0], sh.ny - buffer_width[0][1]), sh.j0, sh.nyl)
+            rv = _owned_crop(sh.ny + 1, slice(buffer_width[0][0], sh.ny + 1 - buffer_width[0][1]), sh.j0, sh.nyl + last)
+            cu = slice(buffer_width[1][0], sh.nx + 1 - buffer_width[1][1])
+            cv = slice(buffer_width[1][0], sh.nx - buffer_width[1][1])
+            du.append(u[ru, cu][None]); dv.append(v[rv, cv][None])
+            du_gt.append(gt.data[1].data[0, sh.j0:sh.j1, :, 0][ru, cu][None])
+            dv_gt.append(gt.data[0].data[0, sh.j0:sh.j1 + last, :, 0][rv, cv][None])
+            continue
         u, v = velocity_fields[0][s].data[1].data, velocity_fields[0][s].data[0].data
         su = (slice(None), slice(buffer_width[0][0], int(u.shape[1]) - buffer_width[0][1]),
               slice(buffer_width[1][0], int(u.shape[2]) - buffer_width[1][1]), 0)

@@ -249,7 +249,12 @@ class StepSharding(object):
                  dmask=self.scatter_staggered(_host(sim.dirichlet_mask).astype(np.float32), torch.float32, device).ne(0).to(torch.uint8).contiguous(),
                  no_slip=None)
         if sim.no_slip_mask is not None:
-            c["no_slip"] = self.scatter_mask(_host(sim.no_slip_mask).astype(np.float32), torch.float32, device).ne(0).to(torch.uint8).contiguous()
+            # (as SimulationParameters.no_slip_flat reads it on one GPU: the first (ny + 2)(nx + 2) elements of an array that may be larger -
+            # spatialMixingLayer_setup hands over one of the staggered tensor's shape)
+            ns, need = _host(sim.no_slip_mask).astype(np.float32).reshape(-1), (self.ny + 2) * (self.nx + 2)
+            if ns.size < need:
+                raise ValueError("no_slip_mask must cover the padded cell grid (Ny+2)*(Nx+2)")
+            c["no_slip"] = self.scatter_mask(ns[:need], torch.float32, device).ne(0).to(torch.uint8).contiguous()
         self._sim_cache[key] = (sim, stamp, c)
         return c
 

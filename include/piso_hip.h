@@ -738,6 +738,53 @@ int piso_cg_solve_slab_emulated_f64(int slabs, int nx, int ny, int periodic_x, i
                                     int rank_deficient, int residual_reset, int* iterations_out, void* workspace,
                                     size_t workspace_bytes, piso_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Training losses on flat u-first face vectors (csrc/loss.hip; the reference computes them as TensorFlow graph ops,
+ * diffpiso/losses.py:6-35 and :66-95).  pred / target: the `.flat` vector of a step's result - the whole grid's, or for the *_slab
+ * twins the rank's stored rows (piso_slab_t).  Fields are read as float32 and every term is formed in float32 in the order of the
+ * reference's ops; only the sum is float64.
+ *
+ * Value entries: two launches - float64 per-block partials into `workspace` (piso_loss_workspace_bytes()), then ONE workgroup re-adds
+ *   them in index order into value[0] (a device double; the same bits on every run of the same launch).  A slab launch adds what the rank
+ *   OWNS, so the ranks' values add up to the whole grid's: L2 - its owned faces (the duplicate row v[ny] belongs to the slab with
+ *   owns_last_face_row); strain - the entries of its owned cell rows (corner (j, i) belongs to cell row j).
+ * Gradient entries (*_grad): d_pred[face] = upstream[0] * d value / d pred[face] as float32, one thread per owned face, GATHERING - a
+ *   launch writes the owned faces and nothing else (the caller zeroes the halo rows of d_pred once).  upstream: ONE float on the device.
+ *
+ * piso_loss_l2:  factor / 2 * sum (pred - target)^2 over the crop window.  The window lives on the indices of the staggered tensor
+ *   [ny + 1][nx + 1][2] the torch loss slices: a u face (j, i), 0 <= j < ny, 0 <= i <= nx, and a v face (j, i), 0 <= j <= ny, 0 <= i < nx,
+ *   count iff y0 <= j < y1 and x0 <= i < x1 (0 <= y0, y1 <= ny + 1, 0 <= x0, x1 <= nx + 1; y1 <= y0 or x1 <= x0: empty).  The tensor's
+ *   padded last row of u and last column of v are not faces and contribute nothing.  Gradient: factor * (pred - target) inside, 0 outside.
+ *
+ * piso_loss_strain:  factor * (sum |D yy| + 2 sum |D off| + sum |D xx|), D e = e(pred) - e(target), the unpadded strain entries
+ *     yy  at cells (j, i), 0 <= j < ny, 0 <= i < nx:        (v[j+1][i] - v[j][i]) / dy
+ *     xx  at the same cells:                                 (u[j][i+1] - u[j][i]) / dx
+ *     off at the INTERIOR grid corners (j, i), 1 <= j <= ny - 1, 1 <= i <= nx - 1 (corner (j, i) = the lower left corner of cell (j, i)):
+ *                                                            ((v[j][i] - v[j][i-1]) / dx + (u[j][i] - u[j-1][i]) / dy) / 2
+ *   The corner set has no entry on the border of the domain: row 0 and column 0 are not corners, and neither are row ny / column nx.
+ *   off counts twice - the reference sums the four parts [yy, off, off, xx].  Gradient of a face: the sum of sign(D e) * (d e / d face)
+ *   over the at most six entries that read it, sign(0) = 0.  Both launches read rows j - 1 .. j + 1 around an owned row j of pred AND
+ *   target: on slabs the caller fills their halo rows (one row either side suffices; the stored 2 (u) / 3 (v) rows hold it).
+ * nx, ny >= 1 (strain: >= 2, dx, dy > 0); anything else, or an illegal slab: PISO_ERR_INVALID_ARG before any launch.
+ * ------------------------------------------------------------------------------------------------------------- */
+size_t piso_loss_workspace_bytes(void);
+int piso_loss_l2(const float* pred, const float* target, int nx, int ny, int y0, int y1, int x0, int x1, double factor, double* value,
+                 void* workspace, size_t workspace_bytes, piso_stream_t stream);
+int piso_loss_l2_slab(const float* pred, const float* target, int nx, int ny, int y0, int y1, int x0, int x1, double factor, double* value,
+                      void* workspace, size_t workspace_bytes, piso_stream_t stream, const piso_slab_t* slab);
+int piso_loss_l2_grad(const float* pred, const float* target, int nx, int ny, int y0, int y1, int x0, int x1, float factor,
+                      const float* upstream, float* d_pred, piso_stream_t stream);
+int piso_loss_l2_grad_slab(const float* pred, const float* target, int nx, int ny, int y0, int y1, int x0, int x1, float factor,
+                           const float* upstream, float* d_pred, piso_stream_t stream, const piso_slab_t* slab);
+int piso_loss_strain(const float* pred, const float* target, int nx, int ny, float dx, float dy, double factor, double* value, void* workspace,
+                     size_t workspace_bytes, piso_stream_t stream);
+int piso_loss_strain_slab(const float* pred, const float* target, int nx, int ny, float dx, float dy, double factor, double* value,
+                          void* workspace, size_t workspace_bytes, piso_stream_t stream, const piso_slab_t* slab);
+int piso_loss_strain_grad(const float* pred, const float* target, int nx, int ny, float dx, float dy, double factor, const float* upstream,
+                          float* d_pred, piso_stream_t stream);
+int piso_loss_strain_grad_slab(const float* pred, const float* target, int nx, int ny, float dx, float dy, double factor, const float* upstream,
+                               float* d_pred, piso_stream_t stream, const piso_slab_t* slab);
+
 #ifdef __cplusplus
 }
 #endif
