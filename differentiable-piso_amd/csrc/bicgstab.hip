@@ -302,9 +302,24 @@ __device__ __forceinline__ M block_exclusive_scan(M v, M* smem) {
 //   d(i,j) = cC - cW(i,j) cE(i-1,j) / d(i-1,j) - [j > band start] cS(i,j) cN(i,j-1) / d(i,j-1)
 //   LW = cW(k)/d(k-1), LS = cS(k)/d(k-W), UE = cE(k)/d(k), UN = cN(k)/d(k) (LS / UN zero across band edges)
 // ------------------------------------------------------------------------------------------------------------------
+// Both this recurrence and the sweeps' below stand once, in two forms of moving a row (LDS = false / true).  Direct: a thread loads and
+// stores the E consecutive elements it scans.  Lanes are then E elements apart: every load / store instruction touches E cache lines'
+// worth of address range per 64 lanes and every line is visited by E instructions - for wide rows the texture addresser, not HBM, set
+// the pace (2048^2 sweeps: 2.0 / 3.6 TB/s forward / backward).  Staged (round 5): every global access COALESCED - a row moves between
+// memory and LDS in element order (lane = consecutive element) and between LDS and the scan's registers in thread order (E consecutive
+// elements per thread; odd strides are conflict-free, even ones padded by one word per 32).  The forms differ in which column a thread
+// moves, where the scan finds its operands and where the results go - not in one arithmetic statement, so they agree bit for bit.
+// 2048^2, per sweep: forward 47 -> 29 us, backward 68 -> 33 us (of which 59 -> 33 by forming y / d behind the scan, see load_row).
+template <int E>
+__device__ __forceinline__ int sweep_slot(int s) { return (E % 2 == 0) ? s + (s >> 5) : s; }
 template <typename T, int E>
+constexpr bool kSweepLds = bi_lds_instance(sizeof(T), E);   // (bicgstab_dispatch.h: the one statement of which staged instances exist)
+
+template <typename T, int E, bool LDS>
 __global__ __launch_bounds__(kBlock) void bi_factor(BiArgs<T> a) {
+  constexpr int kRow = LDS ? E * kBlock + E * 8 : 1;          // (direct: the rows are never touched and take no LDS)
   __shared__ Moebius<T> smem[4];
+  __shared__ T bw[kRow], bs[kRow], bc[kRow], be[kRow], bn[kRow];      // a row's five coefficients on the way in, its five results on the way out
   const int c = blockIdx.y;
   const Geo& g = a.g;
   const int band = a.bb[c] + blockIdx.x;
@@ -316,66 +331,7 @@ __global__ __launch_bounds__(kBlock) void bi_factor(BiArgs<T> a) {
   T cN_prev_row[E];
 #pragma unroll
   for (int e = 0; e < E; ++e) { d_prev_row[e] = 1; cN_prev_row[e] = 0; }
-  for (int j = j0; j < j1; ++j) {
-    const int kb = a.kx(c, j * W);
-    T A[E], B[E], cw[E], cs[E], ce[E], cn[E];
-    Moebius<T> f = Moebius<T>::identity();
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const int i = i0 + e;
-      A[e] = 1; B[e] = 0; cw[e] = cs[e] = ce[e] = cn[e] = 0;
-      if (i < W) {
-        const int k = kb + i;
-        cw[e] = a.cW[k]; cs[e] = a.cS[k]; ce[e] = a.cE[k]; cn[e] = a.cN[k];
-        const T ce_left = (i >= 1) ? a.cE[k - 1] : (T)0;
-        A[e] = a.cC[k] - ((j > j0) ? cs[e] * cN_prev_row[e] / d_prev_row[e] : (T)0);
-        B[e] = cw[e] * ce_left;
-        const Moebius<T> fi = {A[e], -B[e], (T)1, (T)0};
-        f = Moebius<T>::then(f, fi);
-      }
-    }
-    const Moebius<T> pre = block_exclusive_scan(f, smem);
-    // pivot just left of my chunk: pre(infinity) = a / c  (thread 0: unused because B == 0 at i == 0)
-    T dl = (threadIdx.x == 0 || pre.c == 0) ? (T)1 : pre.a / pre.c;
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const int i = i0 + e;
-      if (i < W) {
-        const int k = kb + i;
-        const T d = A[e] - B[e] / dl;
-        const T inv = (T)1 / d;
-        a.L[k] = Pair<T>{(i >= 1) ? cw[e] / dl : (T)0, (j > j0) ? cs[e] / d_prev_row[e] : (T)0};
-        a.U[k] = Tri<T>{inv, ce[e] * inv, (j < j1 - 1) ? cn[e] * inv : (T)0};
-        dl = d;
-        d_prev_row[e] = d;
-        cN_prev_row[e] = cn[e];
-      }
-    }
-  }
-}
-
-template <int E>
-__device__ __forceinline__ int sweep_slot(int s) { return (E % 2 == 0) ? s + (s >> 5) : s; }
-template <typename T, int E>
-constexpr bool kSweepLds = bi_lds_instance(sizeof(T), E);   // (bicgstab_dispatch.h: the one statement of which instances exist)
-
-// bi_factor with coalesced memory accesses (see bi_sweep_lds): a row's five coefficients come in element order, are staged in LDS,
-// read back E consecutive elements per thread; the five results go the same way back.  Bitwise bi_factor's results.
-template <typename T, int E>
-__global__ __launch_bounds__(kBlock) void bi_factor_lds(BiArgs<T> a) {
-  constexpr int kRow = E * kBlock + E * 8;
-  __shared__ Moebius<T> smem[4];
-  __shared__ T bw[kRow], bs[kRow], bc[kRow], be[kRow], bn[kRow];
-  const int c = blockIdx.y;
-  const Geo& g = a.g;
-  const int band = a.bb[c] + blockIdx.x;
-  if (band >= a.be[c]) return;
-  const int W = g.W[c], H = g.H[c];
-  const int j0 = band * g.R, j1 = min(j0 + g.R, H);
-  const int i0 = threadIdx.x * E;
-  T d_prev_row[E], cN_prev_row[E];
-#pragma unroll
-  for (int e = 0; e < E; ++e) { d_prev_row[e] = 1; cN_prev_row[e] = 0; }
+  // staged form, memory side: column i = e * kBlock + thread
   T lw[E], ls[E], lc[E], le[E], ln[E];
   auto load_row = [&](int j) __attribute__((always_inline)) {
     const int kb = a.kx(c, j * W);
@@ -399,9 +355,11 @@ __global__ __launch_bounds__(kBlock) void bi_factor_lds(BiArgs<T> a) {
       }
     }
   };
-  load_row(j0);
-  stage_row();
-  __syncthreads();
+  if constexpr (LDS) {
+    load_row(j0);
+    stage_row();
+    __syncthreads();
+  }
   for (int j = j0; j < j1; ++j) {
     const int kb = a.kx(c, j * W);
     T A[E], B[E], cw[E], cs[E], ce[E], cn[E];
@@ -411,48 +369,65 @@ __global__ __launch_bounds__(kBlock) void bi_factor_lds(BiArgs<T> a) {
       const int i = i0 + e;
       A[e] = 1; B[e] = 0; cw[e] = cs[e] = ce[e] = cn[e] = 0;
       if (i < W) {
-        const int q = sweep_slot<E>(i);
-        cw[e] = bw[q]; cs[e] = bs[q]; ce[e] = be[q]; cn[e] = bn[q];
-        const T ce_left = (i >= 1) ? (e > 0 ? ce[e - 1] : be[sweep_slot<E>(i - 1)]) : (T)0;
-        A[e] = bc[q] - ((j > j0) ? cs[e] * cN_prev_row[e] / d_prev_row[e] : (T)0);
+        T ce_left, cc;
+        if constexpr (LDS) {
+          const int q = sweep_slot<E>(i);
+          cw[e] = bw[q]; cs[e] = bs[q]; ce[e] = be[q]; cn[e] = bn[q];
+          ce_left = (i >= 1) ? (e > 0 ? ce[e - 1] : be[sweep_slot<E>(i - 1)]) : (T)0;
+          cc = bc[q];
+        } else {
+          const int k = kb + i;
+          cw[e] = a.cW[k]; cs[e] = a.cS[k]; ce[e] = a.cE[k]; cn[e] = a.cN[k];
+          ce_left = (i >= 1) ? a.cE[k - 1] : (T)0;
+          cc = a.cC[k];
+        }
+        A[e] = cc - ((j > j0) ? cs[e] * cN_prev_row[e] / d_prev_row[e] : (T)0);
         B[e] = cw[e] * ce_left;
         const Moebius<T> fi = {A[e], -B[e], (T)1, (T)0};
         f = Moebius<T>::then(f, fi);
       }
     }
-    load_row(j + 1);                              // (in flight during the scan)
-    const Moebius<T> pre = block_exclusive_scan(f, smem);      // (its barriers: every thread has read the staged row)
+    if constexpr (LDS) load_row(j + 1);           // (in flight during the scan)
+    const Moebius<T> pre = block_exclusive_scan(f, smem);      // (staged: its barriers - every thread has read the staged row)
+    // pivot just left of my chunk: pre(infinity) = a / c  (thread 0: unused because B == 0 at i == 0)
     T dl = (threadIdx.x == 0 || pre.c == 0) ? (T)1 : pre.a / pre.c;
 #pragma unroll
     for (int e = 0; e < E; ++e) {
       const int i = i0 + e;
       if (i < W) {
-        const int q = sweep_slot<E>(i);
         const T d = A[e] - B[e] / dl;
         const T inv = (T)1 / d;
-        bw[q] = (i >= 1) ? cw[e] / dl : (T)0;                           // LW
-        bs[q] = (j > j0) ? cs[e] / d_prev_row[e] : (T)0;                // LS
-        bc[q] = inv;
-        be[q] = ce[e] * inv;                                            // UE
-        bn[q] = (j < j1 - 1) ? cn[e] * inv : (T)0;                      // UN
+        const T LW = (i >= 1) ? cw[e] / dl : (T)0;
+        const T LS = (j > j0) ? cs[e] / d_prev_row[e] : (T)0;
+        const T UE = ce[e] * inv;
+        const T UN = (j < j1 - 1) ? cn[e] * inv : (T)0;
+        if constexpr (LDS) {
+          const int q = sweep_slot<E>(i);
+          bw[q] = LW; bs[q] = LS; bc[q] = inv; be[q] = UE; bn[q] = UN;
+        } else {
+          a.L[kb + i] = Pair<T>{LW, LS};
+          a.U[kb + i] = Tri<T>{inv, UE, UN};
+        }
         dl = d;
         d_prev_row[e] = d;
         cN_prev_row[e] = cn[e];
       }
     }
-    __syncthreads();
+    if constexpr (LDS) {
+      __syncthreads();                            // (the row's results are in LDS)
 #pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const int i = e * kBlock + threadIdx.x;
-      if (i < W) {
-        const int q = sweep_slot<E>(i);
-        a.L[kb + i] = Pair<T>{bw[q], bs[q]};
-        a.U[kb + i] = Tri<T>{bc[q], be[q], bn[q]};
+      for (int e = 0; e < E; ++e) {
+        const int i = e * kBlock + threadIdx.x;
+        if (i < W) {
+          const int q = sweep_slot<E>(i);
+          a.L[kb + i] = Pair<T>{bw[q], bs[q]};
+          a.U[kb + i] = Tri<T>{bc[q], be[q], bn[q]};
+        }
       }
+      __syncthreads();                            // (the results are out of LDS)
+      stage_row();                                // row j + 1
+      __syncthreads();                            // (... is staged)
     }
-    __syncthreads();                              // (the results are out of LDS)
-    stage_row();                                  // row j + 1
-    __syncthreads();
   }
 }
 
@@ -464,10 +439,12 @@ __global__ __launch_bounds__(kBlock) void bi_factor_lds(BiArgs<T> a) {
 template <typename T>
 __device__ __forceinline__ CompScalars<T> folded_scalars(const BiArgs<T>& a, int c, T* smem);   // (with the scalar stages, below)
 
-template <typename T, int E, bool FWD>
+template <typename T, int E, bool FWD, bool LDS>
 __global__ __launch_bounds__(kBlock) void bi_sweep(BiArgs<T> a, const T* in, T* __restrict__ out) {
+  constexpr int kRow = LDS ? E * kBlock + E * 8 : 1;          // (direct: the rows are never touched and take no LDS)
   __shared__ Affine<T> smem[4];
   __shared__ T smem_fold[16];
+  __shared__ T bv[kRow], ba[kRow], bb[kRow], by[kRow];        // a row's value and two coefficients on the way in, its y on the way out
   const int c = blockIdx.y;
   const Geo& g = a.g;
   const CompScalars<T> sc = folded_scalars(a, c, smem_fold);  // (folded: the ||s|| test in front of s_hat; ||r|| test, rho / beta in front of p_hat)
@@ -479,21 +456,24 @@ __global__ __launch_bounds__(kBlock) void bi_sweep(BiArgs<T> a, const T* in, T* 
   const int j0 = band * g.R, j1 = min(j0 + g.R, H);
   const Pair<T>* __restrict__ cl = a.L;
   const Tri<T>* __restrict__ cu = a.U;
-  // element order along the scan: forward i ascending, backward i descending
+  // element order along the scan: forward i ascending, backward i descending - place s along the scan <-> column i, either way round
+  auto across = [&](int s) { return FWD ? s : W - 1 - s; };
   const int i0 = threadIdx.x * E;
   T prev[E];
 #pragma unroll
   for (int e = 0; e < E; ++e) prev[e] = 0;
   // The rows of a band are sequential (y(k) needs y(k-W)), but what a row READS from memory does not depend on the
   // recurrence: the inputs of row jj+1 are loaded while row jj is scanned (a row is latency-, not bandwidth-bound).
+  // Slot e of a thread holds, direct: the column of its e-th place along the scan; staged: column e * kBlock + thread (ascending
+  // addresses in both directions).
   T nv[E], na[E], nb[E], nd[E], n2[E], n3[E];
   auto load_row = [&](int jj) __attribute__((always_inline)) {
     const int j = FWD ? j0 + jj : j1 - 1 - jj;
     const int kb = a.kx(c, j * W);
 #pragma unroll
     for (int e = 0; e < E; ++e) {
-      const int s = i0 + e;
-      const int i = FWD ? s : W - 1 - s;
+      const int s = LDS ? e * kBlock + threadIdx.x : i0 + e;
+      const int i = LDS ? s : across(s);
       nv[e] = 0; na[e] = 0; nb[e] = 0; nd[e] = 0; n2[e] = 0; n3[e] = 0;
       if (s < W && jj < j1 - j0) {
         const int k = kb + i;
@@ -505,88 +485,11 @@ __global__ __launch_bounds__(kBlock) void bi_sweep(BiArgs<T> a, const T* in, T* 
       }
     }
   };
-  load_row(0);
-  for (int jj = 0; jj < j1 - j0; ++jj) {
-    const int j = FWD ? j0 + jj : j1 - 1 - jj;
-    const int kb = a.kx(c, j * W);
-    T m[E], cst[E];
-    Affine<T> f = Affine<T>::identity();
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const int s = i0 + e;                       // position along the scan
-      m[e] = 0; cst[e] = 0;
-      if (s < W) {
-        T v = FWD ? nv[e] : nv[e] * nd[e];
-        if (fuse) { v = (nv[e] - sc.omega * n2[e]) * sc.beta + n3[e]; a.p[kb + s] = v; }
-        cst[e] = v - nb[e] * prev[e];
-        m[e] = -na[e];
-        f = Affine<T>::then(f, Affine<T>{m[e], cst[e]});
-      }
-    }
-    load_row(jj + 1);                             // (in flight during the scan below)
-    const Affine<T> pre = block_exclusive_scan(f, smem);
-    T yl = pre.c;                                 // value just before my chunk (pre applied to 0; first m is 0 anyway)
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const int s = i0 + e;
-      const int i = FWD ? s : W - 1 - s;
-      if (s < W) {
-        const T y = fma(m[e], yl, cst[e]);
-        out[kb + i] = y;
-        prev[e] = y;
-        yl = y;
-      }
-    }
-  }
-}
-
-// The same sweep with every global access COALESCED (round 5).  In bi_sweep a thread loads and stores the E consecutive elements it
-// scans: lanes E * 4 bytes apart, every load / store instruction touches E cache lines' worth of address range per 64 lanes and every
-// line is visited by E instructions - the texture addresser, not HBM, set the pace (2048^2: 2.0 / 3.6 TB/s forward / backward).  Here
-// a row moves between memory and LDS in element order (lane = consecutive element) and between LDS and the scan's registers in
-// thread order (E consecutive elements per thread; odd strides are conflict-free, even ones padded by one word per 32).  One more
-// barrier per row; the arithmetic, the scan and therefore every result are bitwise bi_sweep's.  2048^2, per sweep: forward 47 -> 29 us,
-// backward 68 -> 33 us (of which 59 -> 33 by forming y / d behind the scan instead of in front of it, see load_row).
-template <typename T, int E, bool FWD>
-__global__ __launch_bounds__(kBlock) void bi_sweep_lds(BiArgs<T> a, const T* in, T* __restrict__ out) {
-  constexpr int kRow = E * kBlock + E * 8;
-  __shared__ Affine<T> smem[4];
-  __shared__ T smem_fold[16];
-  __shared__ T bv[kRow], ba[kRow], bb[kRow], by[kRow];
-  const int c = blockIdx.y;
-  const Geo& g = a.g;
-  const CompScalars<T> sc = folded_scalars(a, c, smem_fold);
-  if (sc.done) return;
-  const bool fuse = FWD && a.fuse_p;
-  const int band = a.bb[c] + blockIdx.x;
-  if (band >= a.be[c]) return;
-  const int W = g.W[c], H = g.H[c];
-  const int j0 = band * g.R, j1 = min(j0 + g.R, H);
-  const Pair<T>* __restrict__ cl = a.L;
-  const Tri<T>* __restrict__ cu = a.U;
-  const int i0 = threadIdx.x * E;
-  T prev[E];
-#pragma unroll
-  for (int e = 0; e < E; ++e) prev[e] = 0;
-  T nv[E], na[E], nb[E], nd[E], n2[E], n3[E];
-  // memory side: column i = e * kBlock + thread (ascending addresses in both directions); its place along the scan is i (forward) or
-  // W - 1 - i (backward)
-  auto load_row = [&](int jj) __attribute__((always_inline)) {
-    const int j = FWD ? j0 + jj : j1 - 1 - jj;
-    const int kb = a.kx(c, j * W);
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const int i = e * kBlock + threadIdx.x;
-      nv[e] = 0; na[e] = 0; nb[e] = 0; nd[e] = 0; n2[e] = 0; n3[e] = 0;
-      if (i < W && jj < j1 - j0) {
-        const int k = kb + i;
-        nv[e] = in[k];
-        if (fuse) { n2[e] = a.v[k]; n3[e] = a.r[k]; }
-        if (FWD) { const Pair<T> cf = cl[k]; na[e] = cf.a; nb[e] = cf.b; }
-        else { const Tri<T> cf = cu[k]; nd[e] = cf.d; na[e] = cf.a; nb[e] = cf.b; }      // (y / d is formed where the row is consumed: a product
-                                                                                        // here would wait for the loads BEFORE the scan they hide behind)
-      }
-    }
+  // what the recurrence starts from at the column slot e holds, element k of the vectors; `fresh`: the slot holds a row of the band
+  auto value = [&](int e, int k, bool fresh) __attribute__((always_inline)) {
+    T v = FWD ? nv[e] : nv[e] * nd[e];
+    if (fuse && fresh) { v = (nv[e] - sc.omega * n2[e]) * sc.beta + n3[e]; a.p[k] = v; }
+    return v;
   };
   auto stage_row = [&](int jj) __attribute__((always_inline)) {      // the row load_row(jj) asked for
     const int kb = a.kx(c, (FWD ? j0 + jj : j1 - 1 - jj) * W);
@@ -594,16 +497,16 @@ __global__ __launch_bounds__(kBlock) void bi_sweep_lds(BiArgs<T> a, const T* in,
     for (int e = 0; e < E; ++e) {
       const int i = e * kBlock + threadIdx.x;
       if (i < W) {
-        const int q = sweep_slot<E>(FWD ? i : W - 1 - i);
-        T v = FWD ? nv[e] : nv[e] * nd[e];
-        if (fuse && jj < j1 - j0) { v = (nv[e] - sc.omega * n2[e]) * sc.beta + n3[e]; a.p[kb + i] = v; }
-        bv[q] = v; ba[q] = na[e]; bb[q] = nb[e];
+        const int q = sweep_slot<E>(across(i));
+        bv[q] = value(e, kb + i, jj < j1 - j0); ba[q] = na[e]; bb[q] = nb[e];
       }
     }
   };
   load_row(0);
-  stage_row(0);
-  __syncthreads();
+  if constexpr (LDS) {
+    stage_row(0);
+    __syncthreads();
+  }
   for (int jj = 0; jj < j1 - j0; ++jj) {
     const int j = FWD ? j0 + jj : j1 - 1 - jj;
     const int kb = a.kx(c, j * W);
@@ -615,30 +518,34 @@ __global__ __launch_bounds__(kBlock) void bi_sweep_lds(BiArgs<T> a, const T* in,
       m[e] = 0; cst[e] = 0;
       if (s < W) {
         const int q = sweep_slot<E>(s);
-        cst[e] = bv[q] - bb[q] * prev[e];
-        m[e] = -ba[q];
+        const T v = LDS ? bv[q] : value(e, kb + across(s), true);
+        cst[e] = v - (LDS ? bb[q] : nb[e]) * prev[e];
+        m[e] = -(LDS ? ba[q] : na[e]);
         f = Affine<T>::then(f, Affine<T>{m[e], cst[e]});
       }
     }
     load_row(jj + 1);                             // (in flight during the scan below)
-    const Affine<T> pre = block_exclusive_scan(f, smem);      // (its barriers: every thread has read the staged row)
-    T yl = pre.c;
+    const Affine<T> pre = block_exclusive_scan(f, smem);      // (staged: its barriers - every thread has read the staged row)
+    T yl = pre.c;                                 // value just before my chunk (pre applied to 0; first m is 0 anyway)
 #pragma unroll
     for (int e = 0; e < E; ++e) {
       const int s = i0 + e;
       if (s < W) {
         const T y = fma(m[e], yl, cst[e]);
-        by[sweep_slot<E>(s)] = y;
+        if constexpr (LDS) by[sweep_slot<E>(s)] = y;
+        else out[kb + across(s)] = y;
         prev[e] = y;
         yl = y;
       }
     }
-    stage_row(jj + 1);
-    __syncthreads();
+    if constexpr (LDS) {
+      stage_row(jj + 1);
+      __syncthreads();                            // (row jj's y and row jj + 1 are in LDS)
 #pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const int i = e * kBlock + threadIdx.x;
-      if (i < W) out[kb + i] = by[sweep_slot<E>(FWD ? i : W - 1 - i)];
+      for (int e = 0; e < E; ++e) {
+        const int i = e * kBlock + threadIdx.x;
+        if (i < W) out[kb + i] = by[sweep_slot<E>(across(i))];
+      }
     }
   }
 }
@@ -998,9 +905,9 @@ static void launch_factor(const BiPlan& pl, const BiArgs<T>& a, hipStream_t s) {
   bi_with_E(pl.E, [&](auto e) {
     constexpr int E = decltype(e)::value;
     if constexpr (kSweepLds<T, E>) {
-      if (pl.factor_lds) { bi_factor_lds<T, E><<<gb, kBlock, 0, s>>>(a); return; }
+      if (pl.factor_lds) { bi_factor<T, E, true><<<gb, kBlock, 0, s>>>(a); return; }
     }
-    bi_factor<T, E><<<gb, kBlock, 0, s>>>(a);
+    bi_factor<T, E, false><<<gb, kBlock, 0, s>>>(a);
   });
 }
 template <typename T>
@@ -1010,13 +917,13 @@ static void launch_sweeps(const BiPlan& pl, const BiArgs<T>& aL, const BiArgs<T>
     constexpr int E = decltype(e)::value;
     if constexpr (kSweepLds<T, E>) {
       if (pl.sweep_lds) {
-        bi_sweep_lds<T, E, true><<<gb, kBlock, 0, s>>>(aL, in, aL.y);
-        bi_sweep_lds<T, E, false><<<gb, kBlock, 0, s>>>(aU, aU.y, out);
+        bi_sweep<T, E, true, true><<<gb, kBlock, 0, s>>>(aL, in, aL.y);
+        bi_sweep<T, E, false, true><<<gb, kBlock, 0, s>>>(aU, aU.y, out);
         return;
       }
     }
-    bi_sweep<T, E, true><<<gb, kBlock, 0, s>>>(aL, in, aL.y);
-    bi_sweep<T, E, false><<<gb, kBlock, 0, s>>>(aU, aU.y, out);
+    bi_sweep<T, E, true, false><<<gb, kBlock, 0, s>>>(aL, in, aL.y);
+    bi_sweep<T, E, false, false><<<gb, kBlock, 0, s>>>(aU, aU.y, out);
   });
 }
 

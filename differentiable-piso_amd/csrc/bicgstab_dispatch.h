@@ -1,6 +1,6 @@
 // Host side of the ILU(0)-BiCGStab's kernel choice (bicgstab.hip): the geometry of the two face arrays, the plan of a solve (bi_plan:
 // pure, no HIP calls - band height, row and band ranges, E, LDS forms, grids, first host look, folding, every shape it refuses),
-// WHICH (T, E) have bi_sweep_lds / bi_factor_lds instances (bi_lds_instance: the one statement of it) and the E ladder (bi_with_E: the
+// WHICH (T, E) have LDS-staged forms of bi_sweep / bi_factor (bi_lds_instance: the one statement of it) and the E ladder (bi_with_E: the
 // only place that spells it).  Plain C++: a host compiler can include this file and walk every plan without a card.
 #pragma once
 #include <stddef.h>
@@ -97,7 +97,7 @@ inline bool bi_with_E(int E, F&& f) {
   return false;
 }
 
-// ---- which (sizeof T, E) have bi_sweep_lds<T, E, FWD> / bi_factor_lds<T, E> instances: `rows` staged rows of E * 256 + E * 8 elements
+// ---- which (sizeof T, E) have bi_sweep<T, E, FWD, LDS = true> / bi_factor<T, E, LDS = true> instances: `rows` staged rows of E * 256 + E * 8 elements
 // in 96 KB.  The planner asks at run time, the launchers at compile time; nothing else states it.
 // (rows of up to 1 024 faces - E <= 4 - are no faster this way: 512^2 89.6 against 97.1 us per iteration, 1024^2 166.0 against 160.9)
 constexpr bool bi_lds_rows_fit(size_t elem, int E, int rows) { return (size_t)rows * (E * kBiBlock + E * 8) * elem <= (size_t)96 * 1024; }
@@ -110,7 +110,7 @@ constexpr bool bi_factor_fits_wherever_the_sweeps_do() {
       if (bi_lds_instance(elem, e) && !bi_lds_rows_fit(elem, e, 5)) return false;
   return true;
 }
-static_assert(bi_factor_fits_wherever_the_sweeps_do(), "bi_factor_lds stages five rows: an E whose sweeps fit and whose factorisation does not needs a predicate of its own");
+static_assert(bi_factor_fits_wherever_the_sweeps_do(), "the staged bi_factor holds five rows: an E whose sweeps fit and whose factorisation does not needs a predicate of its own");
 
 // ---- the plan: everything the driver needs to know before it binds a workspace, creates a stream or launches
 struct BiQuery {

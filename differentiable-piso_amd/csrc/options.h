@@ -31,7 +31,7 @@ enum Opt {
   OPT_CG_XCD_MAP,          // 1 (tests): keep the XCD of every workgroup of a solve's last chip-wide persistent launch for piso_cg_last_xcd_map
   OPT_CONV_LDS,            // 0: the closure's convolutions - forward / input gradient (CINP >= 16, KS >= 3) AND weight gradient (cin, cout multiples of 4; the 64 -> 64 kernel) - read their operands straight from L2 (default: staged through LDS)
   OPT_BICG_FOLD,           // 0: the BiCGStab scalar stages always run as launches of their own (default: folded into their consumers on one GPU)
-  OPT_BICG_SWEEP_LDS,      // 0: the triangular sweeps address memory in scan order (bi_sweep) instead of staging rows through LDS (bi_sweep_lds)
+  OPT_BICG_SWEEP_LDS,      // 0: the triangular sweeps address memory in scan order (bi_sweep<.., LDS = false>) instead of staging rows through LDS (LDS = true)
   OPT_BICG_FUSE_P,         // 0: the direction update of BiCGStab runs as a launch of its own (bi_update_p) instead of inside the forward sweep that reads it
   OPT_SLAB_FORCE,          // 1: a communicator of ONE rank still runs the slab code paths (ring of one: halo messages and sums to itself; tests)
   OPT_SLAB_HOP_TICKS,      // measurements only: the persistent slab kernel's cross-GPU records leave this many 10 ns ticks late (an emulated link latency)

@@ -147,9 +147,9 @@ int piso_multi_bicgstab_ilu_f64(const double* csr_val, const int* csr_rowptr, co
  * and changes nothing that is computed.  Fields, in this order:
  *    0 sizeof(T)        8 / 4
  *    1 E                row elements per thread of bi_factor / bi_sweep: the smallest of 1, 2, 3, 4, 5, 8, 9, 16, 32 with nx + 1 <= 256 E
- *    2 sweep_lds        1: the sweeps that stage rows through LDS ran (bi_sweep_lds: float E = 5, 8, 9, 16, double E = 5, 8, 9; option
+ *    2 sweep_lds        1: the sweeps that stage rows through LDS ran (bi_sweep<.., LDS = true>: float E = 5, 8, 9, 16, double E = 5, 8, 9; option
  *                       bicg_sweep_lds 0: never)
- *    3 factor_lds       1: likewise the factorisation (bi_factor_lds, the same instances)
+ *    3 factor_lds       1: likewise the factorisation (bi_factor<.., LDS = true>, the same instances)
  *    4 R                band height in face rows after the automatic choice and the clamp to ny + 1
  *    5 bands_u          bands (= workgroups of a sweep) of the u component this rank works on: ceil(ny / R) on one GPU
  *    6 bands_v          ... of the v component: ceil((ny + 1) / R) - a last band of one row when R divides ny

@@ -2,7 +2,7 @@
 
 One call of piso_multi_bicgstab_ilu_* picks (csrc/bicgstab_dispatch.h: bi_plan, the one place the driver bi_solve of csrc/bicgstab.hip decides in)
   E       row elements per thread of the factorisation and the sweeps, from need = ceil((nx + 1) / 256): 1, 2, 3, 4, 5, 8, 9, 16, 32
-  LDS     bi_sweep_lds / bi_factor_lds instead of bi_sweep / bi_factor where they exist (float E = 5, 8, 9, 16; double E = 5, 8, 9) and option
+  LDS     the LDS-staged forms of bi_sweep / bi_factor instead of the direct ones where they exist (float E = 5, 8, 9, 16; double E = 5, 8, 9) and option
           bicg_sweep_lds is not 0
   R       the band height: band_rows < 0 one band, 0 automatic (ny >= 2048: 8, >= 1024: 4, >= 256: 2, else 8), > 0 as given; clamped to ny + 1
   blocks  ceil(rows of the larger component / 1024) rounded up to 8, at most 1 024
@@ -44,7 +44,7 @@ f32, f64 = np.float32, np.float64
 CASES = ("periodic", "xper_ywall", "cavity", "spatial_ml")
 REGIME = {"easy": dict(cfl=0.5, viscosity=1e-2), "mid": dict(cfl=2.0, viscosity=0.1), "hard": dict(cfl=6.0, viscosity=0.5)}
 E_LADDER = (1, 2, 3, 4, 5, 8, 9, 16, 32)
-# (sizeof T, E) that have bi_sweep_lds / bi_factor_lds instances: bi_lds_instance - four (factor: five) staged rows of E * 256 + E * 8 elements in 96 KB
+# (sizeof T, E) that have LDS-staged bi_sweep / bi_factor instances: bi_lds_instance - four (factor: five) staged rows of E * 256 + E * 8 elements in 96 KB
 LDS_FORMS = {(4, 5), (4, 8), (4, 9), (4, 16), (8, 5), (8, 8), (8, 9)}
 K_DEFAULT = (1, 2, 3, 5, 7)           # 7: past the first doubling of the look cadence (looks after 2, 4, 6 / 1, 3, 5, 7 iterations)
 

@@ -391,18 +391,23 @@ def test_bicgstab_folded_scalar_stages_are_bitwise_neutral(name, shape, transpos
 
 
 _KERNEL_VARIANT_CASES = [("periodic", (40, 36), False, 1e-5, 200), ("cavity", (40, 36), True, 1e-30, 5), ("spatial_ml", (40, 36), False, 1e-30, 3),
-                         ("periodic", (64, 1300), False, 1e-6, 50), ("xper_ywall", (48, 1280), True, 1e-30, 4),      # rows of > 1 024 faces: bi_sweep_lds
-                         ("periodic", (16, 2304), False, 1e-30, 3)]                                                # E = 10 -> the 16-element instance (padded LDS slots)
-# (float64 has no LDS instance at E = 16 - four staged rows would need 132 KB - so the float64 leg of the last case compares bi_sweep with
-# itself under bicg_sweep_lds and is a real comparison for bicg_fuse_p only; float64's LDS forms are compared at 64 x 1300 and 48 x 1280,
-# E = 8, and every instance is held to the oracle in test_gpu_bicgstab_dispatch.py)
+                         ("periodic", (64, 1300), False, 1e-6, 50), ("xper_ywall", (48, 1280), True, 1e-30, 4),      # rows of > 1 024 faces: the LDS forms
+                         ("periodic", (16, 2304), False, 1e-30, 3),                                                # E = 10 -> the 16-element instance (padded LDS slots)
+                         ("periodic", (11, 1024), False, 1e-6, 50), ("xper_ywall", (9, 2048), True, 1e-6, 50),     # E = 5, E = 9 (transposed)
+                         ("periodic", (16, 2304), False, 1e-6, 50)]                                                # E = 16
+# (The cases with tol = 1e-30 fail both passes and return x = 0: they compare the iteration counts and the failure path, not solutions.
+# The REAL comparisons - a converged, non-zero x - are the tol >= 1e-6 cases: 40 x 36 (E = 1, no LDS form: bicg_fuse_p only), 64 x 1300
+# (E = 8), 11 x 1024 (E = 5), 9 x 2048 (E = 9) and 16 x 2304 (E = 16), i.e. all seven (T, E) LDS forms of the sweeps and the factorisation.
+# float64 has no LDS form at E = 16 - four staged rows would need 132 KB - so the float64 leg of 16 x 2304 compares the direct form with
+# itself under bicg_sweep_lds and is a real comparison for bicg_fuse_p only.  Every instance is held to the oracle in
+# test_gpu_bicgstab_dispatch.py.)
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 @pytest.mark.parametrize("name,shape,transpose,tol,max_it", _KERNEL_VARIANT_CASES)
 def test_bicgstab_kernel_variants_are_bitwise_neutral(name, shape, transpose, tol, max_it, dtype, piso_option):
     """Round 5's kernel variants change HOW memory is walked, not what is computed: the sweeps / the factorisation that stage rows through
-    LDS (bi_sweep_lds, bi_factor_lds; option bicg_sweep_lds) and the direction update inside the forward sweep (BiArgs::fuse_p; option
+    LDS (bi_sweep<.., LDS = true>, bi_factor<.., LDS = true>; option bicg_sweep_lds) and the direction update inside the forward sweep (BiArgs::fuse_p; option
     bicg_fuse_p) must give bitwise the solution and the iteration counts of the kernels they replace."""
     from diffpiso.solvers import multi_bicgstab_ilu_native
     ny, nx = shape
