@@ -173,6 +173,14 @@ lib.piso_conv2d_forward_any.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _
 lib.piso_conv2d_forward_any.restype = _i
 lib.piso_conv2d_wgrad_any.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]
 lib.piso_conv2d_wgrad_any.restype = _i
+lib.piso_conv_epilogue_plan.argtypes = [_i, _i, _ip, _ip]
+lib.piso_conv_epilogue_plan.restype = _i
+lib.piso_conv_epilogue_workspace_bytes.argtypes = [_i, _i]
+lib.piso_conv_epilogue_workspace_bytes.restype = _sz
+lib.piso_conv_epilogue_forward.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]
+lib.piso_conv_epilogue_forward.restype = _i
+lib.piso_conv_epilogue_backward.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]
+lib.piso_conv_epilogue_backward.restype = _i
 lib.piso_conv_last_geometry.argtypes = [_ip, _i]
 lib.piso_conv_last_geometry.restype = _i
 lib.piso_leaky_relu_backward.argtypes = [_vp, _vp, _vp, _sz, _vp]
@@ -368,6 +376,13 @@ def conv2d_instantiated(entry, ks, cin, cout):
     """Do the fixed instance tables serve (entry 1 forward | 2 weight gradient, ks, cin, cout)?  (include/piso_hip.h: piso_conv2d_instantiated;
     pure host code.)  False: the shape runs the run-time-shaped family of the *_any entries."""
     return bool(lib.piso_conv2d_instantiated(int(entry), int(ks), int(cin), int(cout)))
+
+
+def conv_epilogue_plan(pixels, channels):
+    """(bands, pixels_per_band) of the bias sum of piso_conv_epilogue_backward (include/piso_hip.h: piso_conv_epilogue_plan; pure host code)."""
+    bands, ppb = C.c_int(0), C.c_int(0)
+    check(lib.piso_conv_epilogue_plan(int(pixels), int(channels), C.byref(bands), C.byref(ppb)), "piso_conv_epilogue_plan")
+    return bands.value, ppb.value
 
 
 CONV_GEOMETRY_FIELDS = ("pad_y", "pad_x", "wrap_y", "wrap_x")

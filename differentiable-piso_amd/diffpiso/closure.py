@@ -6,7 +6,8 @@ network output (2 channels at cell centres) resampled to the faces as the forcin
 On the GPU the convolutions run on hand-written MFMA kernels (csrc/conv.hip: exact fp32 v_mfma_f32_16x16x4_f32, NHWC, fused
 leaky ReLU, forward / input gradient / weight gradient) behind `conv2d_leaky`: the tuned, fixed instances for the shapes of the
 reference's network, the run-time-shaped family of csrc/conv_any.hip for every other odd kernel size up to 9 and channel counts up
-to 256 (`FullyConvNetwork(layers=...)`).  A device tensor the kernels cannot serve raises - nothing on the GPU ever goes to another
+to 256 (`FullyConvNetwork(layers=...)`).  Bias, skip connections and ReLU (`conv2d_act`, `FullyConvNetwork(bias=, activation=, skips=)`) are one fused
+pass per direction behind the convolution (csrc/conv_epilogue.hip).  A device tensor the kernels cannot serve raises - nothing on the GPU ever goes to another
 convolution library.  HOST tensors (the CPU tests of the network's shape logic, the
 oracle chain of the GPU tests, the offline fixture generator) go through torch's CPU conv2d.
 The field-algebra pieces (at_centers, gradient, centre -> face resampling) are pinned by tests/golden (PhiFlow numpy backend).
@@ -218,6 +219,83 @@ def conv2d_leaky(x_nhwc, w_oihw, pad, leaky, wrap=(False, False)):
     return y.permute(0, 2, 3, 1)
 
 
+_ACTIVATIONS = {None: 0, "leaky_relu": 1, "relu": 2}                  # the `act` codes of piso_conv_epilogue_* (include/piso_hip.h)
+
+
+class _ConvEpilogue(torch.autograd.Function):
+    """y = act((z + bias) + skip) behind a convolution that ran with leaky=False: piso_conv_epilogue_forward, one pass.  Reverse mode:
+    piso_conv_epilogue_backward, one pass - g' = g act'(y) from the saved OUTPUT (saved only where there is an activation) and, in the same
+    pass, d bias = sum over pixels of g' (banded, deterministic; workspace "conv_epilogue").  g' is the cotangent of z and of skip alike."""
+
+    @staticmethod
+    def forward(ctx, z, bias, skip, act):
+        from . import _native as N
+        z = z.contiguous()
+        skip = None if skip is None else skip.contiguous()
+        _, Ho, Wo, cout = z.shape
+        y = torch.empty_like(z)
+        N.check(N.lib.piso_conv_epilogue_forward(N.ptr(z), N.ptr(bias), N.ptr(skip), N.ptr(y), Ho * Wo, cout, act, N.stream_ptr()), "piso_conv_epilogue_forward")
+        ctx.save_for_backward(y if act else None)
+        ctx.act = act
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        import ctypes as C
+        from . import _native as N
+        y, = ctx.saved_tensors
+        act = ctx.act
+        g = g.contiguous()
+        _, Ho, Wo, cout = g.shape
+        gpre = torch.empty_like(g) if act else None
+        dbias = ws = None
+        if ctx.needs_input_grad[1]:
+            dbias = torch.empty(cout, dtype=torch.float32, device=g.device)
+            ws = N.workspace(N.lib.piso_conv_epilogue_workspace_bytes(Ho * Wo, cout), g.device, "conv_epilogue")
+        N.check(N.lib.piso_conv_epilogue_backward(N.ptr(g), N.ptr(y), N.ptr(gpre), N.ptr(dbias), Ho * Wo, cout, act, N.ptr(ws),
+                                                  C.c_size_t(0 if ws is None else ws.numel() // 4), N.stream_ptr()), "piso_conv_epilogue_backward")
+        if not act:
+            gpre = g
+        return gpre, dbias, gpre if ctx.needs_input_grad[2] else None, None
+
+
+def conv2d_act(x_nhwc, w_oihw, pad, activation="leaky_relu", bias=None, skip=None, wrap=(False, False)):
+    """One layer of a closure network: act((conv2d(x, w) + bias) + skip), NHWC; activation "leaky_relu" (slope 0.2), "relu" or None, bias [cout] or
+    None, skip of the output's shape or None.  pad, wrap: conv2d_leaky's.
+    With no bias, no skip and no ReLU this IS the conv2d_leaky call (the activation fused in the convolution kernel).  Otherwise, on device tensors,
+    the convolution runs without an activation through whichever kernel its shape is routed to (_routes) and ONE fused pass applies the rest
+    (csrc/conv_epilogue.hip), one pass in reverse mode too; a bias that is not a float32 [cout] device tensor, or a skip that is not a float32
+    device tensor of the output's shape, raises.  Host tensors of any dtype: the same torch ops in the same order."""
+    if activation not in _ACTIVATIONS:
+        raise ValueError("conv2d_act: activation is 'leaky_relu', 'relu' or None (got %r)" % (activation,))
+    # (the call FullyConvNetwork.forward always made, argument for argument: `wrap` is passed only where an axis wraps - whatever stands in for
+    # conv2d_leaky, such as the torch checker of the tests with its four parameters, sees what it saw)
+    kw = dict(wrap=wrap) if any(_wrap2(wrap)) else {}
+    if bias is None and skip is None and activation != "relu":
+        return conv2d_leaky(x_nhwc, w_oihw, pad, leaky=activation == "leaky_relu", **kw)
+    z = conv2d_leaky(x_nhwc, w_oihw, pad, leaky=False, **kw)
+    if z.is_cuda:
+        cout = w_oihw.shape[0]
+        if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32 and tuple(bias.shape) == (cout,)):
+            from ._native import PisoNativeError
+            raise PisoNativeError("conv2d_act: the epilogue kernels take the bias as a float32 device tensor of shape [%d] (got %s %s on %s)"
+                                  % (cout, tuple(bias.shape), bias.dtype, bias.device))
+        if skip is not None and not (skip.is_cuda and skip.dtype == torch.float32 and skip.shape == z.shape):
+            from ._native import PisoNativeError
+            raise PisoNativeError("conv2d_act: the epilogue kernels take the skip operand as a float32 device tensor of the output's shape %s (got %s %s on %s)"
+                                  % (tuple(z.shape), tuple(skip.shape), skip.dtype, skip.device))
+        return _ConvEpilogue.apply(z, bias, skip, _ACTIVATIONS[activation])
+    if bias is not None:
+        z = z + bias
+    if skip is not None:
+        z = z + skip
+    if activation == "leaky_relu":
+        z = F.leaky_relu(z, 0.2)
+    elif activation == "relu":
+        z = F.relu(z)
+    return z
+
+
 _KERNELS = [(7, 4, 16), (5, 16, 16), (5, 16, 32), (3, 32, 64), (3, 64, 64), (1, 64, 64), (1, 64, 2)]   # networks.py:62-69
 
 
@@ -231,10 +309,16 @@ class FullyConvNetwork(torch.nn.Module):
     wrap = (wrap_y, wrap_x): the periodic axes of the domain.  A wrapped axis keeps its extent in every layer (pad k // 2, wrap-around),
     whatever `padding` says: `padding="VALID"` shrinks - and `restore_shape` pads back - only the other axis.  A non-zero `buffer_width`
     on a wrapped axis is refused: a cropped axis has no seam.  A periodic simulation wants the network and its coupling
-    (centered_to_staggered / make_forcing_fn) wrapped on the same axes."""
+    (centered_to_staggered / make_forcing_fn) wrapped on the same axes.
+    bias: a bool, or one bool per layer - those layers add a bias [cout] (self.biases, in layer order; zero at construction, no random draw: a seeded
+    network has the weights it has without them; the ParameterList is empty when no layer has one).
+    activation: "leaky_relu" (the reference's), "relu" or None, after all but the last layer.
+    skips: {j: i}, 0 <= i <= j - the pre-activation of layer j adds the INPUT of layer i (i = 0: the network input after the buffer_width crop), a
+    residual connection; cin_i must equal cout_j and every layer i .. j must keep its extent (padding "SAME", or k == 1, or the axis wrapped).
+    A skip adds no receptive field: reduced_buffer_width is the same.  Every layer is one conv2d_act call."""
 
     def __init__(self, buffer_width=None, padding="SAME", restore_shape=False, in_channels=None, seed=None, initialiser=None, wrap=(False, False),
-                 layers=None):
+                 layers=None, bias=False, activation="leaky_relu", skips=None):
         super().__init__()
         if layers is None:
             layers, in_channels = _KERNELS, 4 if in_channels is None else in_channels
@@ -250,6 +334,24 @@ class FullyConvNetwork(torch.nn.Module):
                 raise ValueError("FullyConvNetwork: layer %d takes %d channels, layer %d gives %d" % (i, cin, i - 1, layers[i - 1][2]))
         self.layers = layers
         self.wrap = _wrap2(wrap)
+        if activation not in _ACTIVATIONS:
+            raise ValueError("FullyConvNetwork: activation is 'leaky_relu', 'relu' or None (got %r)" % (activation,))
+        self.activation = activation
+        has_bias = [bool(bias)] * len(layers) if isinstance(bias, (bool, int, np.bool_)) else [bool(b) for b in bias]
+        if len(has_bias) != len(layers):
+            raise ValueError("FullyConvNetwork: bias is a bool or one bool per layer (%d layers, got %d)" % (len(layers), len(has_bias)))
+        self.skips = {}
+        for j, i in (skips or {}).items():
+            i, j = int(i), int(j)
+            if not 0 <= i <= j < len(layers):
+                raise ValueError("FullyConvNetwork: skips = {j: i} with 0 <= i <= j < %d layers (got {%d: %d})" % (len(layers), j, i))
+            if layers[i][1] != layers[j][2]:
+                raise ValueError("FullyConvNetwork: skip {%d: %d}: layer %d takes %d channels, layer %d gives %d" % (j, i, i, layers[i][1], j, layers[j][2]))
+            for m in range(i, j + 1):
+                if not (padding == "SAME" or layers[m][0] == 1 or (self.wrap[0] and self.wrap[1])):
+                    raise ValueError("FullyConvNetwork: skip {%d: %d}: layer %d (k = %d) shrinks its input with padding %r on an axis that is not wrapped: "
+                                     "the skip's operands would differ in extent" % (j, i, m, layers[m][0], padding))
+            self.skips[j] = i
         if buffer_width is not None:
             for axis, name in ((0, "y"), (1, "x")):
                 if self.wrap[axis] and any(int(b) != 0 for b in buffer_width[axis]):
@@ -271,6 +373,12 @@ class FullyConvNetwork(torch.nn.Module):
             else:
                 raise ValueError("initialiser: None / 'glorot_normal' (tf.glorot_normal_initializer, the reference's default) or 'normal'")
             self.weights.append(torch.nn.Parameter(w))
+        self.biases = torch.nn.ParameterList()
+        self.bias_of_layer = []                                # layer -> its index in self.biases, or None
+        for (_, _, cout), has in zip(layers, has_bias):
+            self.bias_of_layer.append(len(self.biases) if has else None)
+            if has:
+                self.biases.append(torch.nn.Parameter(torch.zeros(cout)))
         self.buffer_width = buffer_width
         self.padding = padding
         self.restore_shape = restore_shape
@@ -290,12 +398,18 @@ class FullyConvNetwork(torch.nn.Module):
         same = self.padding == "SAME"
         call_wrap = self.wrap if wrap is None else _wrap2(wrap)
         wrap_y, wrap_x = call_wrap
+        inputs = {i: None for i in self.skips.values()}        # the layer inputs a later layer adds
         for i, w in enumerate(self.weights):
             k = w.shape[-1]
+            if i in inputs:
+                inputs[i] = x
+            act = self.activation if i < len(self.weights) - 1 else None
+            b = None if self.bias_of_layer[i] is None else self.biases[self.bias_of_layer[i]]
+            s = inputs[self.skips[i]] if i in self.skips else None
             if not (wrap_y or wrap_x):
-                x = conv2d_leaky(x, w, k // 2 if same else 0, leaky=i < len(self.weights) - 1)
+                x = conv2d_act(x, w, k // 2 if same else 0, act, b, s)
             else:
-                x = conv2d_leaky(x, w, (k // 2 if same or wrap_y else 0, k // 2 if same or wrap_x else 0), leaky=i < len(self.weights) - 1, wrap=call_wrap)
+                x = conv2d_act(x, w, (k // 2 if same or wrap_y else 0, k // 2 if same or wrap_x else 0), act, b, s, wrap=call_wrap)
         out = x
         if not same and bw is not None and self.restore_shape:
             pn = self.reduced_buffer_width
@@ -306,13 +420,17 @@ class FullyConvNetwork(torch.nn.Module):
         return out
 
 
-def initialise_fullyconv_network(buffer_width, padding="SAME", restore_shape=False, initialiser=None, seed=None, wrap=(False, False), layers=None):
-    """networks.py:59-77 -> (callable, weights, reduced_buffer_width).  wrap: the periodic axes; layers: a list of (k, cin, cout) (FullyConvNetwork)."""
-    net = FullyConvNetwork(buffer_width, padding, restore_shape, seed=seed, initialiser=initialiser, wrap=wrap, layers=layers)
+def initialise_fullyconv_network(buffer_width, padding="SAME", restore_shape=False, initialiser=None, seed=None, wrap=(False, False), layers=None,
+                                 bias=False, activation="leaky_relu", skips=None):
+    """networks.py:59-77 -> (callable, weights, reduced_buffer_width).  wrap: the periodic axes; layers: a list of (k, cin, cout); bias, activation,
+    skips: FullyConvNetwork's.  The second value is every trainable tensor - the weights, then the biases (none by default): what training_run
+    optimises, checkpoints, checks for finite gradients and sums across ranks."""
+    net = FullyConvNetwork(buffer_width, padding, restore_shape, seed=seed, initialiser=initialiser, wrap=wrap, layers=layers, bias=bias,
+                           activation=activation, skips=skips)
     rbw = net.reduced_buffer_width
     if buffer_width is not None:
         rbw = [[i + rbw for i in j] for j in buffer_width]
-    return net, list(net.weights), rbw
+    return net, list(net.weights) + list(net.biases), rbw
 
 
 def centered_gradient(field):

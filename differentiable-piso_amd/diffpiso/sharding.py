@@ -611,6 +611,10 @@ def make_slab_forcing_fn(network, sharding, pressure_included=True, wrap=None, w
     (garbage activations are finite - sums of whole-grid data and zeros - and meet exact zeros).  Each rank ends with the part of d nn_in
     that belongs to its owned outputs, on owned + R rows; the reverse exchange adds the parts across the cuts (one more rounding than on
     one GPU).  Weight gradients: the part that belongs to the rank's owned outputs - StepSharding.allreduce_gradients sums them.
+    A network with biases, skip connections or another activation (FullyConvNetwork(bias=, skips=, activation=)) changes none of this: the
+    epilogue of a layer is element-wise, a skip adds no receptive field and the halo width is the same R.  The bias gradient of a rank is
+    the sum over its extended rows of the layer's pre-activation cotangent, which is exactly zero wherever the saved activations are
+    invalid (above) - the part of the rank's owned outputs; allreduce_gradients over weights and biases gives the whole gradient.
     wrap = (wrap_y, wrap_x) of the resampling (None: edges replicated).  wrap_y must equal the network's: on a y-periodic domain the ring
     halo IS the wrap of both.  wrapper(network, nn_in_ext): the network it is handed runs with (False, wrap_x) unless told otherwise.
     Refused before any launch: VALID padding, a y buffer_width, a network without reduced_buffer_width, slabs thinner than E rows."""

@@ -638,6 +638,32 @@ int piso_conv2d_forward_any(const float* in, const float* w_laid_out, float* out
 int piso_conv2d_wgrad_any(const float* in, const float* grad_out, float* dw, int H, int W, int cin, int cout, int ks, int pad_y, int pad_x,
                           int wrap_y, int wrap_x, void* workspace, size_t workspace_bytes, piso_stream_t stream);
 
+/* The EPILOGUE of a closure layer (csrc/conv_epilogue.hip): bias, skip connection and activation, one pass per direction behind whichever
+ * convolution entry above served the layer (called with leaky_out = 0).  Layout: NHWC [pixels][channels] float32, pixels = Ho Wo, bias [channels].
+ * act: 0 none, 1 leaky ReLU (slope 0.2: v > 0 ? v : 0.2f v), 2 ReLU (v > 0 ? v : 0).
+ *   piso_conv_epilogue_forward:  y[p][c] = act((z[p][c] + bias[c]) + skip[p][c]), fp32, in that order.  bias and skip may each be NULL; y may be z
+ *     (in place); skip must not be y.
+ *   piso_conv_epilogue_backward: gpre[p][c] = g[p][c] act'(y[p][c]) from the saved OUTPUT y (leaky: y > 0 ? g : 0.2f g; ReLU: y > 0 ? g : 0).  act == 0:
+ *     gpre IS g - y and gpre may be NULL and nothing is written to gpre.  dbias non-NULL: dbias[c] = sum over pixels of gpre[p][c], in the same pass
+ *     (g is read once).  The cotangent of skip is gpre itself: no kernel and no copy.
+ *   Summation order of dbias (deterministic, no atomics): the pixels are cut into `bands` bands of `pixels_per_band` consecutive pixels
+ *     (piso_conv_epilogue_plan: pixels_per_band = max(ceil(4096 / channels), ceil(pixels / 1024)), bands = ceil(pixels / pixels_per_band) - a function
+ *     of (pixels, channels) alone, never of the card or the launch).  A workgroup adds one band: thread (row, column) the pixels row, row + rows, ...
+ *     of its band in index order (rows = 256 / columns; columns = channels, or channels / 4 in the 16-byte form), then the rows of a column in a
+ *     fixed tree, and stores ws[band][channels].  A second kernel adds the bands of a channel: band r, r + 64, ... per thread in index order,
+ *     then the 64 partial sums in a fixed tree.  The same call gives the same bits on every run and card.
+ *   workspace: piso_conv_epilogue_workspace_bytes(pixels, channels) = min(ceil(pixels / ceil(4096 / channels)), 1024) x channels x 4 bytes - bands x
+ *     channels x 4 up to 1024 bands, its upper bound beyond (monotone in pixels); ws_elems counts floats.  Needed with dbias only.
+ *   Access form: 16 bytes per lane where channels % 4 == 0 and every pointer given is 16-byte aligned, else guarded 4-byte accesses with NO
+ *     alignment rule; y and gpre are the same bits in both (a dbias may differ in its last bits between the two forms).
+ * Refused with PISO_ERR_INVALID_ARG before any launch, the message naming the rule, and nothing written: z / y / g NULL; channels outside 1 .. 256;
+ * pixels < 1; act outside 0 .. 2; y or gpre NULL with act != 0; ws NULL or ws_elems < bands x channels with dbias given; skip == y. */
+int piso_conv_epilogue_plan(int pixels, int channels, int* bands, int* pixels_per_band);
+size_t piso_conv_epilogue_workspace_bytes(int pixels, int channels);
+int piso_conv_epilogue_forward(const float* z, const float* bias, const float* skip, float* y, int pixels, int channels, int act, piso_stream_t stream);
+int piso_conv_epilogue_backward(const float* g, const float* y, float* gpre, float* dbias, int pixels, int channels, int act, float* ws, size_t ws_elems,
+                                piso_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Slab-decomposed pressure CG (no counterpart in the reference, which is single-GPU).
  * The grid is cut along y into `world` slabs of ny_local rows, one rank (process) per GPU.  Two transports:
