@@ -32,9 +32,12 @@
 // beta and the sums stay on the device; the host queues check_every iterations, then reads the state through a pinned word; kernels of
 // iterations queued after convergence see the device flag and return at once, so neither x nor the count depends on the cadence.
 //
+// Kernels: what looks at a cell's neighbours is one template text over the geometry (whole grid, a rank's slab) and the type of the cycle's
+// values (mg_cells.h; four cells per thread: mg_quads.h); the pointwise kernels and the sums are here.
 // Host: one driver over the type of the cycle's values (mg_grid.h: set-up, V-cycle, PCG iteration, single cycle, the ordinary entries).
-// Opt-in: the same iteration around a float32 cycle (mg_f32.h, piso_mg_*_c32_f64); this file's kernels are its fp64 outer iteration.
+// Opt-in: the same iteration around a float32 cycle (mg_f32.h, piso_mg_*_c32_f64): the float instantiations, under the same fp64 outer iteration.
 // Opt-in: a start from a guess x0 instead of x = 0 where its residual is below the right-hand side (mg_guess.h, piso_mg_*_guess_*).
+#include <type_traits>
 #include <vector>
 
 #include "mg_prepared_carve.h"
@@ -82,7 +85,7 @@ __device__ __forceinline__ Nb neighbours(int c, int i, int j, int nx, int ny) {
   return q;
 }
 // summation order of the reference stencil: S, W, C, E, N (T: double, or float in the float32 cycle of mg_f32.h)
-// `cf(s)` is the cell's coefficient s: read from the level's arrays (stencil), or from the registers of a four-cell thread (mg_f32.h)
+// `cf(s)` is the cell's coefficient s: read from the level's arrays (stencil), or from the registers of a four-cell thread (mg_quads.h)
 template <typename T, typename CF>
 __device__ __forceinline__ T stencil_sum(CF cf, T vs, T vw, T vc, T ve, T vn) {
   T t = cf(0) * vs;
@@ -136,28 +139,13 @@ __device__ __forceinline__ double mg_sum_partials(const double* part, int count,
   return mg_block_sum(s, smem);
 }
 
-// ---- the per-cell code that looks at neighbours, for the whole grid (mg_cells.inc; mg_slab.h includes it again for a rank's slab) -----------
-#define MG_N(name) name
-#define MG_REAL double
-#define MG_LV Lv
-#define MG_RDOT_PARAM
-#define MG_RDOT_ARG(rd)
-#define MG_RDOT(rc, zo, c) rc * zo
-#define MG_R32_PARAM
-#define MG_R32_STORE(c, v)
-#define MG_WHOLE_GRID
-#define MG_GEO_PARAM
-#define MG_NB(c, i, j, nx, ny) neighbours(c, i, j, nx, ny)
-#define MG_JS(j, ny) j > 0 ? j - 1 : ny - 1
-#define MG_JN(j, ny) j < ny - 1 ? j + 1 : 0
-#define MG_EROW(j) (j >> 1)
-#define MG_FIRST_ROW(j) j == 0
-#define MG_LAST_ROW(j, ny) j == ny - 1
-#define MG_DIAG(Lin, idx) Lin[(size_t)idx * 5 + 2]
-#define MG_NCELLS(L) (double)L.n
-#define MG_DIRECTION_HALO_ROWS
-#include "mg_cells.inc"
-#include "mg_cells_undef.inc"
+}  // namespace piso
+
+// the per-cell code that looks at neighbours, over the geometry and the type of the cycle's values; the four-cell kernels of the float32 cycle
+#include "mg_cells.h"
+#include "mg_quads.h"
+
+namespace piso {
 
 // ---- hierarchy ------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void mg_setup_fin(const double* parts, int count, double* scal, int rank_deficient, int ncells, MgState* st) {
@@ -175,21 +163,26 @@ __global__ __launch_bounds__(kBlock) void mg_setup_fin(const double* parts, int 
     (void)ncells;
   }
 }
-// (mg_export, the per-level cycle kernels mg_pre1 / mg_pre2 / mg_jacobi / mg_restrict and the one-workgroup tail mg_tail: mg_cells.inc, MG_WHOLE_GRID)
-
 // ---- outer iteration ------------------------------------------------------------------------------------------------------------------
+// (R: the type of the cycle's values.  Under the float32 cycle rc = fl32(r) is written beside r; the fp64 cycle reads r itself and rc is not touched)
 // r = b' on the present cells (b' = b - mean over the present cells where rank deficient), 0 elsewhere; x = 0
-__global__ __launch_bounds__(kBlock) void mg_init(Lv L, const double* __restrict__ b, double* __restrict__ x, double* __restrict__ r, const double* scal) {
+template <typename R>
+__global__ __launch_bounds__(kBlock) void mg_init(Lv L, const double* __restrict__ b, double* __restrict__ x, double* __restrict__ r, const double* scal,
+                                                  R* __restrict__ rc) {
   const double mean = scal[SC_MEAN_B];
   const Walk w = grid_walk();
   for (int c = w.begin; c < L.n; c += w.step) {
     x[c] = 0;
-    r[c] = L.dinv[c] != 0 ? b[c] - mean : 0.0;
+    const double rv = L.dinv[c] != 0 ? b[c] - mean : 0.0;
+    r[c] = rv;
+    if constexpr (std::is_same<R, float>::value) rc[c] = (float)rv;
   }
 }
 // x += alpha p, r -= alpha q, partials of max|r|
+template <typename R>
 __global__ __launch_bounds__(kBlock) void mg_update(int n, double* __restrict__ x, double* __restrict__ r, const double* __restrict__ p, const double* __restrict__ q,
-                                                    const double* scal, int k, const double* part_pq, int n_pq, double* part_max, const MgState* st) {
+                                                    const double* scal, int k, const double* part_pq, int n_pq, double* part_max, const MgState* st,
+                                                    R* __restrict__ rc) {
   if (st->done) return;
   __shared__ double smem[16];
   const double pq = mg_sum_partials(part_pq, n_pq, smem);
@@ -199,9 +192,10 @@ __global__ __launch_bounds__(kBlock) void mg_update(int n, double* __restrict__ 
   const Walk w = grid_walk();
   for (int c = w.begin; c < n; c += w.step) {
     x[c] += alpha * p[c];
-    const double rc = r[c] - alpha * q[c];
-    r[c] = rc;
-    m = nanmax(m, fabs(rc));
+    const double rv = r[c] - alpha * q[c];
+    r[c] = rv;
+    if constexpr (std::is_same<R, float>::value) rc[c] = (float)rv;
+    m = nanmax(m, fabs(rv));
   }
   m = mg_block_max_nan(m, smem);
   if (threadIdx.x == 0) part_max[blockIdx.x] = m;
@@ -259,7 +253,7 @@ static int mg_pinned(MgState** out) {
 static int mg_build_begin(const Lv& L0, const double* laplace, const double* b, int rank_deficient, double* parts, double* scal, MgState* st, hipStream_t stream) {
   PISO_HIP_CHECK(hipMemsetAsync(st, 0, sizeof(MgState), stream));
   const int g0 = mg_grid(L0.n);
-  mg_setup0<<<g0, kBlock, 0, stream>>>(laplace, L0, b, parts, st);
+  mg_setup0<GeoWhole><<<g0, kBlock, 0, stream>>>(laplace, L0, b, parts, st, GeoWhole{});
   mg_setup_fin<<<1, kBlock, 0, stream>>>(parts, g0, scal, rank_deficient, L0.n, st);
   return PISO_OK;
 }
@@ -297,9 +291,9 @@ static int mg_iteration_args(const char* who, int max_iterations, int residual_r
 
 }  // namespace piso
 
-#include "mg_f32.h"
 #include "mg_guess.h"
 #include "mg_grid.h"
+#include "mg_f32.h"
 #include "mg_slab.h"
 #include "mg_slab_f32.h"
 #include "mg_prepared.h"
@@ -410,7 +404,7 @@ static int mg_slab_level(MgSlabT<C>& M, int q, int level, int* nx_out, int* rows
   *nx_out = M.sp.d.nx[level]; *rows_out = M.sp.rows[level];
   if (!out) return PISO_OK;
   PISO_TRY(M.build(0));
-  MgSlabOps<C>::export_level(M.R[q].lv[level], out, M.s);
+  MgGridOps<C>::export_level(M.R[q].lv[level], out, M.s);
   return M.finish(who);
 }
 template <typename C>

@@ -1,122 +1,99 @@
-// The one-GPU host driver of the multigrid PCG (part of mg.hip's translation unit, after its kernels and those of mg_f32.h and mg_guess.h):
-// ONE text over the type C of the cycle's values, as the slab driver MgSlabT<C> of mg_slab.h has it.  MgGridOps<C> holds what differs by
-// type - the launches of the cycle's kernels, the mixed outer kernels that write fl32(r) beside r, how one cycle reads r and writes z,
-// the element size of the dispatch record; MgGridT<C> holds the set-up, the first sweeps, the V-cycle, the PCG iteration and the single
-// cycle on an MgPlanT<C> (mg_prepared_carve.h), whoever filled it: the ordinary entries from one workspace (below), the prepared entries
-// from their two buffers (mg_prepared.h), the slab driver as a view of a rank's replicated levels (mg_slab.h).
+// The one-GPU host driver of the multigrid PCG (part of mg.hip's translation unit, after its kernels and those of mg_guess.h): ONE text over
+// the type C of the cycle's values, as the slab driver MgSlabT<C> of mg_slab.h has it.  MgGridOps<C> names the kernels the driver launches,
+// kernel<GeoWhole, C>; its four members that differ by type - how level 0 of the cycle comes out of the fp64 set-up, how one cycle reads r
+// and writes z - are specialised (double: below; float: mg_f32.h).  MgGridT<C> holds the set-up, the first sweeps, the V-cycle, the PCG
+// iteration and the single cycle on an MgPlanT<C> (mg_prepared_carve.h), whoever filled it: the ordinary entries from one workspace
+// (below), the prepared entries from their two buffers (mg_prepared.h), the slab driver as a view of a rank's replicated levels (mg_slab.h).
 #pragma once
 
 namespace piso {
 
-// ---- what the driver launches, by the type of the cycle's values ---------------------------------------------------------------------------
-// (x4: the level runs the four-cell kernels; rd: the outer residual in double, the other factor of (r, z) - NULL: no partials; r32: fl32(r))
-template <typename C> struct MgGridOps;
-template <>
-struct MgGridOps<double> {
-  typedef MgTail Tail;
-  static bool quads(const Lv&) { return false; }
-  static void pre1(const Lv& L, const double* r, double* z, const MgState* st, hipStream_t s) { mg_pre1<<<mg_grid(L.n), kBlock, 0, s>>>(L, r, z, st); }
-  static void pre2(const Lv& L, const double* r, double* z, const MgState* st, bool, hipStream_t s) { mg_pre2<<<mg_grid(L.n), kBlock, 0, s>>>(L, r, z, st); }
-  // one sweep; returns the number of (r, z) partials it left (part_rz given)
-  static int jacobi(const Lv& L, const double* r, const double* zin, double* zout, const double* e, int nxc, double* part_rz, const MgState* st, bool,
-                    const double*, hipStream_t s) {
-    const int g = mg_grid(L.n);
-    mg_jacobi<<<g, kBlock, 0, s>>>(L, r, zin, zout, e, nxc, part_rz, st);
-    return g;
+// ---- the launches of a level's cycle kernels that have a four-cell form, over the geometry G and the type C of the cycle's values ----------
+// x4: the level runs the four-cell kernels of mg_quads.h (float only, nx % 4 == 0; the grid counts quads then).  rd: the outer residual in
+// double, the float32 cycle's other factor of (r, z), given exactly where part_rz is - NULL: no partials.
+template <typename C>
+static bool mg_has_quads(const LvOf<C>& L) { return std::is_same<C, float>::value && (L.nx & 3) == 0; }
+template <typename G, typename C>
+static void mg_launch_pre2(const LvOf<C>& L, const C* r, C* z, const MgState* st, bool x4, const G& g, hipStream_t s) {
+  if constexpr (std::is_same<C, float>::value) {
+    if (x4) { mg_pre2_x4<G><<<mg_grid((L.nx >> 2) * L.ny), kBlock, 0, s>>>(L, r, z, st, g); return; }
   }
-  static void restrict_to(const Lv& L, const double* r, const double* z, double* rc, const Lv& Cc, const MgState* st, bool, hipStream_t s) {
-    mg_restrict<<<mg_grid(Cc.n), kBlock, 0, s>>>(L, r, z, rc, Cc.nx, Cc.ny, st);
+  mg_pre2<G, C><<<mg_grid(L.n), kBlock, 0, s>>>(L, r, z, st, g);
+}
+// one sweep; returns the number of (r, z) partials it left (part_rz given)
+template <typename G, typename C>
+static int mg_launch_jacobi(const LvOf<C>& L, const C* r, const C* zin, C* zout, const C* e, int nxc, double* part_rz, const MgState* st, bool x4, const double* rd,
+                            const G& g, hipStream_t s) {
+  const int gl = x4 ? mg_grid((L.nx >> 2) * L.ny) : mg_grid(L.n);
+  if constexpr (std::is_same<C, float>::value) {
+    if (x4) {
+      if (e && rd) mg_jacobi_x4<G, true, true><<<gl, kBlock, 0, s>>>(L, r, zin, zout, e, nxc, part_rz, st, rd, g);
+      else if (e) mg_jacobi_x4<G, true, false><<<gl, kBlock, 0, s>>>(L, r, zin, zout, e, nxc, part_rz, st, rd, g);
+      else if (rd) mg_jacobi_x4<G, false, true><<<gl, kBlock, 0, s>>>(L, r, zin, zout, e, nxc, part_rz, st, rd, g);
+      else mg_jacobi_x4<G, false, false><<<gl, kBlock, 0, s>>>(L, r, zin, zout, e, nxc, part_rz, st, rd, g);
+      return gl;
+    }
   }
-  static void tail(const Tail& T, const double* r, double* z, double* part_rz, int nu, const MgState* st, const double*, hipStream_t s) {
-    mg_tail<<<1, kTailThreads, 0, s>>>(T, r, z, part_rz, nu, st);
+  mg_jacobi<G, C><<<gl, kBlock, 0, s>>>(L, r, zin, zout, e, nxc, part_rz, st, rd, g);
+  return gl;
+}
+template <typename G, typename C>
+static void mg_launch_restrict(const LvOf<C>& L, const C* r, const C* z, C* rc, int nxc, int nyc, const MgState* st, bool x4, const G& g, hipStream_t s) {
+  if constexpr (std::is_same<C, float>::value) {
+    if (x4) { mg_restrict_x4<G><<<mg_grid((L.nx >> 2) * nyc), kBlock, 0, s>>>(L, r, z, rc, nxc, nyc, st, g); return; }
   }
-  static void level0(const Lv&, const Lv&, hipStream_t) {}                                  // (the fp64 set-up writes lv[0] itself)
-  static void coarsen(const Lv& F, const Lv& Cc, hipStream_t s) { mg_coarsen<<<mg_grid(Cc.n), kBlock, 0, s>>>(F, Cc); }
-  static void export_level(const Lv& L, double* out, hipStream_t s) { mg_export<<<mg_grid(L.n), kBlock, 0, s>>>(L, out); }
-  // the outer iteration (r32 is r itself here)
-  static void init(const Lv& L0, const double* b, double* x, double* r, const double* scal, double*, int g0, hipStream_t s) {
-    mg_init<<<g0, kBlock, 0, s>>>(L0, b, x, r, scal);
+  mg_restrict<G, C><<<mg_grid(nxc * nyc), kBlock, 0, s>>>(L, r, z, rc, nxc, nyc, st, g);
+}
+
+// ---- what the driver launches --------------------------------------------------------------------------------------------------------------
+// (rc: what the cycle reads - fl32(r) beside r under the float32 cycle, r itself under the fp64 cycle, where the kernels leave it alone)
+template <typename C>
+struct MgGridOps {
+  typedef LvOf<C> Level;
+  typedef MgTailT<C> Tail;
+  static bool quads(const Level& L) { return mg_has_quads<C>(L); }
+  static void pre1(const Level& L, const C* r, C* z, const MgState* st, hipStream_t s) { mg_pre1<C><<<mg_grid(L.n), kBlock, 0, s>>>(L, r, z, st); }
+  static void pre2(const Level& L, const C* r, C* z, const MgState* st, bool x4, hipStream_t s) { mg_launch_pre2<GeoWhole, C>(L, r, z, st, x4, GeoWhole{}, s); }
+  static int jacobi(const Level& L, const C* r, const C* zin, C* zout, const C* e, int nxc, double* part_rz, const MgState* st, bool x4, const double* rd,
+                    hipStream_t s) {
+    return mg_launch_jacobi<GeoWhole, C>(L, r, zin, zout, e, nxc, part_rz, st, x4, rd, GeoWhole{}, s);
   }
-  static void guess_apply(const Lv& L0, const double* b, const double* x0, double* x, double* r, const double* scal, const MgState* st, double*, int g0, hipStream_t s) {
-    mg_guess_apply<<<g0, kBlock, 0, s>>>(L0, b, x0, x, r, scal, st);
+  static void restrict_to(const Level& L, const C* r, const C* z, C* rc, const Level& Cc, const MgState* st, bool x4, hipStream_t s) {
+    mg_launch_restrict<GeoWhole, C>(L, r, z, rc, Cc.nx, Cc.ny, st, x4, GeoWhole{}, s);
   }
-  static void residual(const Lv& L0, const double* b, const double* x, double* r, const double* scal, const MgState* st, double*, int g0, hipStream_t s) {
-    mg_residual<<<g0, kBlock, 0, s>>>(L0, b, x, r, scal, st);
+  static void tail(const Tail& T, const C* r, C* z, double* part_rz, int nu, const MgState* st, const double* rd, hipStream_t s) {
+    mg_tail<C><<<1, kTailThreads, 0, s>>>(T, r, z, part_rz, nu, st, rd);
   }
-  static void direction(const Lv& L0, const double* z, const double* pold, double* pnew, double* q, const double* part_rz, int n_rz, double* scal, int k, int restart,
+  static void coarsen(const Level& F, const Level& Cc, hipStream_t s) { mg_coarsen<GeoWhole, C><<<mg_grid(Cc.n), kBlock, 0, s>>>(F, Cc, GeoWhole{}); }
+  static void export_level(const Level& L, double* out, hipStream_t s) { mg_export<C><<<mg_grid(L.n), kBlock, 0, s>>>(L, out); }
+  // the outer iteration
+  static void residual(const Lv& L0, const double* b, const double* x, double* r, const double* scal, const MgState* st, C* rc, int g0, hipStream_t s) {
+    mg_residual<GeoWhole, C><<<g0, kBlock, 0, s>>>(L0, b, x, r, scal, st, rc, GeoWhole{});
+  }
+  static void direction(const Lv& L0, const C* z, const double* pold, double* pnew, double* q, const double* part_rz, int n_rz, double* scal, int k, int restart,
                         double* part_pq, const MgState* st, int g0, hipStream_t s) {
-    mg_direction<<<g0, kBlock, 0, s>>>(L0, z, pold, pnew, q, part_rz, n_rz, scal, k, restart, part_pq, st);
+    mg_direction<GeoWhole, C><<<g0, kBlock, 0, s>>>(L0, z, pold, pnew, q, part_rz, n_rz, scal, k, restart, part_pq, st, GeoWhole{});
   }
   static void update(int n, double* x, double* r, const double* p, const double* q, const double* scal, int k, const double* part_pq, int n_pq, double* part_max,
-                     const MgState* st, double*, int g0, hipStream_t s) {
-    mg_update<<<g0, kBlock, 0, s>>>(n, x, r, p, q, scal, k, part_pq, n_pq, part_max, st);
+                     const MgState* st, C* rc, int g0, hipStream_t s) {
+    mg_update<C><<<g0, kBlock, 0, s>>>(n, x, r, p, q, scal, k, part_pq, n_pq, part_max, st, rc);
   }
-  // a cycle on its own: it reads the caller's r where it lies, which is also the double factor of (r, z); z is copied out
-  static const double* load_r(int, const double* r_in, double*, hipStream_t) { return r_in; }
-  static const double* own_rd(const double* r) { return r; }
-  static int store_z(int n, const double* z, double* z_out, hipStream_t s) {
-    PISO_HIP_CHECK(hipMemcpyAsync(z_out, z, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
-    return PISO_OK;
-  }
+  // by type: level 0 of the cycle from the fp64 set-up's; how a cycle on its own reads the caller's r, which double factor its (r, z) has,
+  // how z goes out
+  static void level0(const Lv& D, const Level& F, hipStream_t s);
+  static const C* load_r(int n, const double* r_in, C* r0, hipStream_t s);
+  static const double* own_rd(const C* r);
+  static int store_z(int n, const C* z, double* z_out, hipStream_t s);
 };
-template <>
-struct MgGridOps<float> {
-  typedef MgTail_f32 Tail;
-  static bool quads(const LvF& L) { return (L.nx & 3) == 0; }
-  static int grid(const LvF& L, bool x4) { return x4 ? mg_grid((L.nx >> 2) * L.ny) : mg_grid(L.n); }
-  static void pre1(const LvF& L, const float* r, float* z, const MgState* st, hipStream_t s) { mg_pre1_f32<<<grid(L, false), kBlock, 0, s>>>(L, r, z, st); }
-  static void pre2(const LvF& L, const float* r, float* z, const MgState* st, bool x4, hipStream_t s) {
-    if (x4) mg_pre2_f32x4<<<grid(L, true), kBlock, 0, s>>>(L, r, z, st);
-    else mg_pre2_f32<<<grid(L, false), kBlock, 0, s>>>(L, r, z, st);
-  }
-  static int jacobi(const LvF& L, const float* r, const float* zin, float* zout, const float* e, int nxc, double* part_rz, const MgState* st, bool x4,
-                    const double* rd, hipStream_t s) {
-    const int g = grid(L, x4);
-    if (!x4) mg_jacobi_f32<<<g, kBlock, 0, s>>>(L, r, zin, zout, e, nxc, part_rz, st, rd);
-    else if (e && rd) mg_jacobi_f32x4<true, true><<<g, kBlock, 0, s>>>(L, r, zin, zout, e, nxc, part_rz, st, rd);
-    else if (e) mg_jacobi_f32x4<true, false><<<g, kBlock, 0, s>>>(L, r, zin, zout, e, nxc, part_rz, st, rd);
-    else if (rd) mg_jacobi_f32x4<false, true><<<g, kBlock, 0, s>>>(L, r, zin, zout, e, nxc, part_rz, st, rd);
-    else mg_jacobi_f32x4<false, false><<<g, kBlock, 0, s>>>(L, r, zin, zout, e, nxc, part_rz, st, rd);
-    return g;
-  }
-  static void restrict_to(const LvF& L, const float* r, const float* z, float* rc, const LvF& Cc, const MgState* st, bool x4, hipStream_t s) {
-    if (x4) mg_restrict_f32x4<<<mg_grid((L.nx >> 2) * Cc.ny), kBlock, 0, s>>>(L, r, z, rc, Cc.nx, Cc.ny, st);
-    else mg_restrict_f32<<<mg_grid(Cc.n), kBlock, 0, s>>>(L, r, z, rc, Cc.nx, Cc.ny, st);
-  }
-  static void tail(const Tail& T, const float* r, float* z, double* part_rz, int nu, const MgState* st, const double* rd, hipStream_t s) {
-    mg_tail_f32<<<1, kTailThreads, 0, s>>>(T, r, z, part_rz, nu, st, rd);
-  }
-  static void level0(const Lv& D, const LvF& F, hipStream_t s) { mg_level0_f32<<<mg_grid(D.n), kBlock, 0, s>>>(D, F); }
-  static void coarsen(const LvF& F, const LvF& Cc, hipStream_t s) { mg_coarsen_f32<<<mg_grid(Cc.n), kBlock, 0, s>>>(F, Cc); }
-  static void export_level(const LvF& L, double* out, hipStream_t s) { mg_export_f32<<<mg_grid(L.n), kBlock, 0, s>>>(L, out); }
-  static void init(const Lv& L0, const double* b, double* x, double* r, const double* scal, float* r32, int g0, hipStream_t s) {
-    mg_init_f32<<<g0, kBlock, 0, s>>>(L0, b, x, r, scal, r32);
-  }
-  static void guess_apply(const Lv& L0, const double* b, const double* x0, double* x, double* r, const double* scal, const MgState* st, float* r32, int g0, hipStream_t s) {
-    mg_guess_apply_f32<<<g0, kBlock, 0, s>>>(L0, b, x0, x, r, scal, st, r32);
-  }
-  static void residual(const Lv& L0, const double* b, const double* x, double* r, const double* scal, const MgState* st, float* r32, int g0, hipStream_t s) {
-    mg_residual_f32<<<g0, kBlock, 0, s>>>(L0, b, x, r, scal, st, r32);
-  }
-  static void direction(const Lv& L0, const float* z, const double* pold, double* pnew, double* q, const double* part_rz, int n_rz, double* scal, int k, int restart,
-                        double* part_pq, const MgState* st, int g0, hipStream_t s) {
-    mg_direction_f32<<<g0, kBlock, 0, s>>>(L0, z, pold, pnew, q, part_rz, n_rz, scal, k, restart, part_pq, st);
-  }
-  static void update(int n, double* x, double* r, const double* p, const double* q, const double* scal, int k, const double* part_pq, int n_pq, double* part_max,
-                     const MgState* st, float* r32, int g0, hipStream_t s) {
-    mg_update_f32<<<g0, kBlock, 0, s>>>(n, x, r, p, q, scal, k, part_pq, n_pq, part_max, st, r32);
-  }
-  // a cycle on its own: fl32 of the caller's r, no (r, z); z comes out widened
-  static const float* load_r(int n, const double* r_in, float* r0, hipStream_t s) {
-    mg_cast_f32<<<mg_grid(n), kBlock, 0, s>>>(n, r_in, r0);
-    return r0;
-  }
-  static const double* own_rd(const float*) { return nullptr; }
-  static int store_z(int n, const float* z, double* z_out, hipStream_t s) {
-    mg_widen_f32<<<mg_grid(n), kBlock, 0, s>>>(n, z, z_out);
-    return PISO_OK;
-  }
-};
+// the fp64 cycle: the set-up writes lv[0] itself; a cycle on its own reads the caller's r where it lies, which is also the double factor of
+// (r, z); z is copied out
+template <> inline void MgGridOps<double>::level0(const Lv&, const Lv&, hipStream_t) {}
+template <> inline const double* MgGridOps<double>::load_r(int, const double* r_in, double*, hipStream_t) { return r_in; }
+template <> inline const double* MgGridOps<double>::own_rd(const double* r) { return r; }
+template <> inline int MgGridOps<double>::store_z(int n, const double* z, double* z_out, hipStream_t s) {
+  PISO_HIP_CHECK(hipMemcpyAsync(z_out, z, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
+  return PISO_OK;
+}
 
 // a regular look at the state; a prepared solve's header mismatch is reported here
 static int mg_look(MgState* pinned, const MgState* st, hipStream_t stream) {
@@ -227,7 +204,7 @@ struct MgGridT {
     const int check_every = opt(OPT_MG_CHECK_EVERY) > 0 ? opt(OPT_MG_CHECK_EVERY) : kCheckEvery;
     double* r = S.r64;
     C* rc = S.r[0];                                             // what the cycle reads: fl32(r) beside r, or r itself
-    mg_start<Ops>(L0, divergence, x0, x_out, r, rc, S.scal, S.parts, S.part_max, accuracy, S.st, s);
+    mg_start(L0, divergence, x0, x_out, r, rc, S.scal, S.parts, S.part_max, accuracy, S.st, s);
     bool done = false;
     int iterations = max_iterations;
     for (int k = 0; k < max_iterations && !done; ++k) {
@@ -246,7 +223,7 @@ struct MgGridT {
     }
     if (rank_deficient) {
       mg_sum_x<<<g0, kBlock, 0, s>>>(L0, x_out, S.parts);
-      mg_finish<<<g0, kBlock, 0, s>>>(L0, x_out, S.parts, g0, S.scal);
+      mg_finish<GeoWhole><<<g0, kBlock, 0, s>>>(L0, x_out, S.parts, g0, S.scal, GeoWhole{});
       PISO_LAUNCH_CHECK();
     }
     PISO_HIP_CHECK(hipStreamSynchronize(s));

@@ -58,9 +58,11 @@ __global__ __launch_bounds__(kBlock) void mg_guess_pick(const double* part_g, co
 }
 
 // (x0 may be x; no __restrict__ on the two: a thread reads its own cell of x0 and then writes that cell of x)
-template <bool R32>
-__device__ __forceinline__ void guess_apply(const Lv& L, const double* __restrict__ b, const double* x0, double* x, double* __restrict__ r, const double* scal,
-                                            const MgState* st, float* __restrict__ r32) {
+// R: the type of the cycle's values; under the float32 cycle rc = fl32(r) is written beside r
+template <typename R>
+__global__ __launch_bounds__(kBlock) void mg_guess_apply(Lv L, const double* __restrict__ b, const double* x0, double* x, double* __restrict__ r, const double* scal,
+                                                         const MgState* st, R* __restrict__ rc) {
+  constexpr bool R32 = std::is_same<R, float>::value;
   const bool rejected = (st->flags & MG_FLAG_GUESS_REJECTED) != 0;
   const double mean = scal[SC_MEAN_B];
   const Walk w = grid_walk();
@@ -70,37 +72,29 @@ __device__ __forceinline__ void guess_apply(const Lv& L, const double* __restric
       x[c] = 0;
       const double rv = present ? b[c] - mean : 0.0;
       r[c] = rv;
-      if (R32) r32[c] = (float)rv;
+      if constexpr (R32) rc[c] = (float)rv;
     } else {
       x[c] = present ? x0[c] : 0.0;
-      if (R32) r32[c] = (float)r[c];
+      if constexpr (R32) rc[c] = (float)r[c];
     }
   }
-}
-__global__ __launch_bounds__(kBlock) void mg_guess_apply(Lv L, const double* __restrict__ b, const double* x0, double* x, double* __restrict__ r, const double* scal,
-                                                         const MgState* st) {
-  guess_apply<false>(L, b, x0, x, r, scal, st, nullptr);
-}
-__global__ __launch_bounds__(kBlock) void mg_guess_apply_f32(Lv L, const double* __restrict__ b, const double* x0, double* x, double* __restrict__ r, const double* scal,
-                                                             const MgState* st, float* __restrict__ r32) {
-  guess_apply<true>(L, b, x0, x, r, scal, st, r32);
 }
 
 // what the calling thread's last multigrid solve did with its guess (piso_mg_last_guess): 0 none given, 1 accepted, 2 rejected
 static thread_local int tl_mg_last_guess = 0;
 
-// the start of a solve: mg_init's launch without a guess, the three launches above with one (Ops: MgGridOps<C> of mg_grid.h, which picks the
-// kernel that also writes rc = fl32(r) under the float32 cycle)
+// the start of a solve: mg_init's launch without a guess, the three launches above with one (rc: what the cycle reads, fl32(r) beside r
+// under the float32 cycle)
 // (the partial maxima use slots no kernel has pending then: part_max, which iteration 1 overwrites, and the fourth quarter of `parts`)
-template <typename Ops, typename C>
+template <typename C>
 static void mg_start(const Lv& L0, const double* divergence, const double* x0, double* x, double* r, C* rc, const double* scal, double* parts,
                      double* part_max, float accuracy, MgState* st, hipStream_t stream) {
   const int g0 = grid_for(L0.n, kBlock, kMgGrid);
-  if (!x0) { Ops::init(L0, divergence, x, r, scal, rc, g0, stream); return; }
+  if (!x0) { mg_init<C><<<g0, kBlock, 0, stream>>>(L0, divergence, x, r, scal, rc); return; }
   double* part_b = parts + 3 * kMgGrid;
   mg_guess_residual<<<g0, kBlock, 0, stream>>>(L0, divergence, x0, r, scal, part_max, part_b, st);
   mg_guess_pick<<<1, kBlock, 0, stream>>>(part_max, part_b, g0, accuracy, st);
-  Ops::guess_apply(L0, divergence, x0, x, r, scal, st, rc, g0, stream);
+  mg_guess_apply<C><<<g0, kBlock, 0, stream>>>(L0, divergence, x0, x, r, scal, st, rc);
 }
 // ... and what the host's last look says the device did with the guess
 static void mg_guess_record(const double* x0, const MgState* pinned) {

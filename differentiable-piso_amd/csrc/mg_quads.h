@@ -1,12 +1,24 @@
-// The four-cell kernels of the float32 cycle - the single statement of that code, included twice by mg.hip's translation unit:
-//   * for the WHOLE grid (mg_f32.h): the macros expand to the expressions this code has always had, token for token;
-//   * for a rank's SLAB of a sharded level (mg_slab_f32.h, GeoSlab g): the quads below / above are the storage rows -1 / +1 (the halo rows
-//     are real rows), and the coarse row of a fine row comes from GeoSlab::erow (a global row where the coarser level is replicated).
-// MG_N(stem) names a kernel; MG_GEO_PARAM is the slab's trailing parameter; MG_QUAD_AT the quad of a work item; MG_JS / MG_JN / MG_EROW the
-// fine rows below / above and the coarse row of a fine row (as in mg_cells.inc).  A thread owns four consecutive cells of one row; the
-// trip count is uniform per wave because the lanes exchange values.
+// The four-cell kernels of the float32 cycle (part of mg.hip's translation unit), templates over the geometry G of mg_cells.h: GeoWhole for
+// the whole grid, GeoSlab for a rank's rows of a sharded level - there the quads below / above are the storage rows -1 / +1 (the halo rows
+// are real rows) and the coarse row of a fine row comes from GeoSlab::erow (a global row where the coarser level is replicated).
+// A thread owns four consecutive cells of one row and moves them as 16-byte accesses (rows are 16-byte aligned: nx % 4 == 0, the arena
+// aligns to 256 and a slab's halo offset is nx floats); the W / E neighbours of the quad's end cells come from the neighbouring lane where
+// it holds the same row, from a load at wave edges, row ends and the periodic seam.  The trip count is uniform per wave because the lanes
+// exchange values.  Per cell the kernels evaluate the expressions of the scalar kernels (stencil_sum, pre2_out, jac_out, restrict_term): z
+// is bitwise the same.
+#pragma once
+
+namespace piso {
+
+__device__ __forceinline__ void ld4(const float* p, float (&v)[4]) {
+  const float4 t = *reinterpret_cast<const float4*>(p);
+  v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+}
+__device__ __forceinline__ void st4(float* p, const float (&v)[4]) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
+
 // sweeps 1 and 2 from a zero guess (ph_pre2)
-__global__ __launch_bounds__(kBlock) void MG_N(mg_pre2)(LvF L, const float* r, float* z, const MgState* st MG_GEO_PARAM) {
+template <typename G>
+__global__ __launch_bounds__(kBlock) void mg_pre2_x4(LvF L, const float* r, float* z, const MgState* st, G g) {
   if (st->done) return;
   const int nxq = L.nx >> 2, nq = nxq * L.ny;
   for (int base = blockIdx.x * blockDim.x; base < nq; base += gridDim.x * blockDim.x) {      // (uniform trip count per wave: the lanes exchange values)
@@ -14,7 +26,7 @@ __global__ __launch_bounds__(kBlock) void MG_N(mg_pre2)(LvF L, const float* r, f
     const bool act = qd < nq;
     const int qq = act ? qd : nq - 1;                                                           // an idle lane redoes the last quad and stores nothing
     const int row = qq / nxq;
-    const Quad q = MG_QUAD_AT(row, qq - row * nxq, L.nx, L.ny);
+    const Quad q = g.quad(row, qq - row * nxq, L.nx, L.ny);
     float cf[5][4], di[4], rc[4], z1[4], zs[4], zn[4], a[4], b[4], out[4];
 #pragma unroll
     for (int s = 0; s < 5; ++s) ld4(L.c[s] + q.c0, cf[s]);
@@ -39,9 +51,9 @@ __global__ __launch_bounds__(kBlock) void MG_N(mg_pre2)(LvF L, const float* r, f
 }
 
 // one sweep (ph_jac); HAS_E: the coarse correction is added first; RZ: the block's part of (rd, zout) in double
-template <bool HAS_E, bool RZ>
-__global__ __launch_bounds__(kBlock) void MG_N(mg_jacobi)(LvF L, const float* r, const float* zin, float* zout, const float* e, int nxc, double* part_rz,
-                                                          const MgState* st, const double* rd MG_GEO_PARAM) {
+template <typename G, bool HAS_E, bool RZ>
+__global__ __launch_bounds__(kBlock) void mg_jacobi_x4(LvF L, const float* r, const float* zin, float* zout, const float* e, int nxc, double* part_rz,
+                                                          const MgState* st, const double* rd, G g) {
   if (st->done) return;
   __shared__ double smem[16];
   const int nxq = L.nx >> 2, nq = nxq * L.ny;
@@ -51,7 +63,7 @@ __global__ __launch_bounds__(kBlock) void MG_N(mg_jacobi)(LvF L, const float* r,
     const bool act = qd < nq;
     const int qq = act ? qd : nq - 1;
     const int row = qq / nxq;
-    const Quad q = MG_QUAD_AT(row, qq - row * nxq, L.nx, L.ny);
+    const Quad q = g.quad(row, qq - row * nxq, L.nx, L.ny);
     float cf[5][4], di[4], rc[4], vc[4], vs[4], vn[4], zo[4];
 #pragma unroll
     for (int s = 0; s < 5; ++s) ld4(L.c[s] + q.c0, cf[s]);
@@ -59,11 +71,11 @@ __global__ __launch_bounds__(kBlock) void MG_N(mg_jacobi)(LvF L, const float* r,
     ld4(zin + q.c0, vc); ld4(zin + q.cs, vs); ld4(zin + q.cn, vn);
     float vw = 0, ve = 0;
     if (HAS_E) {
-      const int js = MG_JS(q.j, L.ny), jn = MG_JN(q.j, L.ny);
+      const int js = g.js(q.j, L.ny), jn = g.jn(q.j, L.ny);
       const int col = q.i0 >> 1;                                                                // (even: the two coarse cells above the quad are one 8-byte load)
-      const float2 ec = *reinterpret_cast<const float2*>(e + MG_EROW(q.j) * nxc + col);
-      const float2 es = *reinterpret_cast<const float2*>(e + MG_EROW(js) * nxc + col);
-      const float2 en = *reinterpret_cast<const float2*>(e + MG_EROW(jn) * nxc + col);
+      const float2 ec = *reinterpret_cast<const float2*>(e + g.erow(q.j) * nxc + col);
+      const float2 es = *reinterpret_cast<const float2*>(e + g.erow(js) * nxc + col);
+      const float2 en = *reinterpret_cast<const float2*>(e + g.erow(jn) * nxc + col);
       float ds[4], dn[4];
       ld4(L.dinv + q.cs, ds); ld4(L.dinv + q.cn, dn);
 #pragma unroll
@@ -76,11 +88,11 @@ __global__ __launch_bounds__(kBlock) void MG_N(mg_jacobi)(LvF L, const float* r,
     vw = __shfl_up(vc[3], 1, kWave); ve = __shfl_down(vc[0], 1, kWave);
     if (!q.lane_w) {
       vw = zin[q.cw];
-      if (HAS_E) { const int iw = q.i0 > 0 ? q.i0 - 1 : L.nx - 1; if (L.dinv[q.cw] != 0) vw += e[MG_EROW(q.j) * nxc + (iw >> 1)]; }
+      if (HAS_E) { const int iw = q.i0 > 0 ? q.i0 - 1 : L.nx - 1; if (L.dinv[q.cw] != 0) vw += e[g.erow(q.j) * nxc + (iw >> 1)]; }
     }
     if (!q.lane_e) {
       ve = zin[q.ce];
-      if (HAS_E) { const int ie = q.i0 + 4 < L.nx ? q.i0 + 4 : 0; if (L.dinv[q.ce] != 0) ve += e[MG_EROW(q.j) * nxc + (ie >> 1)]; }
+      if (HAS_E) { const int ie = q.i0 + 4 < L.nx ? q.i0 + 4 : 0; if (L.dinv[q.ce] != 0) ve += e[g.erow(q.j) * nxc + (ie >> 1)]; }
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -102,7 +114,8 @@ __global__ __launch_bounds__(kBlock) void MG_N(mg_jacobi)(LvF L, const float* r,
 }
 
 // rc = P^T (r - A z) on the present cells (ph_restrict): a thread owns four columns of the fine rows 2J, 2J + 1 = two coarse cells
-__global__ __launch_bounds__(kBlock) void MG_N(mg_restrict)(LvF L, const float* r, const float* z, float* rcoarse, int nxc, int nyc, const MgState* st MG_GEO_PARAM) {
+template <typename G>
+__global__ __launch_bounds__(kBlock) void mg_restrict_x4(LvF L, const float* r, const float* z, float* rcoarse, int nxc, int nyc, const MgState* st, G g) {
   if (st->done) return;
   const int nxq = L.nx >> 2, nq = nxq * nyc;
   for (int base = blockIdx.x * blockDim.x; base < nq; base += gridDim.x * blockDim.x) {
@@ -114,7 +127,7 @@ __global__ __launch_bounds__(kBlock) void MG_N(mg_restrict)(LvF L, const float* 
 #pragma unroll
     for (int dj = 0; dj < 2; ++dj) {
       const bool have = 2 * J + dj < L.ny;                                                      // (odd ny: the last coarse row has one fine row)
-      const Quad q = MG_QUAD_AT(have ? 2 * J + dj : 2 * J, iq, L.nx, L.ny);                        // (every lane takes part in the exchange)
+      const Quad q = g.quad(have ? 2 * J + dj : 2 * J, iq, L.nx, L.ny);                        // (every lane takes part in the exchange)
       float cf[5][4], di[4], rc[4], zc[4], zs[4], zn[4];
 #pragma unroll
       for (int t = 0; t < 5; ++t) ld4(L.c[t] + q.c0, cf[t]);
@@ -133,3 +146,5 @@ __global__ __launch_bounds__(kBlock) void MG_N(mg_restrict)(LvF L, const float* 
     if (act) *reinterpret_cast<float2*>(rcoarse + J * nxc + (iq << 1)) = make_float2(s[0], s[1]);
   }
 }
+
+}  // namespace piso

@@ -2,7 +2,7 @@
 // The algorithm, its constants, the hierarchy's dimensions, the stopping rule, the constant-mode treatment and the device-side
 // alpha / beta are the one-GPU solver's; only where rows live and how sums are formed differ.  mg_slab_plan.h is the plan:
 //   * levels [0, g) are SHARDED: a rank holds its nyl >> l rows of every array plus one halo row below and one above (zero where the
-//     grid ends without a periodic wrap).  The slab kernels are the per-cell code of mg.hip with GeoSlab: y-neighbours are the rows
+//     grid ends without a periodic wrap).  The slab kernels are the per-cell code of mg_cells.h with GeoSlab: y-neighbours are the rows
 //     below and above in storage, coarse indices are the rank's own (2 x 2 aggregates never straddle a cut);
 //   * level g and everything coarser is REPLICATED: a rank forms its rows of level g from its rows of level g - 1 (the coefficients
 //     once per solve, the restricted residual once per cycle), the rows are all-gathered, and every rank runs levels g .. coarsest
@@ -13,77 +13,18 @@
 // decisions), the rows of level g and the ranks' maxima of |r| by comm_allgather_f64 (the check kernel takes nanmax over them).
 // One driver over a vector of per-rank contexts and a link: the communicator link has one context, the loopback link V virtual ranks
 // on one device whose rows it copies - no mailbox - so that one process can test every cut.  The driver is ONE text over the type C of the
-// cycle's values, MgSlabT<C>, with its launches in MgSlabOps<C>: MgSlab = MgSlabT<double> is this solver, MgSlabT<float> runs the float32
-// cycle of mg_f32.h on the same plan under the same fp64 outer iteration (mg_slab_f32.h).
+// cycle's values, MgSlabT<C>, with its launches in MgSlabOps<C> (kernel<GeoSlab, C>): MgSlab = MgSlabT<double> is this solver, MgSlabT<float>
+// runs the float32 cycle of mg_f32.h on the same plan under the same fp64 outer iteration (mg_slab_f32.h).
 #pragma once
 
 namespace piso {
 
 // (MgSlabRankT<C>, what a rank holds, and mg_slab_carve, its workspace: mg_slab_carve.h - host code a driver can walk)
-typedef MgSlabRankT<double> MgSlabRank;
 
-// ---- slab instances of the per-cell code (mg_cells.inc a second time) ------------------------------------------------------------------------
-struct GeoSlab {
-  int row0, nyg;             // the rank's first global row of this level and the level's global rows
-  int coarse_global;         // the coarser level is replicated: its rows are global rows (else the rank's, with halo rows -1 and L.ny / 2)
-  const double* dg;          // set-up only: the diagonals of the rank's rows of the caller's matrix, with halo rows
-  double ncells;             // cells of the whole grid
-  __device__ __forceinline__ Nb nb(int c, int i, int nx) const {
-    Nb q;
-    q.s = c - nx; q.w = i > 0 ? c - 1 : c + (nx - 1); q.e = i < nx - 1 ? c + 1 : c - (nx - 1); q.n = c + nx;
-    return q;
-  }
-  // coarse row of the rank's fine row j, -1 and L.ny included (periodic y: row -1 of rank 0 is row nyg - 1; without, the halo row's dinv is
-  // zero and nobody reads the index)
-  __device__ __forceinline__ int erow(int j) const { return coarse_global ? ((row0 + j + nyg) % nyg) >> 1 : j >> 1; }
-};
-#define MG_N(name) name##_slab
-#define MG_REAL double
-#define MG_LV Lv
-#define MG_RDOT_PARAM
-#define MG_RDOT_ARG(rd)
-#define MG_RDOT(rc, zo, c) rc * zo
-#define MG_R32_PARAM
-#define MG_R32_STORE(c, v)
-#define MG_GEO_PARAM , GeoSlab g
-#define MG_NB(c, i, j, nx, ny) g.nb(c, i, nx)
-#define MG_JS(j, ny) j - 1
-#define MG_JN(j, ny) j + 1
-#define MG_EROW(j) g.erow(j)
-#define MG_FIRST_ROW(j) g.row0 + j == 0
-#define MG_LAST_ROW(j, ny) g.row0 + j == g.nyg - 1
-#define MG_DIAG(Lin, idx) g.dg[idx]
-#define MG_NCELLS(L) g.ncells
-// p' = z + beta p on the rank's two halo rows as well: p never crosses a cut (beta is the same bits on every rank)
-#define MG_DIRECTION_HALO_ROWS                                                                                                  \
-  for (int h = blockIdx.x * blockDim.x + threadIdx.x; h < 2 * L.nx; h += gridDim.x * blockDim.x) {                            \
-    const int ch = h < L.nx ? h - L.nx : L.n + (h - L.nx);                                                                      \
-    pnew[ch] = restart ? z[ch] : z[ch] + beta * pold[ch];                                                                       \
-  }
-#include "mg_cells.inc"
-#include "mg_cells_undef.inc"
-
+// ---- kernels of the slab alone (GeoSlab and the per-cell kernels over it: mg_cells.h) ----------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void mg_slab_diag(const double* __restrict__ Lin, double* __restrict__ dg, int n) {
   const Walk w = grid_walk();
   for (int c = w.begin; c < n; c += w.step) dg[c] = Lin[(size_t)c * 5 + 2];
-}
-__global__ __launch_bounds__(kBlock) void mg_pre2_slab(Lv L, const double* r, double* z, const MgState* st, GeoSlab g) {
-  if (st->done) return;
-  ph_pre2_slab(L, r, z, grid_walk(), g);
-}
-__global__ __launch_bounds__(kBlock) void mg_jacobi_slab(Lv L, const double* r, const double* zin, double* zout, const double* e, int nxc, double* part_rz,
-                                                         const MgState* st, GeoSlab g) {
-  if (st->done) return;
-  __shared__ double smem[16];
-  double acc = ph_jac_slab(L, r, zin, zout, e, nxc, grid_walk(), g);
-  if (part_rz) {
-    acc = mg_block_sum(acc, smem);
-    if (threadIdx.x == 0) part_rz[blockIdx.x] = acc;
-  }
-}
-__global__ __launch_bounds__(kBlock) void mg_restrict_slab(Lv L, const double* r, const double* z, double* rc, int nxc, int nyc, const MgState* st, GeoSlab g) {
-  if (st->done) return;
-  ph_restrict_slab(L, r, z, rc, nxc, nyc, grid_walk(), g);
 }
 
 // ---- what the sums need around the collectives ---------------------------------------------------------------------------------------------
@@ -126,8 +67,9 @@ __global__ void mg_slab_setup_spread(const double* g, const double* gmax, int wo
   st->flags |= (g[7] != 0 ? MG_FLAG_BORDER : 0) | (g[8] != 0 ? MG_FLAG_ZERO_DIAG_ROW : 0);
 }
 // zero the halo rows of up to 12 arrays (pointers at owned row 0 of n = nx * rows cells): where the grid ends no exchange writes them
-struct MgHalos { int count; double* a[12]; };
-__global__ __launch_bounds__(kBlock) void mg_slab_zero_halos(MgHalos h, int nx, int n) {
+template <typename T> struct MgHalosT { int count; T* a[12]; };
+template <typename T>
+__global__ __launch_bounds__(kBlock) void mg_slab_zero_halos(MgHalosT<T> h, int nx, int n) {
   const Walk w = grid_walk();
   for (int i = w.begin; i < nx; i += w.step)
     for (int k = 0; k < h.count; ++k) { h.a[k][i - nx] = 0; h.a[k][n + i] = 0; }
@@ -215,56 +157,61 @@ static size_t mg_slab_rank_bytes(const MgSlabPlan& sp) {
 }
 static size_t mg_slab_g_bytes(int local_ranks) { return align_up((size_t)local_ranks * kMgSlabG * sizeof(double), 256); }
 
-// ---- what the driver launches, by the type of the cycle's values (float: mg_slab_f32.h) ---------------------------------------------------------
-template <typename C> struct MgSlabOps;
-template <>
-struct MgSlabOps<double> {
-  typedef MgSlabRank RK;
-  static constexpr bool kRunsG0 = true;
-  static Lv& outer(RK& k, int g) { return g > 0 ? k.lv[0] : k.chunk; }                  // the fp64 level 0 the set-up writes (g = 0: the chunk IS the rank's rows of level 0)
-  static void level0(RK&, hipStream_t) {}
+// ---- what the driver launches ------------------------------------------------------------------------------------------------------------------
+// (x4, rd and the launches of the kernels that have a four-cell form: mg_grid.h; the replicated levels run MgGridOps<C>)
+template <typename C>
+struct MgSlabOps {
+  typedef MgSlabRankT<C> RK;
+  typedef LvOf<C> Level;
+  static constexpr bool kRunsG0 = std::is_same<C, double>::value;       // g = 0, the whole cycle replicated, is the fp64 cycle's alone
   static void zero_halos(RK& k, int l, hipStream_t s) {
-    MgHalos h{9, {k.lv[l].c[0], k.lv[l].c[1], k.lv[l].c[2], k.lv[l].c[3], k.lv[l].c[4], k.lv[l].dinv, k.r[l], k.z[l], k.t[l]}};
-    mg_slab_zero_halos<<<grid_for(k.lv[l].nx, kBlock, 64), kBlock, 0, s>>>(h, k.lv[l].nx, k.lv[l].n);
+    MgHalosT<C> h{9, {k.lv[l].c[0], k.lv[l].c[1], k.lv[l].c[2], k.lv[l].c[3], k.lv[l].c[4], k.lv[l].dinv, k.r[l], k.z[l], k.t[l]}};
+    mg_slab_zero_halos<C><<<grid_for(k.lv[l].nx, kBlock, 64), kBlock, 0, s>>>(h, k.lv[l].nx, k.lv[l].n);
   }
-  static void coarsen_slab(const Lv& F, const Lv& Cc, const GeoSlab& g, hipStream_t s) { mg_coarsen_slab<<<mg_grid(Cc.n), kBlock, 0, s>>>(F, Cc, g); }
-  static void coarsen(const Lv& F, const Lv& Cc, hipStream_t s) { mg_coarsen<<<mg_grid(Cc.n), kBlock, 0, s>>>(F, Cc); }
-  static bool quads(const Lv&) { return false; }
+  static void coarsen_slab(const Level& F, const Level& Cc, const GeoSlab& g, hipStream_t s) { mg_coarsen<GeoSlab, C><<<mg_grid(Cc.n), kBlock, 0, s>>>(F, Cc, g); }
   // the first sweep (nu 1) or the first two (ph_pre2) from a zero guess
-  static void pre(const Lv& L, const double* r, double* z, const MgState* st, const GeoSlab& g, int nu, bool, hipStream_t s) {
-    if (nu >= 2) mg_pre2_slab<<<mg_grid(L.n), kBlock, 0, s>>>(L, r, z, st, g);
-    else mg_pre1<<<mg_grid(L.n), kBlock, 0, s>>>(L, r, z, st);
+  static void pre(const Level& L, const C* r, C* z, const MgState* st, const GeoSlab& g, int nu, bool x4, hipStream_t s) {
+    if (nu >= 2) mg_launch_pre2<GeoSlab, C>(L, r, z, st, x4, g, s);
+    else mg_pre1<C><<<mg_grid(L.n), kBlock, 0, s>>>(L, r, z, st);
   }
-  // one sweep; returns the number of (r, z) partials (part_rz given); rd: the outer residual (the float32 cycle's other factor)
-  static int jacobi(const Lv& L, const double* r, const double* zin, double* zout, const double* e, int nxc, double* part_rz, const MgState* st, const GeoSlab& g,
-                    bool, const double*, hipStream_t s) {
-    const int gl = mg_grid(L.n);
-    mg_jacobi_slab<<<gl, kBlock, 0, s>>>(L, r, zin, zout, e, nxc, part_rz, st, g);
-    return gl;
+  static int jacobi(const Level& L, const C* r, const C* zin, C* zout, const C* e, int nxc, double* part_rz, const MgState* st, const GeoSlab& g, bool x4,
+                    const double* rd, hipStream_t s) {
+    return mg_launch_jacobi<GeoSlab, C>(L, r, zin, zout, e, nxc, part_rz, st, x4, rd, g, s);
   }
-  static void restrict_to(const Lv& L, const double* r, const double* z, double* rc, int nxc, int nyc, const MgState* st, const GeoSlab& g, bool, hipStream_t s) {
-    mg_restrict_slab<<<mg_grid(nxc * nyc), kBlock, 0, s>>>(L, r, z, rc, nxc, nyc, st, g);
+  static void restrict_to(const Level& L, const C* r, const C* z, C* rc, int nxc, int nyc, const MgState* st, const GeoSlab& g, bool x4, hipStream_t s) {
+    mg_launch_restrict<GeoSlab, C>(L, r, z, rc, nxc, nyc, st, x4, g, s);
   }
-  static const double* gather_src(RK& k, int g) { return g > 0 ? k.rchunk : k.ro; }
-  static void init(const Lv& L0, RK& k, int g0, hipStream_t s) { mg_init<<<g0, kBlock, 0, s>>>(L0, k.b, k.x, k.ro, k.scal); }
-  static void residual(const Lv& L0, RK& k, int g0, const GeoSlab& g, hipStream_t s) { mg_residual_slab<<<g0, kBlock, 0, s>>>(L0, k.b, k.x, k.ro, k.scal, k.st, g); }
+  // the outer iteration (r[0]: what the cycle reads, fl32(r) beside r under the float32 cycle)
+  static void init(const Lv& L0, RK& k, int g0, hipStream_t s) { mg_init<C><<<g0, kBlock, 0, s>>>(L0, k.b, k.x, k.ro, k.scal, k.r[0]); }
+  static void residual(const Lv& L0, RK& k, int g0, const GeoSlab& g, hipStream_t s) {
+    mg_residual<GeoSlab, C><<<g0, kBlock, 0, s>>>(L0, k.b, k.x, k.ro, k.scal, k.st, k.r[0], g);
+  }
   static void direction(const Lv& L0, RK& k, int g0, int it, int restart, const GeoSlab& g, hipStream_t s) {
-    mg_direction_slab<<<g0, kBlock, 0, s>>>(L0, k.z_top, k.p[it & 1], k.p[(it + 1) & 1], k.q, k.g, 1, k.scal, it, restart, k.part_pq, k.st, g);
+    mg_direction<GeoSlab, C><<<g0, kBlock, 0, s>>>(L0, k.z_top, k.p[it & 1], k.p[(it + 1) & 1], k.q, k.g, 1, k.scal, it, restart, k.part_pq, k.st, g);
   }
   static void update(int n0, RK& k, int g0, int it, hipStream_t s) {
-    mg_update<<<g0, kBlock, 0, s>>>(n0, k.x, k.ro, k.p[(it + 1) & 1], k.q, k.scal, it, k.g + 1, 1, k.part_max, k.st);
+    mg_update<C><<<g0, kBlock, 0, s>>>(n0, k.x, k.ro, k.p[(it + 1) & 1], k.q, k.scal, it, k.g + 1, 1, k.part_max, k.st, k.r[0]);
   }
-  static void export_level(const Lv& L, double* out, hipStream_t s) { mg_export<<<mg_grid(L.n), kBlock, 0, s>>>(L, out); }
-  // one cycle from the caller's rows of r, its rows of z out
-  static int load_r(RK& k, const double* rows, size_t n, hipStream_t s) {
-    PISO_HIP_CHECK(hipMemcpyAsync(k.ro, rows, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-    return PISO_OK;
-  }
-  static int store_z(RK& k, double* rows, size_t n, hipStream_t s) {
-    PISO_HIP_CHECK(hipMemcpyAsync(rows, k.z_top, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-    return PISO_OK;
-  }
+  // by type: the fp64 level 0 the set-up writes and the cycle's level 0 from it; the rank's rows of the residual of level g; one cycle from
+  // the caller's rows of r, its rows of z out
+  static Lv& outer(RK& k, int g);
+  static void level0(RK& k, hipStream_t s);
+  static const C* gather_src(RK& k, int g);
+  static int load_r(RK& k, const double* rows, size_t n, hipStream_t s);
+  static int store_z(RK& k, double* rows, size_t n, hipStream_t s);
 };
+// the fp64 cycle: its level 0 IS the set-up's (g = 0: the chunk is the rank's rows of level 0)
+template <> inline Lv& MgSlabOps<double>::outer(RK& k, int g) { return g > 0 ? k.lv[0] : k.chunk; }
+template <> inline void MgSlabOps<double>::level0(RK&, hipStream_t) {}
+template <> inline const double* MgSlabOps<double>::gather_src(RK& k, int g) { return g > 0 ? k.rchunk : k.ro; }
+template <> inline int MgSlabOps<double>::load_r(RK& k, const double* rows, size_t n, hipStream_t s) {
+  PISO_HIP_CHECK(hipMemcpyAsync(k.ro, rows, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+  return PISO_OK;
+}
+template <> inline int MgSlabOps<double>::store_z(RK& k, double* rows, size_t n, hipStream_t s) {
+  PISO_HIP_CHECK(hipMemcpyAsync(rows, k.z_top, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+  return PISO_OK;
+}
 
 // levels g .. coarsest on a rank's replicated copy, as the one-GPU driver runs them: its plan as a view of the rank's levels (a cycle on its
 // own there - the fp64 cycle leaves partials of (r_g, z_g) nobody reads, the float32 cycle none)
@@ -301,7 +248,7 @@ struct MgSlabT {
     g.row0 = k.rank * (l == 0 ? sp.nyl : sp.rows[l]); g.nyg = sp.d.ny[l]; g.coarse_global = (l + 1 >= sp.g) ? 1 : 0; g.dg = nullptr; g.ncells = (double)sp.d.nx[0] * sp.d.ny[0];
     return g;
   }
-  bool quads(const RK& k, int l) const { return vec && Ops::quads(k.lv[l]); }
+  bool quads(const RK& k, int l) const { return vec && MgGridOps<C>::quads(k.lv[l]); }
 
   // carve `ws` (the g buffers of all local ranks first, contiguous: the loopback all-reduce walks them)
   int carve(const char* who, void* ws, size_t bytes) {
@@ -325,9 +272,9 @@ struct MgSlabT {
     for (RK& k : R) {
       PISO_HIP_CHECK(hipMemsetAsync(k.st, 0, sizeof(MgState), s));
       for (int l = 0; l < sp.g; ++l) Ops::zero_halos(k, l, s);
-      MgHalos h{3, {k.p[0], k.p[1], k.x}};
+      MgHalosT<double> h{3, {k.p[0], k.p[1], k.x}};
       if (sp.g == 0) { h.a[3] = k.ro; h.a[4] = reinterpret_cast<double*>(k.zo); h.count = 5; }      // (g = 0 is the fp64 cycle's alone)
-      mg_slab_zero_halos<<<grid_for(nx, kBlock, 64), kBlock, 0, s>>>(h, nx, n0);
+      mg_slab_zero_halos<double><<<grid_for(nx, kBlock, 64), kBlock, 0, s>>>(h, nx, n0);
       mg_slab_diag<<<g0, kBlock, 0, s>>>(k.Lin, k.p[0], n0);          // (p[0] is free until the first direction)
     }
     // (around the ring whatever the border: the whole-grid set-up looks at the wrapped row's diagonal there too)
@@ -335,7 +282,7 @@ struct MgSlabT {
     for (RK& k : R) {
       GeoSlab g = geo(k, 0);
       g.dg = k.p[0];
-      mg_setup0_slab<<<g0, kBlock, 0, s>>>(k.Lin, Ops::outer(k, sp.g), k.b, k.parts, k.st, g);
+      mg_setup0<GeoSlab><<<g0, kBlock, 0, s>>>(k.Lin, Ops::outer(k, sp.g), k.b, k.parts, k.st, g);
       Ops::level0(k, s);
       mg_slab_setup_collapse<<<1, kBlock, 0, s>>>(k.parts, g0, k.st, k.g);
     }
@@ -344,8 +291,8 @@ struct MgSlabT {
     for (RK& k : R) {
       mg_slab_setup_spread<<<1, 64, 0, s>>>(k.g, k.gmax, sp.world, k.parts, k.st);
       mg_setup_fin<<<1, kBlock, 0, s>>>(k.parts, sp.world, k.scal, rank_deficient, n0 * sp.world, k.st);
-      MgHalos h{2, {k.p[0], k.p[1]}};                                 // (the diagonals' halo rows: p must start from zero ones)
-      mg_slab_zero_halos<<<grid_for(nx, kBlock, 64), kBlock, 0, s>>>(h, nx, n0);
+      MgHalosT<double> h{2, {k.p[0], k.p[1]}};                                 // (the diagonals' halo rows: p must start from zero ones)
+      mg_slab_zero_halos<double><<<grid_for(nx, kBlock, 64), kBlock, 0, s>>>(h, nx, n0);
     }
     // the sharded levels: halo rows of the diagonal (coarsening reads the neighbours' presence) and of dinv, once per solve
     for (int l = 0; l < sp.g; ++l) {
@@ -358,7 +305,7 @@ struct MgSlabT {
       PISO_TRY(link.allgather(R, [a](RK& k) { return a < 5 ? k.chunk.c[a] : k.chunk.dinv; },
                               [a, this](RK& k) { return a < 5 ? k.lv[sp.g].c[a] : k.lv[sp.g].dinv; }, (size_t)R[0].chunk.n));
     for (RK& k : R)
-      for (int l = sp.g; l + 1 < sp.d.nlev; ++l) Ops::coarsen(k.lv[l], k.lv[l + 1], s);
+      for (int l = sp.g; l + 1 < sp.d.nlev; ++l) MgGridOps<C>::coarsen(k.lv[l], k.lv[l + 1], s);
     PISO_LAUNCH_CHECK();
     PISO_HIP_CHECK(hipMemcpyAsync(pinned, R[0].st, sizeof(MgState), hipMemcpyDeviceToHost, s));
     PISO_HIP_CHECK(hipStreamSynchronize(s));
@@ -481,7 +428,7 @@ struct MgSlabT {
         mg_slab_collapse<<<1, kBlock, 0, s>>>(k.parts, g0, k.g + 3, nullptr);
       }
       PISO_TRY(link.allreduce(R, 3, 1));
-      for (RK& k : R) mg_finish_slab<<<g0, kBlock, 0, s>>>(L0(k), k.x, k.g + 3, 1, k.scal, geo(k, 0));
+      for (RK& k : R) mg_finish<GeoSlab><<<g0, kBlock, 0, s>>>(L0(k), k.x, k.g + 3, 1, k.scal, geo(k, 0));
       PISO_LAUNCH_CHECK();
     }
     if (iterations_out) *iterations_out = iterations;
