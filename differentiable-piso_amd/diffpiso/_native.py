@@ -241,7 +241,15 @@ for _n in ("piso_loss_l2", "piso_loss_l2_grad", "piso_loss_strain", "piso_loss_s
     getattr(lib, _n).restype = _i
     getattr(lib, _n + "_slab").argtypes = getattr(lib, _n).argtypes + [_sp]
     getattr(lib, _n + "_slab").restype = _i
-lib.piso_csr_matvec_f32_slab.argtypes = [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sp]
+lib.piso_loss_centre_crop.argtypes = [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]                    # (faces, nx, ny, y0, y1, x0, x1, planes, stream)
+lib.piso_loss_centre_crop_adjoint.argtypes = [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]            # (d_planes, ..., d_faces, stream)
+lib.piso_loss_spectrum_shells.argtypes = [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]                  # (spec, perm, offsets, h, w, cutoff, energy, stream)
+lib.piso_loss_spectrum_shells_adjoint.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]     # (spec, shell, d_energy, upstream, h, w, cutoff, d_spec, stream)
+lib.piso_loss_spectrum_distance.argtypes = [_vp, _vp, _i, _i, _i, _d, _vp, _vp, _vp]            # (e_pred, e_gt, cutoff, start, log, factor, value, d_e_pred, stream)
+for _n in ("piso_loss_centre_crop", "piso_loss_centre_crop_adjoint", "piso_loss_spectrum_shells", "piso_loss_spectrum_shells_adjoint",
+           "piso_loss_spectrum_distance"):
+    getattr(lib, _n).restype = _i
+lib.piso_csr_matvec_f32_slab.argtypes =[_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sp]
 lib.piso_csr_matvec_f32_slab.restype = _i
 lib.piso_bicgstab_slab_workspace_bytes.argtypes = [_i, _i, _i, _sp]
 lib.piso_bicgstab_slab_workspace_bytes.restype = _sz

@@ -12,7 +12,12 @@ convention and returns the RANK'S PART - the parts add up over the ranks to the 
   spectral     every rank gathers the whole face field (`gather_face_rows`), evaluates the unchanged loss on it and contributes
                value / world; costs ONE whole-grid field per step, transiently (no rocFFT on slabs)
 Whole-grid fields take the torch paths below unchanged; `L2_field_loss(..., fused=True)` / `strain_rate_loss(..., fused=True)` opt into the
-whole-grid instantiation of the same kernels (device tensors only - there is no CPU form of them)."""
+whole-grid instantiation of the same kernels (device tensors only - there is no CPU form of them).
+`spectral_energy_loss(..., fused=True)` replaces the torch expression around the transform by the kernels of csrc/loss_spectrum.hip: centre +
+crop -> torch.fft.fft2 (rocFFT) -> shell sums through the tables of `spectrum_plan` (built once per crop shape, the bins of EK_spectrum_2D_tf
+by construction) -> distance.  Fixed-order float64 sums instead of index_add_'s float atomics, no host read, gather-form adjoints.  On slab
+fields the gathered whole field takes that path on every rank (value / world as before).  `training_dict["fused_losses"] = True` passes
+fused=True to every loss of a training_run (training.py)."""
 import ctypes as C
 
 import numpy as np
@@ -149,6 +154,164 @@ def _fused_strain(field, truth_frame, factor):
     return _FusedStrain.apply(pred, target, (nx, ny, tuple(float(d) for d in field.dx), float(factor), slab_ptr))
 
 
+# ---------------------------------------------------------------------------------------- fused spectral loss (csrc/loss_spectrum.hip)
+def spectrum_window(buffer_width, sponge_start, ny, nx):
+    """(y0, y1, x0, x1): the crop of spectral_energy_loss on CELL indices [ny][nx], exactly the two slices it takes of the centred field
+    (sponge_start 0: the field's width), resolved like Python resolves a slice and never inverted."""
+    rows, cols = int(ny), int(nx)
+    if sponge_start == 0:
+        sponge_start = cols
+    y0, y1, _ = slice(int(buffer_width[0][0]), rows - int(buffer_width[0][1])).indices(rows)
+    x0, x1, _ = slice(int(buffer_width[1][0]), int(sponge_start) - int(buffer_width[1][1])).indices(cols)
+    return y0, max(y1, y0), x0, max(x1, x0)
+
+
+class SpectrumPlan(object):
+    """The wavenumber shells of an h x w crop, as tables on `device` (all int32):
+      shell    [h * w] on the UNSHIFTED FFT index q = q0 * w + q1: the shell EK_spectrum_2D_tf adds that coefficient to - its `wvn` read
+               at p = (q - n // 2) mod n per axis, tf_fftshift's quadrant swap without the copies
+      perm     the q with shell[q] < cutoff, sorted by (shell, q)
+      offsets  [cutoff + 1]: shell k is perm[offsets[k] : offsets[k + 1]]
+    cutoff = min(h, w) // 2."""
+
+    def __init__(self, h, w, device):
+        h, w = int(h), int(w)
+        if h < 1 or w < 1:
+            raise ValueError("spectrum plan: a crop of %d x %d cells" % (h, w))
+        # the float32 expression of EK_spectrum_2D_tf, evaluated on the host: the arguments of sqrt are exact multiples of 1/4, a radius of
+        # exactly k + 1/2 is the root of an exact square (exact on every IEEE sqrt, then rounded to even by torch.round like there), and
+        # every other radius is further from k + 1/2 than any sqrt's error - so these are the device's bins, with no device-to-host copy
+        ii = (torch.arange(h, dtype=torch.float32) - h / 2) ** 2
+        jj = (torch.arange(w, dtype=torch.float32) - w / 2) ** 2
+        wvn = torch.round(torch.sqrt(ii[:, None] + jj[None, :])).to(torch.int64)
+        p0 = (torch.arange(h) - h // 2) % h
+        p1 = (torch.arange(w) - w // 2) % w
+        shell = wvn[p0][:, p1].reshape(-1)
+        self.h, self.w, self.cutoff = h, w, min(h, w) // 2
+        order = torch.sort(shell, stable=True).indices        # (shell, q): q ascends inside a shell because the sort is stable
+        below = int((shell < self.cutoff).sum())
+        counts = torch.bincount(shell[shell < self.cutoff], minlength=self.cutoff)[:self.cutoff]
+        offsets = torch.zeros(self.cutoff + 1, dtype=torch.int64)
+        offsets[1:] = torch.cumsum(counts, 0)
+        self.shell = shell.to(torch.int32).to(device)
+        self.perm = order[:below].to(torch.int32).to(device)
+        self.offsets = offsets.to(torch.int32).to(device)
+
+
+_spectrum_plans = {}
+_SPECTRUM_PLANS_MAX = 16
+
+
+def spectrum_plan(h, w, device="cpu"):
+    """The cached SpectrumPlan of an h x w crop on `device` (at most 16 are kept, the oldest goes first)."""
+    key = (int(h), int(w), str(torch.device(device)))
+    plan = _spectrum_plans.pop(key, None)
+    if plan is None:
+        plan = SpectrumPlan(h, w, device)
+        while len(_spectrum_plans) >= _SPECTRUM_PLANS_MAX:
+            _spectrum_plans.pop(next(iter(_spectrum_plans)))
+    _spectrum_plans[key] = plan                                # (re-inserted: the dict's order is the order of last use)
+    return plan
+
+
+def _table_ptr(t):
+    """Device pointer of a table that may be empty (a crop one cell wide has no shell below its cutoff): the entries refuse NULL, and an
+    empty tensor has no address - one spare element stands in, which nothing reads."""
+    return N.ptr(t if t.numel() else t.new_zeros(1))
+
+
+def fused_centre_crop(flat, nx, ny, window):
+    """piso_loss_centre_crop: flat u-first face vector -> [2, h, w] float32, the crop of at_centers() (plane 0: v, plane 1: u)."""
+    y0, y1, x0, x1 = (int(v) for v in window)
+    out = torch.empty((2, max(y1 - y0, 0), max(x1 - x0, 0)), dtype=torch.float32, device=flat.device)
+    N.check(N.lib.piso_loss_centre_crop(N.ptr(flat), int(nx), int(ny), y0, y1, x0, x1, N.ptr(out), N.stream_ptr()), "piso_loss_centre_crop")
+    return out
+
+
+def fused_centre_crop_adjoint(d_planes, nx, ny, window):
+    """piso_loss_centre_crop_adjoint: the cotangent of the planes -> the cotangent of the whole flat face vector (gathering)."""
+    out = torch.empty((int(nx) + 1) * int(ny) + int(nx) * (int(ny) + 1), dtype=torch.float32, device=d_planes.device)
+    N.check(N.lib.piso_loss_centre_crop_adjoint(N.ptr(d_planes), int(nx), int(ny), *[int(v) for v in window], N.ptr(out), N.stream_ptr()),
+            "piso_loss_centre_crop_adjoint")
+    return out
+
+
+def fused_shell_sums(spec_real, plan):
+    """piso_loss_spectrum_shells: torch.view_as_real(fft2(planes)) [2, h, w, 2] -> E[cutoff] float64, the first `cutoff` entries of
+    EK_spectrum_2D_tf, summed in a fixed order."""
+    store = torch.empty(max(plan.cutoff, 1), dtype=torch.float64, device=spec_real.device)
+    N.check(N.lib.piso_loss_spectrum_shells(N.ptr(spec_real), _table_ptr(plan.perm), N.ptr(plan.offsets), plan.h, plan.w, plan.cutoff, N.ptr(store),
+                                            N.stream_ptr()), "piso_loss_spectrum_shells")
+    return store[:plan.cutoff]
+
+
+def fused_shell_sums_adjoint(spec_real, plan, d_energy, upstream=None):
+    """piso_loss_spectrum_shells_adjoint: (upstream *) d E -> the cotangent of the real view of the transform, a pure map."""
+    out = torch.empty_like(spec_real)
+    N.check(N.lib.piso_loss_spectrum_shells_adjoint(N.ptr(spec_real), N.ptr(plan.shell), _table_ptr(d_energy), N.ptr(upstream), plan.h, plan.w,
+                                                    plan.cutoff, N.ptr(out), N.stream_ptr()), "piso_loss_spectrum_shells_adjoint")
+    return out
+
+
+def fused_spectrum_distance(e_pred, e_gt, cutoff, start_wavenumber, log_distance, factor):
+    """piso_loss_spectrum_distance -> (value [1], d value / d e_pred [cutoff]), float64 on the device."""
+    out = torch.empty(1 + max(int(cutoff), 1), dtype=torch.float64, device=e_pred.device)
+    N.check(N.lib.piso_loss_spectrum_distance(_table_ptr(e_pred), _table_ptr(e_gt), int(cutoff), int(start_wavenumber), 1 if log_distance else 0,
+                                              C.c_double(float(factor)), N.ptr(out), N.ptr(out[1:]), N.stream_ptr()),
+            "piso_loss_spectrum_distance")
+    return out[:1], out[1:1 + int(cutoff)]
+
+
+class _CentreCrop(torch.autograd.Function):
+    """cfg = (nx, ny, window): the flat face vector -> the cropped planes at the cell centres; reverse mode is the gathering adjoint."""
+
+    @staticmethod
+    def forward(ctx, flat, cfg):
+        ctx.cfg = cfg
+        return fused_centre_crop(flat, *cfg)
+
+    @staticmethod
+    def backward(ctx, g):
+        return fused_centre_crop_adjoint(g.to(torch.float32).contiguous(), *ctx.cfg), None
+
+
+class _SpectrumDistance(torch.autograd.Function):
+    """The real view of the prediction's transform, the ground truth's shell energies -> the loss term as a float32 scalar (shell sums +
+    distance, two launches).  cfg = (start_wavenumber, log_distance, factor).  Reverse mode is ONE map over the coefficients: the distance
+    launch has left d value / d E on the device, the upstream scalar is read there too."""
+
+    @staticmethod
+    def forward(ctx, spec_real, e_gt, plan, cfg):
+        e = fused_shell_sums(spec_real, plan)
+        value, d_e = fused_spectrum_distance(e, e_gt, plan.cutoff, *cfg)
+        ctx.plan = plan
+        ctx.save_for_backward(spec_real, d_e)
+        return value[0].to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, g):
+        spec_real, d_e = ctx.saved_tensors
+        return fused_shell_sums_adjoint(spec_real, ctx.plan, d_e, g.to(torch.float32).reshape(1).contiguous()), None, None, None
+
+
+def _fused_spectral(field, truth_frame, buffer_width, sponge_start, log_distance, start_wavenumber, factor):
+    """One step's term of spectral_energy_loss(fused=True) on a whole-grid field: centre + crop -> torch.fft.fft2 (rocFFT) -> shell sums ->
+    distance; the ground-truth frame through the same kernels without a graph."""
+    from .fused import flat_faces
+    ny, nx = (int(r) for r in field.resolution)
+    pred = flat_faces(field).to(torch.float32).contiguous()
+    if not pred.is_cuda:
+        raise N.PisoNativeError("spectral_energy_loss(fused=True) needs device tensors; got a %s field (there is no CPU form of the fused "
+                                "losses)" % pred.device)
+    target = flat_faces(StaggeredGrid(truth_frame)).to(device=pred.device, dtype=torch.float32).contiguous()
+    window = spectrum_window(buffer_width, sponge_start, ny, nx)
+    plan = spectrum_plan(window[1] - window[0], window[3] - window[2], pred.device)
+    with torch.no_grad():
+        e_gt = fused_shell_sums(torch.view_as_real(torch.fft.fft2(fused_centre_crop(target, nx, ny, window))).contiguous(), plan)
+    spec = torch.view_as_real(torch.fft.fft2(_CentreCrop.apply(pred, (nx, ny, window)))).contiguous()
+    return _SpectrumDistance.apply(spec, e_gt, plan, (int(start_wavenumber), bool(log_distance), float(factor)))
+
+
 class _GatherFaces(torch.autograd.Function):
     """The rank's stored rows -> the whole grid's flat face vector on every rank (distributed.gather_face_rows).  Every rank then evaluates
     the SAME function of the replicated field and contributes value / world: the cotangent that arrives is 1 / world of the whole gradient,
@@ -236,7 +399,14 @@ def L2_field_loss(loss, fields, ground_truths, step_range, buffer_width, loss_fa
 def spectral_energy_loss(loss, velocity_fields, ground_truths, step_range, buffer_width=[[0, 0], [0, 0]], loss_factor=1,
                          sponge_start=0, log_distance=True, start_wavenumber=0, sum_steps=True, loss_influence_range=None,
                          **kwargs):
-    """losses.py:38-64: distance between the shell-summed energy spectra of prediction and ground truth (first batch entry)."""
+    """losses.py:38-64: distance between the shell-summed energy spectra of prediction and ground truth (first batch entry).
+
+    fused=True (device tensors only): the kernels of csrc/loss_spectrum.hip either side of torch.fft.fft2 - centre + crop, shell sums in
+    float64 over tables cached per crop shape (`spectrum_plan`), the distance - instead of the torch expression: no atomics (the same bits
+    on every run, where index_add_ is non-deterministic on the GPU), no host read, a float32 scalar per step.  Same shells, same
+    meaning of every argument and the same return shapes.  One deliberate difference: identical spectra in the log form (a sum of exactly
+    0) give value 0 and gradient 0, where the torch path's sqrt'(0) returns NaN gradients.  A shell of zero or non-finite energy inside the
+    log form's range still gives a non-finite value."""
     step_range = _step_range(step_range)
     if not isinstance(loss_factor, list):
         loss_factor = [loss_factor for _ in range(step_range[1])]
@@ -245,6 +415,12 @@ def spectral_energy_loss(loss, velocity_fields, ground_truths, step_range, buffe
         vel, share = velocity_fields[0][s], None
         if isinstance(vel, SlabStaggered):                   # the replicated whole field; this rank's part is value / world
             vel, share = _gathered_grid(vel), 1.0 / vel.sharding.world
+        if kwargs.get("fused", False):
+            contrib.append(_fused_spectral(vel, ground_truths[0][:, s, ...], buffer_width, sponge_start, log_distance, start_wavenumber,
+                                           loss_factor[s]))
+            if share is not None:
+                contrib[-1] = contrib[-1] * share
+            continue
         central = vel.at_centers().data
         if sponge_start == 0:
             sponge_start = central.shape[2]

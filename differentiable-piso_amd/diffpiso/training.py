@@ -141,9 +141,12 @@ class _Run(object):
         td = self.td
         loss = torch.zeros((), device=self.device) if td["sum_steps"] else [torch.zeros((), device=self.device)] * td["step_count"]
         contributions = []
+        # training_dict["fused_losses"]: every loss function is called with fused=True (losses.py: the kernels of csrc/loss.hip and
+        # csrc/loss_spectrum.hip; the multistep loss takes the keyword and ignores it).  Absent: the calls as they always were.
+        fused = {"fused": True} if td.get("fused_losses") else {}
         for fn, factor in zip(td["loss_functions"], td["loss_factor"]):
             loss, contrib = fn(loss, [steps], [target], td["step_count"], self.loss_buffer_width, factor, self.sponge_start,
-                               sum_steps=td["sum_steps"], loss_influence_range=td.get("loss_influence_range"))
+                               sum_steps=td["sum_steps"], loss_influence_range=td.get("loss_influence_range"), **fused)
             contributions.append(float(sum(torch.as_tensor(c).sum() for c in (contrib if isinstance(contrib, list) else [contrib]))))
         total = loss if td["sum_steps"] else sum(loss)
         return total, contributions

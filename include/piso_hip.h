@@ -811,6 +811,42 @@ int piso_loss_strain_grad(const float* pred, const float* target, int nx, int ny
 int piso_loss_strain_grad_slab(const float* pred, const float* target, int nx, int ny, float dx, float dy, double factor, const float* upstream,
                                float* d_pred, piso_stream_t stream, const piso_slab_t* slab);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Spectral-energy loss around the transform (csrc/loss_spectrum.hip; the reference's losses.py:38-64 over evaluation_tools.py:157-186).
+ * The FFT itself is the caller's (rocFFT); these are the passes either side of it.  Whole-grid kernels, no atomics, no workspace: every
+ * output is the same bits on every run of the same launch.
+ *
+ * piso_loss_centre_crop:  flat u-first face vector -> planes [2][h][w] float32, the crop of the field at the cell centres.  The crop lives
+ *   on CELL indices: cell (j, i) counts iff y0 <= j < y1 and x0 <= i < x1 (0 <= y0 < y1 <= ny, 0 <= x0 < x1 <= nx); h = y1 - y0, w = x1 - x0.
+ *   plane 0 (v at the centres): 0.5f * (v[j+1][i] + v[j][i]);  plane 1 (u at the centres): 0.5f * (u[j][i+1] + u[j][i]).
+ * piso_loss_centre_crop_adjoint:  d_planes [2][h][w] -> d_faces (the WHOLE flat vector is written): one thread per face gathers
+ *   0.5f * d_planes of the at most two cropped cells that read the face; 0 for a face no cropped cell reads.
+ *
+ * piso_loss_spectrum_shells:  spec = the complex64 transform of the planes, [2][h][w] interleaved (re, im) floats, UNSHIFTED.
+ *   energy[k] = 0.5 / (h w)^2 * sum over the coefficients q of shell k of (|spec[0][q]|^2 + |spec[1][q]|^2), 0 <= k < cutoff, float64.
+ *   The shells come as a table: perm[offsets[k]] .. perm[offsets[k + 1] - 1] are the flat indices q = q0 * w + q1 of shell k (int32, offsets
+ *   has cutoff + 1 entries, entries of perm outside [0, h w) are skipped).  One workgroup per shell, strided by thread, fixed-order block sum.
+ * piso_loss_spectrum_shells_adjoint:  d_spec[c][q] = upstream[0] * 2 * 0.5 / (h w)^2 * d_energy[shell[q]] * spec[c][q] for both floats of the
+ *   pair - the cotangent of the REAL view of the transform -, 0 where shell[q] is not in [0, cutoff).  shell: int32 [h w], the shell of
+ *   every unshifted coefficient.  upstream: ONE float on the device, or NULL for 1.
+ *
+ * piso_loss_spectrum_distance:  one workgroup; value[0] and d_e_pred[k] = d value / d e_pred[k] (all cutoff entries are written), float64.
+ *     log_distance != 0:  factor * sqrt(sum over k >= 1 + start_wavenumber of log(e_gt[k] / e_pred[k])^2)
+ *     log_distance == 0:  factor * sum over k >= 1 of |e_gt[k] - e_pred[k]|  (start_wavenumber is ignored, as in the reference)
+ *   An empty range (cutoff <= 1 + start_wavenumber) gives 0.  A sum of exactly 0 in the log form (identical spectra) gives value 0 and
+ *   gradient 0.  A zero or non-finite energy inside the range of the log form gives a non-finite value (log of 0, of infinity or of 0 / 0).
+ * NULL pointers (upstream excepted), h or w below 1, a crop outside the grid, cutoff outside [0, min(h, w) / 2], a negative
+ * start_wavenumber: PISO_ERR_INVALID_ARG before any launch.
+ * ------------------------------------------------------------------------------------------------------------- */
+int piso_loss_centre_crop(const float* faces, int nx, int ny, int y0, int y1, int x0, int x1, float* planes, piso_stream_t stream);
+int piso_loss_centre_crop_adjoint(const float* d_planes, int nx, int ny, int y0, int y1, int x0, int x1, float* d_faces, piso_stream_t stream);
+int piso_loss_spectrum_shells(const float* spec, const int* perm, const int* offsets, int h, int w, int cutoff, double* energy,
+                              piso_stream_t stream);
+int piso_loss_spectrum_shells_adjoint(const float* spec, const int* shell, const double* d_energy, const float* upstream, int h, int w, int cutoff,
+                                      float* d_spec, piso_stream_t stream);
+int piso_loss_spectrum_distance(const double* e_pred, const double* e_gt, int cutoff, int start_wavenumber, int log_distance, double factor,
+                                double* value, double* d_e_pred, piso_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
